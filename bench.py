@@ -11,9 +11,11 @@ One step = rollout forward + MSE + BPTT backward (one hipGraph) + gradient all-r
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        (no launcher: starts the command above itself, see spawn_ranks)
 
-The N = 1 line carries, after the headline: "secondary" = configs[2] (SFNO) on the reference's dlwpbench protocol and "tertiary" =
-configs[3] (Swin, Pangu at 128x256, window 7) and configs[4] (FourCastNet AFNO at 721x1440), each with its own value, roofline
-(the kernel that leads that workload's step, measured live) and cpu_baseline.
+A plain run sets up, warms up, times --steps steps and prints the headline line (--dump-outputs DIR also writes what the last
+timed step computed).  With --full the N = 1 line carries, after the headline: roofline probes of the step's leading kernels, a
+CPU baseline, "secondary" = configs[2] (SFNO) on the reference's dlwpbench protocol and "tertiary" = configs[3] (Swin, Pangu at
+128x256, window 7) and configs[4] (FourCastNet AFNO at 721x1440), each with its own value, roofline (the kernel that leads that
+workload's step, measured live) and cpu_baseline.  --workload X lines carry their roofline and cpu_baseline with --full too.
 """
 import argparse
 import json
@@ -45,12 +47,17 @@ def parse():
     ap.add_argument("--T", type=int, default=None, help="frames per trajectory of the fno workload (default 20 = the headline; the "
                     "reference's own protocol is sequence_length 50 -> --T 49: 40 net calls per sample, "
                     "src/nsbench/configs/training/default.yaml:6, scripts/train_commands.txt:83)")
-    ap.add_argument("--no-secondary", action="store_true", help="fno workload at N=1: do not append the short SFNO (configs[2]) run "
+    ap.add_argument("--full", action="store_true", help="N = 1: besides the headline, measure the roofline probes, the CPU baseline and "
+                    "(fno workload) the \"secondary\" and \"tertiary\" runs; the --no-* options below drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(loss and parameters after the update; fno workload: the rollout prediction too) as DIR/<name>.npy, "
+                    "float32, at most 64 MB in all: an array above its share is replaced by a fixed seeded sample of its elements")
+    ap.add_argument("--no-secondary", action="store_true", help="--full, fno workload at N=1: do not append the short SFNO (configs[2]) run "
                     "as the line's \"secondary\" object")
-    ap.add_argument("--no-tertiary", action="store_true", help="fno workload at N=1: do not append the configs[3] / [4] runs (Swin, Pangu, "
-                    "AFNO 721x1440) as the line's \"tertiary\" list")
-    ap.add_argument("--time-budget", type=float, default=420.0, help="wall seconds the default N = 1 run may take (from process start): the "
-                    "tertiary workloads and their CPU legs are skipped once it is nearly used up (the driver stops bench.py at 600 s)")
+    ap.add_argument("--no-tertiary", action="store_true", help="--full, fno workload at N=1: do not append the configs[3] / [4] runs (Swin, "
+                    "Pangu, AFNO 721x1440) as the line's \"tertiary\" list")
+    ap.add_argument("--time-budget", type=float, default=420.0, help="wall seconds a --full N = 1 run may take (from process start): the "
+                    "tertiary workloads and their CPU legs are skipped once it is nearly used up")
     ap.add_argument("--no-spawn", action="store_true", help="--gpus N > 1 without a launcher (WORLD_SIZE unset): exit with an error that "
                     "names the torch.distributed.run command instead of starting the N ranks")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
@@ -61,9 +68,9 @@ def parse():
     ap.add_argument("--no-clip", action="store_true", help="dlwpbench workloads: no gradient clipping (the reference's training protocol "
                     "clips at max_norm = learning rate before every optimizer step: src/dlwpbench/configs/training/default.yaml:3, "
                     "scripts/train.py:133-135; on by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: no roofline probes")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample (--full)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for the "
                     "single-GPU functional test of the N>1 code path)")
     ap.add_argument("--share-device", action="store_true", help="all ranks use cuda:0 (functional test only)")
@@ -112,6 +119,25 @@ def spawn_ranks(args):
     print("bench.py: WORLD_SIZE unset with --gpus %d: starting %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
+
+
+DUMP_BUDGET_BYTES = 60_000_000          # under the 64 MB a dump may take, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32.  A tensor with more elements than
+    its equal share of DUMP_BUDGET_BYTES is written as a sample of that many elements, flattened, at indices drawn from a generator
+    seeded with 0: the same positions in every run, so two builds compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > share:
+            idx = torch.randint(0, a.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
 
 
 PEAK_HBM_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
@@ -718,7 +744,7 @@ def dlwp_cpu_baseline(workload, B, budget_s, clip=None, threads=None):
 
 
 def main_sfno(args):
-    line = run_dlwp(args, args.workload, args.steps, args.warmup, init_dist=True)
+    line = run_dlwp(args, args.workload, args.steps, args.warmup, init_dist=True, dump_dir=args.dump_outputs)
     if line is not None:
         print(json.dumps(line), flush=True)
 
@@ -743,11 +769,12 @@ def rank_evidence(dist, device, backend, dt, steps):
     return {"backend": backend, "rccl_ranks": world if backend == "nccl" else 0, "world_size": world, "rccl_version": ver, "ranks": box}
 
 
-def run_dlwp(args, workload, steps, warmup, init_dist, roofline=True, cpu=True, batch=None, clip=None):
+def run_dlwp(args, workload, steps, warmup, init_dist, roofline=True, cpu=True, batch=None, clip=None, dump_dir=None):
     """BASELINE configs[2] (sfno) and the supplementary configs[3] / [4] lines (pangu, swin, afno): one step = rollout + MSE +
     backward + all-reduce (N>1) + fused Adam through train_engine.GraphedTrainStep (captured in a hipGraph at N = 1 and for the
     flat reducer; the 28-72 M parameter models use the bucketed reducer launched from backward hooks at N > 1: eager step).
-    Returns the JSON line (rank 0) or None."""
+    roofline / cpu: allow those objects of a --full line.  dump_dir: --dump-outputs of this run.  Returns the JSON line (rank 0)
+    or None."""
     import torch
     import torch.distributed as dist
     from dlwp_benchmark_amd import ddp, dlwpbench, lib as L
@@ -823,6 +850,8 @@ def run_dlwp(args, workload, steps, warmup, init_dist, roofline=True, cpu=True, 
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"loss": step.loss, "params": step.flat})          # (the fused Adam step zeroes the gradients)
     line = None
     if rank == 0:
         line = {"metric": w["metric"],
@@ -850,14 +879,14 @@ def run_dlwp(args, workload, steps, warmup, init_dist, roofline=True, cpu=True, 
             line["config"]["buckets_overlapped"] = getattr(step.allreduce, "overlapped", None)
         if evidence is not None:
             line["ranks"] = evidence
-        if world == 1 and not args.no_roofline and roofline:
+        if world == 1 and args.full and not args.no_roofline and roofline:
             if workload == "sfno" and precision == "bf16" and storage == "bf16":
                 line["roofline"] = sfno_dominant_probe(device, B)
             elif workload == "sfno":
                 line["roofline"] = sfno_gemm_probe(device, B, precision, storage=storage, shape=w["gemm"])
             else:
                 line["roofline"] = live_dominant_roofline(step, workload)
-        if world == 1 and not args.no_cpu_baseline and cpu:
+        if world == 1 and args.full and not args.no_cpu_baseline and cpu:
             del step
             torch.cuda.empty_cache()
             line["cpu_baseline"] = (sfno_cpu_baseline(B, args.cpu_seconds, clip=clip_max_norm) if workload == "sfno" else
@@ -946,6 +975,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        # the prediction of the last timed step is the output buffer of the trainer that step ran on
+        tr = model.trainer(B, w["T"], w["H"], w["W"], min(w["teacher_forcing_steps"], w["T"]))
+        dump_outputs(args.dump_outputs, {"loss": loss, "prediction": tr.out, "params": model.flat_params})
 
     if rank == 0:
         ncalls = w["T"] - w["context_size"] + 1
@@ -966,7 +999,7 @@ def main():
         if evidence is not None:
             line["ranks"] = evidence
             line["config"]["grad_reduce"] = "one all-reduce of the flat gradient buffer between the graph replays"
-        if world == 1 and not args.no_roofline:
+        if world == 1 and args.full and not args.no_roofline:
             line["roofline"] = roofline_probe(device, B)
             if B <= 8 and args.hidden is None:
                 # how to read a fraction this low: at the reference's batch size the step is a serial chain of 215 launches of
@@ -998,9 +1031,9 @@ def main():
             if w["hidden_channels"] <= 64:          # the fused lifting kernel exists for narrow layers only
                 line["roofline_mfma"] = mfma_probe(device, B)
             line["roofline_mix"] = mix_probe(device, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(B, args.cpu_seconds)
-        if world == 1 and not args.no_secondary and args.hidden is None and args.T is None:
+        if world == 1 and args.full and not args.no_secondary and args.hidden is None and args.T is None:
             # the other half of BASELINE's metric ("FNO 64^2, SFNO 32x64") in the same driver-timed record: a short run of
             # configs[2] with its own roofline object (python bench.py --workload sfno prints the full line)
             del model, opt
@@ -1023,7 +1056,7 @@ def main():
                 L.set_gemm_precision("bf16" if prev_precision == 1 else "fp32")
                 if prev_storage == "bf16" and prev_precision == 1:
                     L.set_storage("bf16")
-        if world == 1 and not args.no_tertiary and args.hidden is None and args.T is None:
+        if world == 1 and args.full and not args.no_tertiary and args.hidden is None and args.T is None:
             # BASELINE configs[3] (Swin, Pangu: 128 x 256, window 7) and configs[4] (FourCastNet AFNO on 721 x 1440) in the same
             # driver-timed record: value, roofline of the kernel that leads each step (live) and a bounded cpu_baseline each
             # (python bench.py --workload swin|pangu|afno721 prints a full line)

@@ -1,6 +1,6 @@
 """bench.py host logic that needs no GPU: the N > 1 launch guard (round-5 verdict: `python bench.py --gpus 8` without a launcher
-silently benchmarked ONE GPU and printed "n_gpus": 1) and the helpers that pick the roofline kernel from a committed rocprofv3
-step table (profiles/*_step_kernel_stats.csv)."""
+silently benchmarked ONE GPU and printed "n_gpus": 1), the --dump-outputs writer and the helpers that pick the roofline kernel from a
+committed rocprofv3 step table (profiles/*_step_kernel_stats.csv)."""
 import os
 import subprocess
 import sys
@@ -40,6 +40,26 @@ def test_world_size_mismatch_is_refused():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--steps", "1", "--warmup", "0"], env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_dump_outputs_stays_under_64_mb_with_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: small arrays are written whole with their shape, a large one as a sample of fixed positions, 64 MB at most."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.randn(40_000_000, generator=torch.Generator().manual_seed(1))
+    arrays = {"loss": torch.tensor(0.5), "prediction": torch.randn(2, 3, 4), "params": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["loss.npy", "params.npy", "prediction.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    assert np.load(tmp_path / "a" / "loss.npy") == np.float32(0.5)
+    assert np.array_equal(np.load(tmp_path / "a" / "prediction.npy"), arrays["prediction"].numpy())
+    pa, pb = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "b" / "params.npy")
+    assert pa.dtype == np.float32 and 0 < pa.size < big.numel() and np.array_equal(pa, pb)
+    assert np.isin(pa[:100], big.numpy()).all()          # sampled elements, not a reduction of them
 
 
 def test_kernel_short_name_and_committed_tables():

@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 O=$R/gpurun_out/final_r02
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python3 $R/bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 600 python3 $R/bench.py --full > $O/bench_line.json 2> $O/bench.err
 echo "bench done"; tail -c 400 $O/bench_line.json
-timeout 300 python3 $R/bench.py --hidden 217 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_line_h217.json 2>> $O/bench.err
+timeout 300 python3 $R/bench.py --full --hidden 217 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_line_h217.json 2>> $O/bench.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-roofline > /dev/null 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_h217 -- python3 $R/bench.py --hidden 217 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > /dev/null 2>&1
 echo "step profiles done"
@@ -22,8 +22,8 @@ python3 $R/tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write fno_spatial_kernel $O/
 echo "probes done"
 timeout 400 python3 $R/tools/bench_fft.py > $O/fft_bench.txt 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fft -- python3 $R/tools/probe_fft.py > /dev/null 2>&1
-timeout 400 python3 $R/bench.py --workload sfno > $O/bench_line_sfno.json 2> $O/bench_sfno.err
-for wl in swin pangu afno; do timeout 300 python3 $R/bench.py --workload $wl --steps 20 --warmup 3 > $O/bench_line_$wl.json 2>> $O/bench_sfno.err; done
+timeout 400 python3 $R/bench.py --full --workload sfno > $O/bench_line_sfno.json 2> $O/bench_sfno.err
+for wl in swin pangu afno; do timeout 300 python3 $R/bench.py --full --workload $wl --steps 20 --warmup 3 > $O/bench_line_$wl.json 2>> $O/bench_sfno.err; done
 timeout 900 python3 $R/tools/bench_models.py all --steps 10 > $O/models.jsonl 2> $O/models.err
 for m in fno_dlwp tfno_dlwp fno_ctx swin_dlwp; do timeout 250 python3 $R/tools/bench_models.py $m --steps 20 >> $O/models.jsonl 2>> $O/models.err; done
 timeout 400 python3 $R/tools/bench_models.py afno_c5p1 --steps 3 >> $O/models.jsonl 2>> $O/models.err

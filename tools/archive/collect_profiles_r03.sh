@@ -9,10 +9,10 @@ mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 prof() { d=$1; shift; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$d -- python3 "$@" > /dev/null 2>&1; find $O/$d -name "*_kernel_trace.csv" -delete; }
 if [ "$1" = "a" ]; then
-  timeout 600 python3 $R/bench.py > $O/bench_line.json 2> $O/bench.err
+  timeout 600 python3 $R/bench.py --full > $O/bench_line.json 2> $O/bench.err
   echo "bench done"; cut -c1-300 $O/bench_line.json
   timeout 200 python3 $R/bench.py --T 49 --steps 50 --warmup 5 --no-cpu-baseline --no-roofline > $O/bench_line_T49.json 2>> $O/bench.err
-  timeout 300 python3 $R/bench.py --hidden 217 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_line_h217.json 2>> $O/bench.err
+  timeout 300 python3 $R/bench.py --full --hidden 217 --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_line_h217.json 2>> $O/bench.err
   for b in 1 2 8 16 32 64; do timeout 200 python3 $R/bench.py --batch $b --steps 40 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary >> $O/bench_batch_sweep.jsonl 2>> $O/bench.err; done
   prof prof_bench $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary
   prof prof_probe $R/tools/probe_spatial.py
@@ -24,8 +24,8 @@ if [ "$1" = "a" ]; then
   timeout 400 python3 $R/tools/bench_fft.py > $O/fft_bench.txt 2>&1
   cat $O/traffic.log; cut -c1-200 $O/bench_line_T49.json
 else
-  timeout 400 python3 $R/bench.py --workload sfno > $O/bench_line_sfno.json 2> $O/bench_b.err
-  for wl in swin pangu afno afno721; do timeout 300 python3 $R/bench.py --workload $wl --steps 20 --warmup 3 > $O/bench_line_$wl.json 2>> $O/bench_b.err; echo "$wl done"; done
+  timeout 400 python3 $R/bench.py --full --workload sfno > $O/bench_line_sfno.json 2> $O/bench_b.err
+  for wl in swin pangu afno afno721; do timeout 300 python3 $R/bench.py --full --workload $wl --steps 20 --warmup 3 > $O/bench_line_$wl.json 2>> $O/bench_b.err; echo "$wl done"; done
   prof prof_bf16s_sfno $R/bench.py --workload sfno --steps 20 --warmup 3 --no-cpu-baseline --no-roofline
   for m in afno_fcn pangu_c4 swin_c4; do prof prof_bf16s_$m $R/tools/bench_models.py $m --steps 3 --precision bf16 --storage bf16; done
   timeout 300 python3 $R/tools/bench_gemm.py > $O/gemm_bench.txt 2>&1

@@ -23,14 +23,14 @@ if [ "$1" = "b" ]; then
   cat $O/traffic.log
   for d in prof_bench prof_bf16s_sfno_b16 prof_bf16s_swin prof_bf16s_pangu prof_bf16s_afno prof_bf16s_afno721; do f=$(ls -t $O/$d/*/*kernel_stats.csv 2>/dev/null | head -1); echo "== $d"; [ -n "$f" ] && python3 $R/tools/kernel_table.py $f 1 4; done
 else
-  ( time timeout 560 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err ) 2> $O/bench.time
+  ( time timeout 560 python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err ) 2> $O/bench.time
   echo "bench done"; cat $O/bench.time; cut -c1-300 $O/bench_line.json
   timeout 200 python3 $R/bench.py --T 49 --steps 50 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --no-tertiary > $O/bench_line_T49.json 2>> $O/bench.err
-  timeout 300 python3 $R/bench.py --hidden 217 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-tertiary > $O/bench_line_h217.json 2>> $O/bench.err
+  timeout 300 python3 $R/bench.py --full --hidden 217 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-tertiary > $O/bench_line_h217.json 2>> $O/bench.err
   for b in 1 2 8 16 32 64; do timeout 200 python3 $R/bench.py --batch $b --steps 40 --warmup 5 --no-cpu-baseline --no-roofline --no-secondary --no-tertiary >> $O/bench_batch_sweep.jsonl 2>> $O/bench.err; done
-  timeout 400 python3 $R/bench.py --workload sfno > $O/bench_line_sfno.json 2>> $O/bench.err
-  timeout 200 python3 $R/bench.py --workload sfno --batch 4 --no-clip > $O/bench_line_sfno_b4.json 2>> $O/bench.err
-  for wl in swin pangu afno afno721; do timeout 300 python3 $R/bench.py --workload $wl --steps 20 --warmup 3 --cpu-seconds 5 > $O/bench_line_$wl.json 2>> $O/bench.err; echo "$wl done"; done
+  timeout 400 python3 $R/bench.py --full --workload sfno > $O/bench_line_sfno.json 2>> $O/bench.err
+  timeout 200 python3 $R/bench.py --full --workload sfno --batch 4 --no-clip > $O/bench_line_sfno_b4.json 2>> $O/bench.err
+  for wl in swin pangu afno afno721; do timeout 300 python3 $R/bench.py --full --workload $wl --steps 20 --warmup 3 --cpu-seconds 5 > $O/bench_line_$wl.json 2>> $O/bench.err; echo "$wl done"; done
   for f in sfno sfno_b4 swin pangu afno afno721; do cut -c1-200 $O/bench_line_$f.json; done
 fi
 echo "=== done $1"
