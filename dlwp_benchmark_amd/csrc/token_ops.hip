@@ -1192,6 +1192,15 @@ __global__ __launch_bounds__(256) void gemm_slab_reduce_kernel(const float* __re
         for (int k = 0; k < 4; ++k) cp[k] = v[k];
     }
 }
+// the launch of both sliced weight-gradient kernels (C accumulates: the caller zeroed it for its own split-K when it does not);
+// accounting: one add per slice and element, every slice plane read once, C read and written once
+static void gemm_slab_reduce_launch(const float* slab, float* C, int M, int N, int ldc, int slices, hipStream_t s) {
+    const long long units = (long long)M * (N / 4);
+    const double mn = (double)M * N;
+    dlwp_prof_scope prof(s, mn * slices, 4.0 * mn * (slices + 2), "gemm_slab_reduce_kernel");
+    hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)std::min<long long>((units + 255) / 256, 2048)), dim3(256), 0, s,
+                       slab, C, M, N, ldc, slices, 1);
+}
 
 // Scratch for the slices of the sliced weight-gradient kernel.  One slab per DEVICE, grow-only and never freed: a hipGraph captured
 // earlier keeps the pointer it was captured with, so a slab that was handed out once must stay valid for the life of the
@@ -1273,12 +1282,8 @@ static int gemm_glds_tn_launch(const GemmDev& a_in, hipStream_t s) {
         hipLaunchKernelGGL(gemm_glds_tn_kernel<64>, grid, dim3(256), lds, s, a);
     }
     }
-    if (a.slab) {
-        // the caller zeroed C for its own split-K when it does not accumulate: adding to it is the same either way
-        const long long units = (long long)a.M * (a.N / 4);
-        hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)std::min<long long>((units + 255) / 256, 2048)), dim3(256), 0, s,
-                           a.slab, a.C, a.M, a.N, a.ldc, (int)grid.z, 1);
-    }
+    // the caller zeroed C for its own split-K when it does not accumulate: adding to it is the same either way
+    if (a.slab) gemm_slab_reduce_launch(a.slab, a.C, a.M, a.N, a.ldc, (int)grid.z, s);
     return DLWP_OK;
 }
 
@@ -1848,10 +1853,11 @@ static int gemm_p8_tn_launch(const GemmDev& a_in, hipStream_t s, bool* taken) {
     const size_t lds = (size_t)2 * 4 * 128 * 64 * 2;
     int rc;
     if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_p8_tn_kernel), lds, "gemm_p8_tn"))) return rc;
+    {
+    dlwp_prof_scope prof(s, gemm_prof_flops(a), gemm_prof_bytes(a), "gemm_p8_tn_kernel%s", gemm_prof_tag(a).s);
     hipLaunchKernelGGL(gemm_p8_tn_kernel, dim3(std::min(tiles * splits, ncu)), dim3(512), lds, s, a);
-    const long long units = (long long)a.M * (a.N / 4);
-    hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)std::min<long long>((units + 255) / 256, 2048)), dim3(256), 0, s,
-                       a.slab, a.C, a.M, a.N, a.ldc, splits, 1);
+    }
+    gemm_slab_reduce_launch(a.slab, a.C, a.M, a.N, a.ldc, splits, s);
     *taken = true;
     return DLWP_OK;
 }
@@ -1890,15 +1896,22 @@ static int gemm_queue_flush(hipStream_t s) {
         gz = std::max(gz, (unsigned)(q.gg.g[i].nbatch * q.gg.g[i].splits));
     }
     const dim3 grid(gx, q.n, gz);
+    double flops = 0, bytes = 0;
+    for (int i = 0; i < q.n; ++i) {
+        flops += gemm_prof_flops(q.gg.g[i]);
+        bytes += gemm_prof_bytes(q.gg.g[i]);
+    }
     int rc;
     if (g_gemm_bf16) {
         constexpr int KS = gemm_bf_kstep(0, 1, false, false);
         const size_t lds = sizeof(float) * 4 * ((64 * (KS + 8) > KS * (64 + 8) ? 64 * (KS + 8) : KS * (64 + 8)) / 2);
         if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_group_any_kernel<true>), lds, "gemm_group_any"))) return rc;
+        dlwp_prof_scope prof(s, flops, bytes, "gemm_group_any_kernel<true>");
         hipLaunchKernelGGL(gemm_group_any_kernel<true>, grid, dim3(256), lds, s, q.gg);
     } else {
         const size_t lds = sizeof(float) * 4 * Tile<1>::FLOATS;
         if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_group_any_kernel<false>), lds, "gemm_group_any"))) return rc;
+        dlwp_prof_scope prof(s, flops, bytes, "gemm_group_any_kernel<false>");
         hipLaunchKernelGGL(gemm_group_any_kernel<false>, grid, dim3(256), lds, s, q.gg);
     }
     q.n = 0;

@@ -2,6 +2,8 @@
 exactly what the bf16-operand GEMM gives on the same values held in fp32 (the matrix units round the operands to bf16 either
 way), outputs are the fp32 results rounded once, and a train step with bf16 hidden activations + the engine's bf16 weight copy
 stays within bf16 rounding of the fp32-storage step."""
+import contextlib
+
 import pytest
 import torch
 import torch.nn as nn
@@ -271,9 +273,11 @@ def test_sfno_train_step_with_bf16_storage_tracks_fp32_storage(cuda):
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (1000, 384, 192), (8192, 576, 192), (130, 128, 64), (4100, 768, 3072), (32768, 384, 96)])
 @pytest.mark.parametrize("epi", ["plain", "bias_gelu_preact_bf16", "residual_fp32", "gelu_grad_mul", "res_pre_accumulate"])
 def test_lds_dma_bf16_gemm_matches_the_register_staged_kernel(cuda, monkeypatch, M, N, K, epi):
-    """y = x W^T with both operands bf16 arrays: the 128 x 128 x 64 LDS-DMA kernel (csrc/token_ops.hip, gemm_glds_nt_kernel)
-    against the register-staged kernel (DLWP_GEMM_NOGLDS is read once per process, so the oracle here is a float64 product of
-    the bf16-rounded operands) for every epilogue the token layers use, with edge tiles in M and N."""
+    """y = x W^T with both operands bf16 arrays: the 128 x 128 LDS-DMA kernel (csrc/token_ops.hip, gemm_glds_kernel<true, ..>, taken at
+    every shape through GEMM_GLDS_FORCE: the shape rule alone leaves the small ones on the register-staged kernel) against a float64
+    product of the bf16-rounded operands for every epilogue the token layers use, with edge tiles in M and N.  The one exception is the
+    bare fp32 product of 4100 x 768 x 3072: the entry cuts it along K (float atomics) before any kernel is chosen, and no LDS-DMA
+    kernel takes a split-K product -- it runs on the register-staged kernel, and the test says so."""
     from dlwp_benchmark_amd import lib as L
     from dlwp_benchmark_amd.token_ops import _gemm, _gemm_batched
     g = torch.Generator().manual_seed(M + N + K)
@@ -281,7 +285,9 @@ def test_lds_dma_bf16_gemm_matches_the_register_staged_kernel(cuda, monkeypatch,
     w = (torch.randn(N, K, generator=g) / K ** 0.5).to(cuda).to(torch.bfloat16)
     bias = torch.randn(N, generator=g).to(cuda)
     ref = x.double() @ w.double().T
-    with L.gemm_precision("bf16"):
+    with contextlib.ExitStack() as knobs, L.gemm_precision("bf16"), L.kernel_accounting() as acc:
+        L.set_tuning("GEMM_GLDS_FORCE", 1)
+        knobs.callback(L.set_tuning, "GEMM_GLDS_FORCE", None)
         if epi == "plain":
             y = torch.empty(M, N, device=cuda)
             _gemm(x, w, y, M, N, K, K, K, N, 0, 1)
@@ -311,7 +317,10 @@ def test_lds_dma_bf16_gemm_matches_the_register_staged_kernel(cuda, monkeypatch,
             y0 = y.double().clone()
             _gemm_batched(x, w, y, M, N, K, K, K, N, 0, 1, bias=bias, act=1, residual=r, res_pre=1, accumulate=1)
             want = y0 + torch.nn.functional.gelu(ref + bias.double() + r.double())
-    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+    names = [r["name"] for r in acc.rows if r["name"].startswith("gemm")]
+    split_k = epi == "plain" and K >= 256 and (M, N) == (4100, 768)
+    assert len(names) == 1 and names[0].startswith("gemm_kernel<true, true," if split_k else "gemm_glds_kernel<true,"), names
     tol = 1e-2 if y.dtype == torch.bfloat16 else 2e-5
     assert ((y.double() - want).abs().max() / want.abs().max()).item() <= tol
 
@@ -365,8 +374,9 @@ def test_tile256_two_group_gemm_matches_float64(cuda, M, N, K, epi):
     bias = torch.randn(N, generator=g).to(cuda)
     ref = x.double() @ w.double().T
     L.set_gemm_tile256(1)
+    L.set_tuning("GEMM_GLDS_FORCE", 1)          # the 256 x 256 kernel is only reached where the LDS-DMA kernels apply
     try:
-        with L.gemm_precision("bf16"):
+        with L.gemm_precision("bf16"), L.kernel_accounting() as acc:
             outs = []
             for _ in range(3):
                 if epi == "bias":          # (a product without any epilogue may be cut along K by the dispatcher: float atomics)
@@ -391,7 +401,10 @@ def test_tile256_two_group_gemm_matches_float64(cuda, M, N, K, epi):
         assert ((outs[0].double() - want).abs().max() / want.abs().max()).item() <= tol
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[1], outs[2])
     finally:
+        L.set_tuning("GEMM_GLDS_FORCE", None)
         L.set_gemm_tile256(0)
+    rows = [r for r in acc.rows if r["name"].startswith("gemm")]
+    assert len(rows) == 1 and rows[0]["name"].startswith("gemm_p8_kernel<") and rows[0]["calls"] == 3, rows
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 2048), (768, 512, 4100), (3072, 768, 16200), (520, 264, 3000)])
@@ -438,9 +451,10 @@ def test_tile256_input_gradient_form(cuda, T, Nout, Kin):
     (gd,) = torch.autograd.grad(torch.nn.functional.gelu(zd).sum(), zd)
     want = (g.double() @ w.double()) * gd
     L.set_gemm_tile256(1)
+    L.set_tuning("GEMM_GLDS_FORCE", 1)          # the 256 x 256 kernel is only reached where the LDS-DMA kernels apply
     try:
         outs = []
-        with L.gemm_precision("bf16"):
+        with L.gemm_precision("bf16"), L.kernel_accounting() as acc:
             for _ in range(3):
                 gx = torch.empty(T, Kin, device=cuda, dtype=torch.bfloat16)
                 _gemm_batched(g, w, gx, T, Kin, Nout, Nout, Kin, Kin, 0, 0, act=4, residual=z)
@@ -449,7 +463,10 @@ def test_tile256_input_gradient_form(cuda, T, Nout, Kin):
         assert ((gx.double() - want).abs().max() / want.abs().max()).item() <= 1e-2
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[1], outs[2])
     finally:
+        L.set_tuning("GEMM_GLDS_FORCE", None)
         L.set_gemm_tile256(0)
+    rows = [r for r in acc.rows if r["name"].startswith("gemm")]
+    assert [r["name"] for r in rows] == ["gemm_p8_kernel<true, false, true>"] and rows[0]["calls"] == 3, rows
 
 
 def test_weight_gradient_slab_survives_growth_behind_a_captured_graph(cuda):
@@ -567,24 +584,30 @@ def test_tile256_wide_row_epilogue_is_the_narrow_one_bit_for_bit(cuda, M, N, K, 
     res = torch.randn(M, N, generator=g).to(cuda)
     outs = {}
     L.set_gemm_tile256(1)
+    L.set_tuning("GEMM_GLDS_FORCE", 1)          # the 256 x 256 kernel is only reached where the LDS-DMA kernels apply
     try:
         with L.gemm_precision("bf16"):
             for wide in (1, 0):
                 L.set_tuning("GEMM_P8_WIDE", wide)
-                y = torch.full((M, N), 3.0, device=cuda, dtype=torch.float32 if form == "fc2_bias_residual_fp32" else torch.bfloat16)
-                z = torch.full((M, N), 5.0, device=cuda, dtype=torch.bfloat16)
-                if form == "fc1_gelu_stored_derivative":
-                    _gemm(x, w, y, M, N, K, K, K, N, 0, 1, bias, 7, z, None)
-                elif form == "gh_times_stored_derivative":
-                    _gemm_batched(x, wt, y, M, N, K, K, N, N, 0, 0, act=8, residual=zd)
-                elif form == "fc2_bias_residual_fp32":
-                    _gemm(x, w, y, M, N, K, K, K, N, 0, 1, bias, 0, None, res)
-                else:
-                    _gemm(x, w, y, M, N, K, K, K, N, 0, 1)
-                torch.cuda.synchronize()
+                with L.kernel_accounting() as acc:
+                    y = torch.full((M, N), 3.0, device=cuda, dtype=torch.float32 if form == "fc2_bias_residual_fp32" else torch.bfloat16)
+                    z = torch.full((M, N), 5.0, device=cuda, dtype=torch.bfloat16)
+                    if form == "fc1_gelu_stored_derivative":
+                        _gemm(x, w, y, M, N, K, K, K, N, 0, 1, bias, 7, z, None)
+                    elif form == "gh_times_stored_derivative":
+                        _gemm_batched(x, wt, y, M, N, K, K, N, N, 0, 0, act=8, residual=zd)
+                    elif form == "fc2_bias_residual_fp32":
+                        _gemm(x, w, y, M, N, K, K, K, N, 0, 1, bias, 0, None, res)
+                    else:
+                        _gemm(x, w, y, M, N, K, K, K, N, 0, 1)
+                    torch.cuda.synchronize()
+                names = [r["name"] for r in acc.rows if r["name"].startswith("gemm")]
+                bkc = "false" if form.startswith("gh_") else "true"          # gh = g W2: B is [k][n]
+                assert names == [f"gemm_p8_kernel<true, {bkc}, {'true' if wide else 'false'}>"], names
                 outs[wide] = (y.clone(), z.clone())
     finally:
         L.set_tuning("GEMM_P8_WIDE", None)
+        L.set_tuning("GEMM_GLDS_FORCE", None)
         L.set_gemm_tile256(0)
     assert torch.equal(outs[1][0], outs[0][0]) and torch.equal(outs[1][1], outs[0][1])
     ref = x.double() @ w.double().T

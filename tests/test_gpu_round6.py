@@ -52,6 +52,51 @@ def test_kernel_accounting_records_launches_with_their_algorithmic_work(cuda):
     assert torch.allclose(Cm, A @ B.T, rtol=1e-4, atol=1e-3)
 
 
+def test_kernel_accounting_names_the_sliced_and_queued_gemm_launches(cuda):
+    """The GEMM launches outside a product's main kernel have rows of their own: the 256 x 256 weight-gradient kernel, the ordered
+    reduction of the K slices after it and after the LDS-DMA weight-gradient kernel, and the one launch of a queue of small products
+    (lib.gemm_group) -- each with the algorithmic work of what it launched."""
+    from dlwp_benchmark_amd import lib as L
+    from dlwp_benchmark_amd.token_ops import _gemm
+    BF = torch.bfloat16
+    M, N, K = 768, 512, 4096          # 6 x 4 = 24 tiles of 128: the LDS-DMA weight-gradient kernel takes the slab
+    g = torch.Generator().manual_seed(3)
+    gm, x = torch.randn(K, M, generator=g).to(cuda).to(BF), torch.randn(K, N, generator=g).to(cuda).to(BF)
+    gw = torch.zeros(M, N, device=cuda)
+    a, b = torch.randn(100, 64, generator=g).to(cuda), torch.randn(72, 64, generator=g).to(cuda)
+    c1, c2 = torch.empty(100, 72, device=cuda), torch.empty(72, 100, device=cuda)
+    with L.gemm_precision("bf16"):
+        L.set_gemm_tile256(1)
+        try:
+            with L.kernel_accounting() as acc_p8:
+                _gemm(gm, x, gw, M, N, K, M, N, N, 1, 0, accumulate=1)
+        finally:
+            L.set_gemm_tile256(0)
+        with L.kernel_accounting() as acc_tn:
+            _gemm(gm, x, gw, M, N, K, M, N, N, 1, 0, accumulate=1)
+        with L.kernel_accounting() as acc_q:
+            with L.gemm_group():
+                _gemm(a, b, c1, 100, 72, 64, 64, 64, 72, 0, 1)
+                _gemm(b, a, c2, 72, 100, 64, 64, 64, 100, 0, 1)
+        torch.cuda.synchronize()
+    for acc, main in ((acc_p8, "gemm_p8_tn_kernel"), (acc_tn, "gemm_glds_tn_kernel<64>")):
+        rows = {r["name"]: r for r in acc.rows if r["name"].startswith("gemm")}
+        assert sorted(rows) == [main, "gemm_slab_reduce_kernel"], sorted(rows)
+        assert rows[main]["calls"] == 1 and rows[main]["flops"] == pytest.approx(2.0 * M * N * K)
+        red = rows["gemm_slab_reduce_kernel"]
+        slices = red["flops"] / (M * N)           # one add per slice and element; every slice plane read, C read and written
+        assert red["calls"] == 1 and slices >= 2 and slices == int(slices)
+        assert red["bytes"] == pytest.approx(4.0 * M * N * (slices + 2))
+        assert 0 < red["ms"] < 50
+    rows = [r for r in acc_q.rows if r["name"].startswith("gemm")]
+    assert [r["name"] for r in rows] == ["gemm_group_any_kernel<true>"] and rows[0]["calls"] == 1, rows
+    assert rows[0]["flops"] == pytest.approx(2 * 2.0 * 100 * 72 * 64)
+    want = 2 * (gm.double().T @ x.double())
+    assert ((gw.double() - want).abs().max() / want.abs().max()).item() <= 2e-5
+    ab = a.bfloat16().double() @ b.bfloat16().double().T
+    assert rel(c1, ab) <= 2e-5 and rel(c2, ab.T) <= 2e-5
+
+
 @pytest.mark.parametrize("T,N", [(32, 4096), (48, 1000)])
 def test_tall_column_sum_overwrite_is_correct_under_graph_replay(cuda, T, N):
     """dlwp_colsum_ex(overwrite = 1) with more than 16 rows zero-fills its output before the atomic slab kernel: with a kernel, not
