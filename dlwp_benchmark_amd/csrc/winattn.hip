@@ -596,6 +596,8 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const float* __restrict
 extern "C" int dlwp_window_attn_pack_table(const float* bias_table, float* packed, int TB, int ntypes, int heads, void* stream) {
     DLWP_REQUIRE(bias_table && packed && TB > 0 && ntypes > 0 && heads > 0, DLWP_E_INVALID, "window_attn_pack_table: bad argument");
     const int TH = ntypes * heads;
+    // live accounting: a transposed copy, no arithmetic; the table is read once and its copy written once
+    dlwp_prof_scope prof((hipStream_t)stream, 0.0, 8.0 * TB * TH, "pack_table_kernel");
     hipLaunchKernelGGL(pack_table_kernel, dim3((TB + 31) / 32, (TH + 31) / 32), dim3(256), 0, (hipStream_t)stream, bias_table,
                        packed, TB, TH);
     DLWP_LAUNCH_CHECK();
@@ -759,7 +761,10 @@ extern "C" int dlwp_window_attn_bwd_qrange(const float* qkv, const float* bias_t
 #undef WA_BWD_B
 #undef WA_BWD
     if (slab) {
-        const int nqt = (N + QT - 1) / QT, n_items = (B_ / ntypes) * nqt;
+        const int nqt = (N + QT - 1) / QT, n_items = (B_ / ntypes) * nqt, chunks = (n_items + FOLD_CH - 1) / FOLD_CH;
+        // live accounting: one add per slab partial; the slab is read once, every chunk adds its sums into the table
+        dlwp_prof_scope prof((hipStream_t)stream, (double)n_items * heads * ntypes * TB,
+                             4.0 * n_items * heads * ntypes * TB + 8.0 * chunks * TB * ntypes * heads, "winattn_fold_kernel");
         hipLaunchKernelGGL(winattn_fold_kernel, dim3((TB + 255) / 256, heads * ntypes, (n_items + FOLD_CH - 1) / FOLD_CH),
                            dim3(256), 0, (hipStream_t)stream, slab, gbias_table, TB, ntypes, heads, nqt, n_items);
     }
@@ -868,6 +873,8 @@ extern "C" int dlwp_window_softmax_fwd(float* s, const float* bias_table, const 
     DLWP_REQUIRE(N <= 1024, DLWP_E_UNSUPPORTED, "window_softmax_fwd: at most 1024 tokens per window (got %d)", N);
     RowSmDev a{s, nullptr, bias_table, nullptr, ia, ib, labels, B_, nW, N, ntypes, heads, scale};
     const long long rows = (long long)B_ * heads * N;
+    // live accounting: per score scale + bias + exp + sum + normalise; the scores are read and written in place once
+    dlwp_prof_scope prof((hipStream_t)stream, 5.0 * rows * N, 8.0 * rows * N, "winattn_rows_kernel<false>");
     hipLaunchKernelGGL(winattn_rows_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
@@ -880,6 +887,8 @@ extern "C" int dlwp_window_softmax_bwd(const float* p, float* dp, float* gbias_t
     DLWP_REQUIRE(N <= 1024, DLWP_E_UNSUPPORTED, "window_softmax_bwd: at most 1024 tokens per window (got %d)", N);
     RowSmDev a{dp, p, nullptr, gbias_table, ia, ib, nullptr, B_, nW, N, ntypes, heads, scale};
     const long long rows = (long long)B_ * heads * N;
+    // live accounting: per score the dot term, dS = p (dp - dot) and its scaled copy; p read, dp read and written in place
+    dlwp_prof_scope prof((hipStream_t)stream, 5.0 * rows * N, 12.0 * rows * N, "winattn_rows_kernel<true>");
     hipLaunchKernelGGL(winattn_rows_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;

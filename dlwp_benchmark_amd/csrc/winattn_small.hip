@@ -1570,31 +1570,33 @@ bool dlwp_winattn_small_applies(int N, int d, long long pairs) {
         const int nc = (N + 15) / 16, ndb = (d + 15) / 16;                                                                \
         const bool vec = d % 4 == 0;                                                                                      \
         const dim3 grid((unsigned)(heads * ntypes * a.groups)), block(256);                                               \
-        auto go = [&](auto knl) -> int {                                                                                  \
+        /* the accounting name carries the whole template argument list (the defaulted TOK = IOBF = false included) */     \
+        auto go = [&](auto knl, int NCv, int NDBv, bool V, bool B) -> int {                                               \
             int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, #KERNEL);                                  \
             if (rc2) return rc2;                                                                                          \
-            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), #KERNEL "<%d, %d>", nc <= 4 ? 4 : 8, ndb); \
+            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), #KERNEL "<%d, %d, %s, %s, false, false>", \
+                                 NCv, NDBv, V ? "true" : "false", B ? "true" : "false");                                  \
             hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);                                            \
             return DLWP_OK;                                                                                               \
         };                                                                                                                \
         int rc3 = DLWP_OK;                                                                                                \
         const bool bf = dlwp_get_gemm_precision() == 1;      /* bf16 matrix arithmetic asked for: bf16 MFMA operands */   \
         if (bf && ndb == 3) {                       /* head dims 33 .. 48, windows of at most 64 tokens (small_applies) */  \
-            rc3 = go(KERNEL<4, 3, true, true>);                                                                           \
+            rc3 = go(KERNEL<4, 3, true, true>, 4, 3, true, true);                                                         \
         } else if (bf) {                                                                                                  \
             if (ndb == 1) {                                                                                               \
-                if (nc <= 4) rc3 = vec ? go(KERNEL<4, 1, true, true>) : go(KERNEL<4, 1, false, true>);                    \
-                else rc3 = vec ? go(KERNEL<8, 1, true, true>) : go(KERNEL<8, 1, false, true>);                            \
+                if (nc <= 4) rc3 = vec ? go(KERNEL<4, 1, true, true>, 4, 1, true, true) : go(KERNEL<4, 1, false, true>, 4, 1, false, true); \
+                else rc3 = vec ? go(KERNEL<8, 1, true, true>, 8, 1, true, true) : go(KERNEL<8, 1, false, true>, 8, 1, false, true); \
             } else {                                                                                                      \
-                if (nc <= 4) rc3 = vec ? go(KERNEL<4, 2, true, true>) : go(KERNEL<4, 2, false, true>);                    \
-                else rc3 = vec ? go(KERNEL<8, 2, true, true>) : go(KERNEL<8, 2, false, true>);                            \
+                if (nc <= 4) rc3 = vec ? go(KERNEL<4, 2, true, true>, 4, 2, true, true) : go(KERNEL<4, 2, false, true>, 4, 2, false, true); \
+                else rc3 = vec ? go(KERNEL<8, 2, true, true>, 8, 2, true, true) : go(KERNEL<8, 2, false, true>, 8, 2, false, true); \
             }                                                                                                             \
         } else if (ndb == 1) {                                                                                            \
-            if (nc <= 4) rc3 = vec ? go(KERNEL<4, 1, true, false>) : go(KERNEL<4, 1, false, false>);                      \
-            else rc3 = vec ? go(KERNEL<8, 1, true, false>) : go(KERNEL<8, 1, false, false>);                              \
+            if (nc <= 4) rc3 = vec ? go(KERNEL<4, 1, true, false>, 4, 1, true, false) : go(KERNEL<4, 1, false, false>, 4, 1, false, false); \
+            else rc3 = vec ? go(KERNEL<8, 1, true, false>, 8, 1, true, false) : go(KERNEL<8, 1, false, false>, 8, 1, false, false); \
         } else {                                                                                                          \
-            if (nc <= 4) rc3 = vec ? go(KERNEL<4, 2, true, false>) : go(KERNEL<4, 2, false, false>);                      \
-            else rc3 = vec ? go(KERNEL<8, 2, true, false>) : go(KERNEL<8, 2, false, false>);                              \
+            if (nc <= 4) rc3 = vec ? go(KERNEL<4, 2, true, false>, 4, 2, true, false) : go(KERNEL<4, 2, false, false>, 4, 2, false, false); \
+            else rc3 = vec ? go(KERNEL<8, 2, true, false>, 8, 2, true, false) : go(KERNEL<8, 2, false, false>, 8, 2, false, false); \
         }                                                                                                                 \
         if (rc3) return rc3;                                                                                              \
     } while (0)
@@ -1613,7 +1615,7 @@ int dlwp_winattn_small_fwd(const float* qkv, const float* table, const float* pa
         auto go = [&](auto knl) -> int {
             int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, "winattn_small_fwd_kernel");
             if (rc2) return rc2;
-            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_small_fwd_kernel<4, %d> (bf16)", ndb);
+            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_small_fwd_kernel<4, %d, true, true, false, true>", ndb);
             hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);
             return DLWP_OK;
         };
@@ -1719,7 +1721,8 @@ int dlwp_winattn_small_bwd(const float* qkv, const float* table, const float* pa
     auto go = [&](auto knl) -> int {
         int rc = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, "winattn_small_bwd");
         if (rc) return rc;
-        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 5), ws_prof_bytes(a, true), "winattn_small_bwd_kernel<%d>", d <= 16 ? 1 : 2);
+        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 5), ws_prof_bytes(a, true), "winattn_small_bwd_kernel<%d, %s, %s>", d <= 16 ? 1 : 2,
+                             vec ? "true" : "false", dlwp_get_gemm_precision() == 1 ? "true" : "false");
         hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);
         return DLWP_OK;
     };
@@ -1807,8 +1810,8 @@ extern "C" int dlwp_window_attn_fwd_tokens(const float* qkv_tokens, const float*
     auto go = [&](auto knl) -> int {
         int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, "winattn_small_fwd_tokens");
         if (rc2) return rc2;
-        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_small_fwd_kernel<%d, %d> (tokens)",
-                             nc <= 4 ? 4 : 8, d <= 16 ? 1 : 2);
+        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_small_fwd_kernel<%d, %d, true, true, true, %s>",
+                             nc <= 4 ? 4 : 8, d <= 16 ? 1 : 2, io_bf16 ? "true" : "false");
         hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);
         return DLWP_OK;
     };
