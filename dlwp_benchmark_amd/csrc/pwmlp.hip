@@ -17,6 +17,18 @@
 // form re-read each fragment four times through L1: 14.9 / 12.4 us against 11.4 / 10.1).  The forward kernel can append the W-axis DFT of its output
 // rows (lifting -> first spectral block), the backward kernel the adjoint DFT of its input
 // gradient rows (projection backward -> last spectral block's backward).
+//
+// The exact-f32 MFMA issues at the fp32 vector rate (32 cycles per 16x16x4 per SIMD) and does not overlap VALU work of the same
+// SIMD, so the backward kernel's main loop costs its MFMA count; two products that multiply zeros or an identity are kept off
+// the matrix pipe, both exactly (every output is bit for bit what the all-MFMA form gave):
+//  - Cout == 1 (the projection of every scalar-field FNO, pwmlp_bwd_kernel<NIB, 0, 8>): g_a = W2^T gy has one real row of 16,
+//    so g_a[p][h] = gy[p] * w2[h] is one VALU multiply, bit-identical to the zero-padded MFMA (one rounded product + zeros).
+//  - every backward: gz^T -> gz goes through a wave-private 16 x 16 LDS tile (one 16-byte write, four 4-byte reads, row stride
+//    20 floats: conflict-free both ways, no workgroup barrier) instead of a 4-MFMA product with the identity.
+// 36 -> 28 MFMAs per 16 x 16 tile in the projection backward, 32 -> 28 in the lifting backward.  The other one-row products
+// (dW2 in the backward, the second GEMM of the forward) stay on the MFMA: as VALU sums they were 0.8 - 1 us faster per launch
+// but reorder fp32 additions, which moved the training step's parameters (profiles/r07_experiments.md).
+// Step table of the headline (64 x 64, B 4): projection backward 22.4 -> 20.5 us, lifting backward 20.4 -> 19.3 us.
 #include "common.hip.h"
 #include "dlwpmi_internal.h"
 #include "fno_rows.hip.h"
@@ -358,8 +370,23 @@ __device__ __forceinline__ void grad_flush(float* slab_ptr, float* grad_ptr, boo
     else atomic_add_f32(grad_ptr, v);
 }
 
+constexpr int TPS = 20;       // row stride of a wave's 16 x 16 transpose tile: 16-byte row writes and 4-byte column reads both conflict-free
+
+// orders a wave's own LDS writes against its own later reads of other lanes' words (the LDS executes one wave's instructions in
+// order; this only keeps the compiler from moving them): no workgroup barrier, no instruction
+__device__ __forceinline__ void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// NOB == 0 is the scalar-output form (Cout == 1): g_a^T[p][h] = gy[p] * w2[h] is one VALU multiply (bit-identical to the
+// zero-padded MFMA: one rounded product plus exact zeros); everything else, dW2 included, is as for NOB == 1.  (It is an
+// instantiation of this template and not a second kernel around a shared body: a body that takes the arguments by reference
+// loads the whole argument block up front and spills scalar registers, +1.1 us on every instantiation.)
 template <int NIB, int NOB, int NW>
 __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
+    constexpr bool SC = NOB == 0;
+    constexpr int NB = SC ? 1 : NOB;         // 16-row output blocks of the slab layout and the operand arrays
     constexpr int NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* xs = smem;                        // [Cin_pad][LDP]
@@ -377,19 +404,25 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
     // weight fragments of one hidden block, straight from L2: W1 rows (B operand of z^T), b1, W2 columns of the block (B operand
     // of g_a^T), W1 columns (A operand of dX).  A wave owns its hidden blocks alone, so every fragment is read once per workgroup.
     struct HbW {
-        f32x4 w1b[NIB], w2c[NOB], w1c[NIB];
-        float b1v;
+        f32x4 w1b[NIB], w2c[NB], w1c[NIB];
+        float b1v, w2v;               // w2v (SC): W2[0][hb*16 + r]
     };
     auto load_hb = [&](int hb, HbW& h) {
 #pragma unroll
         for (int kc = 0; kc < NIB; ++kc) h.w1b[kc] = frag_row(a.w1, a.Ch, a.Cin, hb * 16 + r, kc * 16 + 4 * g, vec1);
+        if constexpr (!SC) {
 #pragma unroll
-        for (int oc = 0; oc < NOB; ++oc) h.w2c[oc] = frag_col(a.w2, a.Cout, a.Ch, oc * 16 + 4 * g, hb * 16 + r);
+            for (int oc = 0; oc < NB; ++oc) h.w2c[oc] = frag_col(a.w2, a.Cout, a.Ch, oc * 16 + 4 * g, hb * 16 + r);
+        }
 #pragma unroll
         for (int ib = 0; ib < NIB; ++ib) h.w1c[ib] = frag_col(a.w1, a.Ch, a.Cin, hb * 16 + 4 * g, ib * 16 + r);
         const bool okh = hb * 16 + r < a.Ch;
         const float bv = a.b1[okh ? hb * 16 + r : 0];
         h.b1v = okh ? bv : 0.f;
+        if constexpr (SC) {
+            const float wv = a.w2[okh ? hb * 16 + r : 0];
+            h.w2v = okh ? wv : 0.f;
+        }
     };
     HbW wcur;
     load_hb(w < nhb ? w : 0, wcur);                        // in flight while the pixel tiles are staged
@@ -429,31 +462,30 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
 
     DLWP_STAMP(10);
 
+    // wave-private 16 x 16 transpose tile (gz^T -> gz) inside the gx partial-tile region, which is idle until the main loop ends
+    static_assert(16 * TPS <= 16 * LDP, "a wave's transpose tile fits into its own partial-tile rows");
+    float* tp = red + w * 16 * TPS;
+
     f32x4 gxacc[4][NIB];
 #pragma unroll
     for (int pb = 0; pb < 4; ++pb)
 #pragma unroll
         for (int ib = 0; ib < NIB; ++ib) gxacc[pb][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // identity as a permuted-k B operand: I[k = 4g+s][n = r]
-    f32x4 ident;
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2) ident[s2] = (4 * g + s2 == r) ? 1.f : 0.f;
-
     float* sl = a.slab ? a.slab + (long long)blockIdx.x * a.slab_stride : nullptr;
-    // slab layout per workgroup: [nhb][NOB][64][4] dW2 tiles | [nhb][NIB][64][4] dW1 tiles | db1[Ch_pad] | db2[Cout_pad]
-    const long long o_t1 = (long long)(a.Ch_pad / 16) * NOB * 256, o_gb1 = o_t1 + (long long)(a.Ch_pad / 16) * NIB * 256;
+    // slab layout per workgroup: [nhb][NB][64][4] dW2 tiles | [nhb][NIB][64][4] dW1 tiles | db1[Ch_pad] | db2[Cout_pad]
+    const long long o_t1 = (long long)(a.Ch_pad / 16) * NB * 256, o_gb1 = o_t1 + (long long)(a.Ch_pad / 16) * NIB * 256;
     const long long o_gb2 = o_gb1 + a.Ch_pad;
     const bool accum = sl && a.slab_accumulate != 0;
     DLWP_STAMP(11);
     // Everything below works in the TRANSPOSED orientation (rows = pixels 4g+j, column = hidden channel r):
     // the accumulator of z^T / gz^T is then directly the B operand of the pixel contractions (dW2) and, read as an
     // A operand, the hidden-major matrix for dW1; the one product that contracts over the hidden index (dX) gets
-    // its operand through a 4-MFMA multiplication with the identity instead of an LDS round trip.
+    // its operand through a wave-private LDS transpose (no workgroup barrier).
     // One hidden block's state while its four pixel blocks are processed.
     struct HbState {
-        f32x4 pgw2[NOB], pgw1[NIB];   // running slab partials (read-modify-write accumulation across net calls)
+        f32x4 pgw2[NB], pgw1[NIB];   // running slab partials (read-modify-write accumulation across net calls)
         float pgb1;
-        f32x4 gw2acc[NOB], gw1acc[NIB];
+        f32x4 gw2acc[NB], gw1acc[NIB];
         float gb1acc;
         float *t2, *t1;
         int hb;
@@ -464,10 +496,10 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
         // registers of every lane contiguously -> one 16-byte access per lane, 1 KiB per wave-instruction
         // (narrow 64-byte-segment stores were issue-bound: ~350 cycles each).  The old values are fetched here.
         st.pgb1 = 0.f;
-        st.t2 = sl ? sl + ((long long)hb * NOB * 64 + lane) * 4 : nullptr;
+        st.t2 = sl ? sl + ((long long)hb * NB * 64 + lane) * 4 : nullptr;
         st.t1 = sl ? sl + o_t1 + ((long long)hb * NIB * 64 + lane) * 4 : nullptr;
 #pragma unroll
-        for (int ob = 0; ob < NOB; ++ob)
+        for (int ob = 0; ob < NB; ++ob)
             st.pgw2[ob] = accum ? *reinterpret_cast<const f32x4*>(st.t2 + ob * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ib = 0; ib < NIB; ++ib)
@@ -475,7 +507,7 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
         if (accum && g == 0) st.pgb1 = sl[o_gb1 + hb * 16 + r];
         st.gb1acc = 0.f;
 #pragma unroll
-        for (int ob = 0; ob < NOB; ++ob) st.gw2acc[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int ob = 0; ob < NB; ++ob) st.gw2acc[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ib = 0; ib < NIB; ++ib) st.gw1acc[ib] = f32x4{0.f, 0.f, 0.f, 0.f};
     };
@@ -487,25 +519,35 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
     // apart, 433 k together), so the main loop costs MFMA cycles PLUS GELU cycles however they are ordered.
     auto hb_stage_a = [&](const HbW& hw, int pb, f32x4& zt, f32x4& gat) {
         // z^T[p][h] = sum_i x[i][p] W1[h][i];  g_a^T[p][h] = sum_o gy[o][p] W2[o][h]
-        f32x4 az[NIB], ag[NOB];
+        f32x4 az[NIB];
 #pragma unroll
         for (int kc = 0; kc < NIB; ++kc)
 #pragma unroll
             for (int s2 = 0; s2 < 4; ++s2) az[kc][s2] = xs[(kc * 16 + 4 * g + s2) * LDP + pb * 16 + r];
-#pragma unroll
-        for (int oc = 0; oc < NOB; ++oc)
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) ag[oc][s2] = gys[(oc * 16 + 4 * g + s2) * LDP + pb * 16 + r];
         zt = f32x4{0.f, 0.f, 0.f, 0.f};
-        gat = f32x4{0.f, 0.f, 0.f, 0.f};
-        constexpr int NMAX = NIB > NOB ? NIB : NOB;
+        if constexpr (SC) {
 #pragma unroll
-        for (int c = 0; c < NMAX; ++c)
+            for (int c = 0; c < NIB; ++c)
 #pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                if (c < NIB) zt = mfma16(az[c][s2], hw.w1b[c][s2], zt);
-                if (c < NOB) gat = mfma16(ag[c][s2], hw.w2c[c][s2], gat);
-            }
+                for (int s2 = 0; s2 < 4; ++s2) zt = mfma16(az[c][s2], hw.w1b[c][s2], zt);
+            // one 16-byte read of the gy row: pixels pb*16 + 4g .. + 3
+            gat = *reinterpret_cast<const f32x4*>(&gys[pb * 16 + 4 * g]) * f32x4{hw.w2v, hw.w2v, hw.w2v, hw.w2v};
+        } else {
+            f32x4 ag[NB];
+#pragma unroll
+            for (int oc = 0; oc < NB; ++oc)
+#pragma unroll
+                for (int s2 = 0; s2 < 4; ++s2) ag[oc][s2] = gys[(oc * 16 + 4 * g + s2) * LDP + pb * 16 + r];
+            gat = f32x4{0.f, 0.f, 0.f, 0.f};
+            constexpr int NMAX = NIB > NB ? NIB : NB;
+#pragma unroll
+            for (int c = 0; c < NMAX; ++c)
+#pragma unroll
+                for (int s2 = 0; s2 < 4; ++s2) {
+                    if (c < NIB) zt = mfma16(az[c][s2], hw.w1b[c][s2], zt);
+                    if (c < NB) gat = mfma16(ag[c][s2], hw.w2c[c][s2], gat);
+                }
+        }
     };
     auto hb_stage_b = [&](HbState& st, const HbW& hw, int pb, const f32x4 zt, const f32x4 gat) {
         f32x4 actt, gzt, dvt;
@@ -513,18 +555,25 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
         gzt = gat * dvt;
         st.gb1acc += (gzt[0] + gzt[1]) + (gzt[2] + gzt[3]);
         // dW2[o][h] += sum_p gy[o][p] act^T[p][h];  dW1[h][i] += sum_p gz[h][p] x[i][p]  (gz^T registers read as an A operand
-        // are gz);  gz[h][p] in accumulator layout = gz^T (as A operand) x identity
-        f32x4 a2[NOB], b1f[NIB];
+        // are gz)
+        // gz[h][p] in accumulator layout is the 16 x 16 transpose of gz^T: through the wave's own LDS tile (row h = r gets this
+        // lane's four pixels, then column reads), not through the matrix pipe -- a product with the identity was 4 of the
+        // block's MFMAs, 128 issue cycles against ~30 here; the dW2 / dW1 products below do not need gz and cover the round trip
+        f32x4 gz;
+        wave_lds_order();
+        *reinterpret_cast<f32x4*>(&tp[r * TPS + 4 * g]) = gzt;
+        wave_lds_order();
 #pragma unroll
-        for (int ob = 0; ob < NOB; ++ob) a2[ob] = *reinterpret_cast<const f32x4*>(&gys[(ob * 16 + r) * LDP + pb * 16 + 4 * g]);
+        for (int j = 0; j < 4; ++j) gz[j] = tp[(4 * g + j) * TPS + r];
+        f32x4 a2[NB], b1f[NIB];
+#pragma unroll
+        for (int ob = 0; ob < NB; ++ob) a2[ob] = *reinterpret_cast<const f32x4*>(&gys[(ob * 16 + r) * LDP + pb * 16 + 4 * g]);
 #pragma unroll
         for (int ib = 0; ib < NIB; ++ib) b1f[ib] = *reinterpret_cast<const f32x4*>(&xs[(ib * 16 + r) * LDP + pb * 16 + 4 * g]);
-        f32x4 gz = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s2 = 0; s2 < 4; ++s2) {
-            gz = mfma16(gzt[s2], ident[s2], gz);
 #pragma unroll
-            for (int ob = 0; ob < NOB; ++ob) st.gw2acc[ob] = mfma16(a2[ob][s2], actt[s2], st.gw2acc[ob]);
+            for (int ob = 0; ob < NB; ++ob) st.gw2acc[ob] = mfma16(a2[ob][s2], actt[s2], st.gw2acc[ob]);
 #pragma unroll
             for (int ib = 0; ib < NIB; ++ib) st.gw1acc[ib] = mfma16(gzt[s2], b1f[ib][s2], st.gw1acc[ib]);
         }
@@ -538,7 +587,7 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
         const int hb = st.hb;
         if (sl) {
 #pragma unroll
-            for (int ob = 0; ob < NOB; ++ob) {
+            for (int ob = 0; ob < NB; ++ob) {
                 f32x4 v = st.gw2acc[ob];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] += st.pgw2[ob][j];
@@ -554,7 +603,7 @@ __global__ __launch_bounds__(NW * 64) void pwmlp_bwd_kernel(BwdArgs a) {
         } else {
             const int hcol = hb * 16 + r;
 #pragma unroll
-            for (int ob = 0; ob < NOB; ++ob)
+            for (int ob = 0; ob < NB; ++ob)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int o = ob * 16 + 4 * g + j;
@@ -817,6 +866,9 @@ int dlwp_pwmlp_fwd_rows_ex(const dlwp_chan_src* x, const float* w1, const float*
     const size_t lds = sizeof(float) * (fwd_lds_floats(a.Cin_pad, a.Ch_pad, a.Cout_pad) + (size_t)(FWD_WAVES / 4) * a.Cout_pad * LDP);
     constexpr int NW = FWD_WAVES;
     const dim3 grid(B * a.tiles_per_sample), block(NW * 64);
+    const double pix = (double)B * P;
+    dlwp_prof_scope prof(stream, 2.0 * pix * Ch * (Cin + Cout), 4.0 * pix * (Cin + Cout), "pwmlp_fwd_kernel<%d, %d>",
+                         nob, NW);                        // the instantiation this call launches, as the live accounting reports it
 #define LAUNCH(N)                                                             \
     if ((rc = set_lds(pwmlp_fwd_kernel<N, NW>, lds)) != DLWP_OK) return rc;   \
     hipLaunchKernelGGL((pwmlp_fwd_kernel<N, NW>), grid, block, lds, stream, a);
@@ -861,6 +913,9 @@ int dlwp_pwmlp_fwd_chain_ex(const dlwp_chan_src* x1v, const float* w11, const fl
         }
     }
     const dim3 grid(B * c.p.tiles_per_sample), block(NW * 64);
+    const double pix = (double)B * P;
+    dlwp_prof_scope prof(stream, 2.0 * pix * (Ch1 * (Cin1 + Cout1) + Ch2 * (Cin2 + Cout2)), 4.0 * pix * (Cin1 + Cout1 + Cin2 + Cout2),
+                         "pwmlp_fwd_chain_kernel<1, %d, %d>", nob2, NW);
     if (nob2 == 1) {
         if ((rc = set_lds(pwmlp_fwd_chain_kernel<1, 1, NW>, lds)) != DLWP_OK) return rc;
         hipLaunchKernelGGL((pwmlp_fwd_chain_kernel<1, 1, NW>), grid, block, lds, stream, c);
@@ -923,6 +978,10 @@ int dlwp_pwmlp_bwd_rows_ex(const dlwp_chan_src* x, const float* w1, const float*
     constexpr int NW = BWD_WAVES;
     const dim3 grid(B * a.tiles_per_sample), block(NW * 64);
     int rc;
+    const bool scalar = Cout == 1;
+    const double pix = (double)B * P;
+    dlwp_prof_scope prof(stream, 2.0 * pix * Ch * (3 * Cin + 2 * Cout), 4.0 * pix * (2 * Cin + Cout), "pwmlp_bwd_kernel<%d, %d, %d>",
+                         nib, scalar ? 0 : nob, NW);      // the instantiation this call launches, as the live accounting reports it
 #define LAUNCH(I, O)                                                           \
     if ((rc = set_lds(pwmlp_bwd_kernel<I, O, NW>, lds)) != DLWP_OK) return rc; \
     hipLaunchKernelGGL((pwmlp_bwd_kernel<I, O, NW>), grid, block, lds, stream, a);
@@ -933,7 +992,14 @@ int dlwp_pwmlp_bwd_rows_ex(const dlwp_chan_src* x, const float* w1, const float*
         case 3: LAUNCH(I, 3) break;  \
         default: LAUNCH(I, 4) break; \
     }
-    switch (nib) {
+    if (scalar) {            // Cout == 1: the scalar-output instantiations (NOB = 0)
+        switch (nib) {
+            case 1: LAUNCH(1, 0) break;
+            case 2: LAUNCH(2, 0) break;
+            case 3: LAUNCH(3, 0) break;
+            default: LAUNCH(4, 0) break;
+        }
+    } else switch (nib) {
         case 1: ROW(1) break;
         case 2: ROW(2) break;
         case 3: ROW(3) break;
