@@ -343,6 +343,386 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
     DLWP_SPAN_END();
 }
 
+// The staging helpers of common.hip.h and store_x1 stride by blockDim.x.  Role A of the two-role kernel below is the first NT
+// threads of a larger workgroup: the same loops with the stride spelled out (same elements per thread, same order of additions).
+template <int NT, bool TR>
+__device__ __forceinline__ void stage_matrix_tail_nt(float* dst, int ld, const float* __restrict__ src, int rows, int cols,
+                                                     FastDiv dcols, int done4) {
+    const int n = rows * cols;
+#pragma unroll 4
+    for (int e = 4 * done4 + threadIdx.x; e < n; e += NT) {
+        const int rr = fastdiv(e, dcols);
+        const int cc = e - rr * cols;
+        dst[TR ? cc * ld + rr : rr * ld + cc] = src[e];
+    }
+}
+template <int NT>
+__device__ __forceinline__ void zero_padding_nt(float* dst, int ld, int rows, int cols, int rows_pad, int cols_pad) {
+    if (cols_pad > cols)
+        for (int rr = threadIdx.x; rr < rows; rr += NT)
+            for (int cc = cols; cc < cols_pad; ++cc) dst[rr * ld + cc] = 0.f;
+    for (int rr = rows; rr < rows_pad; ++rr)
+        for (int cc = threadIdx.x; cc < cols_pad; cc += NT) dst[rr * ld + cc] = 0.f;
+}
+template <int NT>
+__device__ __forceinline__ void store_x1_nt(const float* x1s, float2* x1_out, int b, int h, int H, int m2c, int C, int C_pad,
+                                            int NP) {
+    float2* dst = x1_out + ((long long)(b * H + h) * m2c) * C;
+    for (int idx = threadIdx.x; idx < m2c * C; idx += NT) {
+        const int kx = idx / C, c = idx % C;
+        float re = 0.f, im = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            re += x1s[(w * C_pad + c) * NP + 2 * kx];
+            im += x1s[(w * C_pad + c) * NP + 2 * kx + 1];
+        }
+        dst[idx] = make_float2(re, im);
+    }
+}
+
+// Backward `spatial` (MODE 1 / 2 with a gradient destination) as TWO ROLES in one workgroup of eight waves.  The by-products of
+// the backward pass -- skip-weight gradient, bias gradient -- feed neither `out` nor `x1_out` and depend only on tin_s / pprev_s,
+// which are complete at the first barrier; in fno_spatial_kernel they run behind the row DFT on the same four waves (one wave per
+// SIMD, nothing to hide a wait behind) and the next launch of the chain waits for them.  Here
+//   role A, waves 0-3: the chain.  Exactly fno_spatial_kernel up to store_x1: same thread-to-element mapping (every stride is 256),
+//           same arithmetic, same three barriers.
+//   role B, waves 4-7: the by-products.  While role A stages (up to barrier 1, where the SIMDs mostly wait for global memory):
+//           the old slab values, and the four per-wave partial tiles of gK -- its MFMA fragments are 16 contiguous bytes of a row
+//           of `tin` / `pprev`, so they are read straight from global memory -- into an LDS region of their own (gks cannot alias
+//           gs / ks / s1 here: role A is filling them).  Between barriers 1 and 2, next to the main GEMM: the cross-wave sum,
+//           the bias row sums from tin_s, the slab write / atomics.  Then it only arrives at barriers 2 and 3.
+// All eight waves meet at the same three barriers, on every path: each is at the top level of the kernel.  Role A's count is that
+// of fno_spatial_kernel.  (Measured, profiles/r08_experiments.md: with role B's GEMM next to the main GEMM both slow down -- MFMA
+// and VALU of one SIMD do not overlap -- and a dependent chain of additions next to MFMAs waits for one MFMA per addition.)
+// Results are bit for bit those of fno_spatial_kernel: partial w2 is one mfma16_chunk chain from zero over the chunks kc = w2,
+// w2 + 4, ... of the same values; the partials are summed w2 = 0 .. 3 from 0.f, then old + v; the bias gradient is the sequential
+// sum over x = 0 .. W-1 from 0.f (16-byte LDS reads), then old + s.
+template <int NCB, int NBN, int MODE>
+__global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
+    static_assert(MODE == 1 || MODE == 2, "backward modes only");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NTA = 256;                      // threads of role A (and of role B)
+    const int LDP = a.W + 4, LDK = a.C_pad + 4, LDS1 = a.NP + 4;
+    float* tin_s = smem;                          // [C_pad][LDP]
+    float* tout_s = tin_s + a.C_pad * LDP;        // [C_pad][LDP]
+    float* pprev_s = tout_s + a.C_pad * LDP;      // [C_pad][LDP]
+    float* ft = pprev_s + a.C_pad * LDP;          // [NP][LDP]
+    float* x1s = ft + a.NP * LDP;                 // [4 waves][C_pad][NP]
+    float* gs = x1s + 4 * a.C_pad * a.NP;         // [NP][LDP]
+    float* ks = gs + a.NP * LDP;                  // [C_pad][LDK]
+    float* s1 = ks + a.C_pad * LDK;               // [C_pad][LDS1]
+    float* gks = s1 + a.C_pad * LDS1;             // [4 waves][C_pad][C_pad]   role B's own
+
+    const int tid = threadIdx.x, lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane(wave_id());   // wave-uniform: the role branches are scalar branches
+    const bool role_a = w < 4;
+    const int tb = tid - NTA, w2 = w - 4;         // role B's thread / wave index
+    const int r = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+    const int W4 = a.W / 4, nwb = a.W / 16;
+    const int tile_units = a.C_pad * W4, tab_units = a.NP * W4;
+    DLWP_SPAN_BEGIN();
+    DLWP_STAMP(0);
+    // ---- issue phase (role A: as fno_spatial_kernel; role B: the running partials of this workgroup's gradient slab)
+    float4 tv[2], pv[2];
+    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), fv = gv;
+    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);   // wskip: one 16-byte unit per role-A thread, the rest in the tail loop
+    int nk = 0;
+    constexpr int MJ = 16;
+    float2 sv[MJ];
+    float2 twl = make_float2(0.f, 0.f);
+    const long long jstride = (long long)a.m2c * a.C;
+    constexpr int SLQ = 4;
+    float slab_old[SLQ], slab_b_old = 0.f;
+#pragma unroll
+    for (int k = 0; k < SLQ; ++k) slab_old[k] = 0.f;
+    const long long slab_off = (long long)blockIdx.x * (((long long)a.C * a.C + a.C + 3) & ~3LL);
+    const int bias_c = 4 * lane + w2;             // role B: bias-gradient channel of this lane (lanes 0-15 of each wave)
+    constexpr int BQ = 16;                        // ... its row pieces read ahead (a whole row at W = 64)
+    const bool bias_on = !role_a && (a.g_bias || a.gslab) && lane < 16 && bias_c < a.C;
+    if (role_a) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int u = tid + NTA * k, c = u / W4, x4 = u - c * W4;
+            tv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            pv[k] = tv[k];
+            if (u < tile_units && c < a.C) {
+                const long long off = (((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4;
+                tv[k] = *reinterpret_cast<const float4*>(&a.tin[off]);
+                pv[k] = *reinterpret_cast<const float4*>(&a.pprev[off]);
+            }
+        }
+        if (tid < tab_units) {
+            gv = reinterpret_cast<const float4*>(a.G)[tid];
+            if (a.x1_out) fv = reinterpret_cast<const float4*>(a.FT)[tid];
+        }
+        nk = a.vec_w ? min((a.C * a.C) >> 2, NTA) : 0;
+        if (tid < nk) kv = reinterpret_cast<const float4*>(a.wskip)[tid];
+        const int d_kx = tid / a.C_pad, d_o = tid - d_kx * a.C_pad;
+        const bool d_valid = tid < a.C_pad * (a.NP / 2) && d_kx < a.m2c && d_o < a.C;
+        const float2* sp = a.spec + (((long long)b * a.m1) * a.m2c + (d_valid ? d_kx : 0)) * a.C + (d_valid ? d_o : 0);
+#pragma unroll
+        for (int j = 0; j < MJ; ++j) sv[j] = sp[(j < a.m1 ? j : a.m1 - 1) * jstride];
+        const int twj = (lane & 15) < a.m1 ? (lane & 15) : a.m1 - 1;
+        twl = a.twH[twj * a.H + h];
+    } else {
+        if (a.gslab && a.gslab_accumulate) {
+#pragma unroll
+            for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tb + NTA * k, a.C * a.C - 1)];
+            slab_b_old = a.gslab[slab_off + a.C * a.C + min(bias_c, a.C - 1)];
+        }
+        // gK partial of wave w2: sum over its 16-pixel chunks of g_pre[o][w] * act(x)[i][w].  The MFMA fragments are 16 contiguous
+        // bytes of a row of `tin` / `pprev`: they come straight from global memory (the values role A is putting into tin_s /
+        // pprev_s; rows >= C are zero there), so this GEMM runs while role A waits for its own loads, not next to the main GEMM
+        f32x4 kacc[NCB][NCB];
+#pragma unroll
+        for (int ob = 0; ob < NCB; ++ob)
+#pragma unroll
+            for (int ib = 0; ib < NCB; ++ib) kacc[ob][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kc = w2; kc < nwb; kc += 4) {
+            f32x4 ta[NCB], pb[NCB];
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {   // clamped addresses, selects afterwards: all loads in flight together
+                const int c = cb * 16 + r;
+                const long long off = (((long long)b * a.C + min(c, a.C - 1)) * a.H + h) * a.W + kc * 16 + 4 * g;
+                ta[cb] = *reinterpret_cast<const f32x4*>(&a.tin[off]);
+                pb[cb] = *reinterpret_cast<const f32x4*>(&a.pprev[off]);
+            }
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {
+                const bool ok = cb * 16 + r < a.C;
+                ta[cb] = ok ? ta[cb] : f32x4{0.f, 0.f, 0.f, 0.f};
+                pb[cb] = ok ? pb[cb] : f32x4{0.f, 0.f, 0.f, 0.f};
+                if (a.act_tin) ta[cb] = gelu4(ta[cb]);
+            }
+#pragma unroll
+            for (int ib = 0; ib < NCB; ++ib) {
+                f32x4 b4 = pb[ib];
+                if (a.act_prev) {
+                    b4 = gelu4(b4);
+                }
+#pragma unroll
+                for (int ob = 0; ob < NCB; ++ob) kacc[ob][ib] = mfma16_chunk(ta[ob], b4, kacc[ob][ib]);
+            }
+        }
+#pragma unroll
+        for (int ob = 0; ob < NCB; ++ob)
+#pragma unroll
+            for (int ib = 0; ib < NCB; ++ib)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    gks[((w2 * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
+        DLWP_STAMP_IF(blockIdx.x == 0 && tb == 0, 13);
+    }
+    DLWP_STAMP(1);
+
+    // ---- commit phase (role A)
+    if (role_a) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int u = tid + NTA * k, c = u / W4, x4 = u - c * W4;
+            if (u < tile_units) {
+                float4 v = tv[k];
+                if (a.act_tin) { const f32x4 ga = gelu4(f32x4{v.x, v.y, v.z, v.w}); v = make_float4(ga[0], ga[1], ga[2], ga[3]); }
+                *reinterpret_cast<float4*>(&tin_s[c * LDP + 4 * x4]) = v;
+                *reinterpret_cast<float4*>(&pprev_s[c * LDP + 4 * x4]) = pv[k];
+            }
+        }
+        for (int idx = tid + 2 * NTA; idx < tile_units; idx += NTA) {
+            const int c = idx / W4, x4 = idx % W4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f), pvv = v;
+            if (c < a.C) {
+                const long long off = (((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4;
+                v = *reinterpret_cast<const float4*>(&a.tin[off]);
+                if (a.act_tin) { const f32x4 ga = gelu4(f32x4{v.x, v.y, v.z, v.w}); v = make_float4(ga[0], ga[1], ga[2], ga[3]); }
+                pvv = *reinterpret_cast<const float4*>(&a.pprev[off]);
+            }
+            *reinterpret_cast<float4*>(&tin_s[c * LDP + 4 * x4]) = v;
+            *reinterpret_cast<float4*>(&pprev_s[c * LDP + 4 * x4]) = pvv;
+        }
+        DLWP_STAMP(2);
+        if (tid < tab_units) {
+            const int n = tid / W4, x4 = tid - n * W4;
+            *reinterpret_cast<float4*>(&gs[n * LDP + 4 * x4]) = gv;
+            if (a.x1_out) *reinterpret_cast<float4*>(&ft[n * LDP + 4 * x4]) = fv;
+        }
+        for (int idx = tid + NTA; idx < tab_units; idx += NTA) {
+            const int n = idx / W4, x4 = idx % W4;
+            *reinterpret_cast<float4*>(&gs[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.G[n * a.W + 4 * x4]);
+            if (a.x1_out)
+                *reinterpret_cast<float4*>(&ft[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.FT[n * a.W + 4 * x4]);
+        }
+        if (tid < nk) {
+            const float vv[4] = {kv.x, kv.y, kv.z, kv.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * tid + q, rr = fastdiv(e, a.dC), cc = e - rr * a.C;
+                ks[a.transpose_w ? cc * LDK + rr : rr * LDK + cc] = vv[q];
+            }
+        }
+        if (a.transpose_w) stage_matrix_tail_nt<NTA, true>(ks, LDK, a.wskip, a.C, a.C, a.dC, nk);
+        else stage_matrix_tail_nt<NTA, false>(ks, LDK, a.wskip, a.C, a.C, a.dC, nk);
+        zero_padding_nt<NTA>(ks, LDK, a.C, a.C, a.C_pad, a.C_pad);
+        DLWP_STAMP(3);
+        // inverse H-axis step for this row: s1[o][2kx(+1)] = sum_j spec[b][j][kx][o] * conj(twH[j][h])
+        float twx[MJ], twy[MJ];
+#pragma unroll
+        for (int j = 0; j < MJ; ++j) { twx[j] = __shfl(twl.x, j, 16); twy[j] = __shfl(twl.y, j, 16); }
+        for (int idx = tid; idx < a.C_pad * (a.NP / 2); idx += NTA) {
+            const int kx = idx / a.C_pad, o = idx - kx * a.C_pad;
+            float re = 0.f, im = 0.f;
+            if (idx == tid) {   // first chunk: operands already in registers
+#pragma unroll
+                for (int j = 0; j < MJ; ++j) {
+                    if (j < a.m1) {
+                        re += sv[j].x * twx[j] + sv[j].y * twy[j];   // v * conj(t)
+                        im += sv[j].y * twx[j] - sv[j].x * twy[j];
+                    }
+                }
+            }
+            if (kx < a.m2c && o < a.C) {
+                const float2* sp2 = a.spec + (((long long)b * a.m1) * a.m2c + kx) * a.C + o;
+                for (int j = (idx == tid ? MJ : 0); j < a.m1; ++j) {
+                    const float2 v = sp2[j * jstride];
+                    const float2 t = a.twH[j * a.H + h];
+                    re += v.x * t.x + v.y * t.y;
+                    im += v.y * t.x - v.x * t.y;
+                }
+            }
+            const bool ok = kx < a.m2c && o < a.C;
+            s1[o * LDS1 + 2 * kx] = ok ? re : 0.f;
+            s1[o * LDS1 + 2 * kx + 1] = ok ? im : 0.f;
+        }
+        DLWP_STAMP(4);
+    }
+    __syncthreads();   // 1: tin_s, pprev_s, gs, ks, s1 complete (role A); the four gK partials complete (role B)
+    DLWP_STAMP(5);
+
+    if (role_a) {
+        // main concatenated-K GEMM: acc[o][w] = sum_i ks[o][i] tin[i][w] + sum_n s1[o][n] gs[n][w]
+        for (int wb = w; wb < nwb; wb += 4) {
+            f32x4 acc[NCB];
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kc = 0; kc < NCB; ++kc) {
+                f32x4 b4;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) b4[s] = tin_s[(kc * 16 + 4 * g + s) * LDP + wb * 16 + r];
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) {
+                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&ks[(cb * 16 + r) * LDK + kc * 16 + 4 * g]);
+                    acc[cb] = mfma16_chunk(a4, b4, acc[cb]);
+                }
+            }
+#pragma unroll
+            for (int nc = 0; nc < NBN; ++nc) {
+                f32x4 b4;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) b4[s] = gs[(nc * 16 + 4 * g + s) * LDP + wb * 16 + r];
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) {
+                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&s1[(cb * 16 + r) * LDS1 + nc * 16 + 4 * g]);
+                    acc[cb] = mfma16_chunk(a4, b4, acc[cb]);
+                }
+            }
+            float ep[NCB][4];
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o = cb * 16 + 4 * g + j, x = wb * 16 + r;
+                    ep[cb][j] = MODE == 1 ? pprev_s[o * LDP + x] : 0.f;
+                }
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {
+                f32x4 v4 = acc[cb];
+                const f32x4 e4 = f32x4{ep[cb][0], ep[cb][1], ep[cb][2], ep[cb][3]};
+                if (MODE == 1) v4 *= gelu_grad4(e4);              // packed fp32 polynomial
+#pragma unroll
+                for (int j = 0; j < 4; ++j) tout_s[(cb * 16 + 4 * g + j) * LDP + wb * 16 + r] = v4[j];
+            }
+        }
+        DLWP_STAMP(6);
+    } else {
+        // cross-wave sum of the gK partials (w2 = 0 .. 3 from 0.f), then old + v into the slab, or the atomics.  The first SLQ
+        // elements of a thread: all LDS reads first, then the sums (a read-then-use loop pays the LDS latency per element)
+        // Bias gradient: channel 4 lane + w2 on lanes 0-15 of every wave, its row of tin_s as 16-byte reads (the first BQ issued
+        // here, in front of the sums), additions in the order x = 0 .. W-1 from 0.f.
+        const float4* brow = reinterpret_cast<const float4*>(&tin_s[min(bias_c, a.C_pad - 1) * LDP]);
+        float4 bq[BQ];
+        if (bias_on) {
+#pragma unroll
+            for (int q = 0; q < BQ; ++q) bq[q] = brow[min(q, W4 - 1)];
+        }
+        float pq[SLQ][4];
+#pragma unroll
+        for (int k = 0; k < SLQ; ++k) {
+            const int idx = min(tb + NTA * k, a.C * a.C - 1), o = fastdiv(idx, a.dC), i = idx - o * a.C;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pq[k][q] = gks[(q * a.C_pad + o) * a.C_pad + i];
+        }
+#pragma unroll
+        for (int k = 0; k < SLQ; ++k) {
+            const int idx = tb + NTA * k;
+            float v = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v += pq[k][q];
+            if (idx < a.C * a.C) {
+                if (a.gslab) a.gslab[slab_off + idx] = (a.gslab_accumulate ? slab_old[k] : 0.f) + v;
+                else atomic_add_f32(&a.g_wskip[idx], v);   // all workgroups hit the same C*C words: slow, API path only
+            }
+        }
+        for (int idx = tb + NTA * SLQ; idx < a.C * a.C; idx += NTA) {
+            const int o = fastdiv(idx, a.dC), i = idx - o * a.C;
+            float v = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v += gks[(q * a.C_pad + o) * a.C_pad + i];
+            if (a.gslab) {
+                float* sl = a.gslab + slab_off + idx;
+                *sl = (a.gslab_accumulate ? *sl : 0.f) + v;
+            } else {
+                atomic_add_f32(&a.g_wskip[idx], v);
+            }
+        }
+        if (bias_on) {
+            float bias_sum = 0.f;
+#pragma unroll
+            for (int q = 0; q < BQ; ++q)
+                if (q < W4) { bias_sum += bq[q].x; bias_sum += bq[q].y; bias_sum += bq[q].z; bias_sum += bq[q].w; }
+            for (int x4 = BQ; x4 < W4; ++x4) {
+                const float4 v = brow[x4];
+                bias_sum += v.x; bias_sum += v.y; bias_sum += v.z; bias_sum += v.w;
+            }
+            if (a.gslab) a.gslab[slab_off + a.C * a.C + bias_c] = (a.gslab_accumulate ? slab_b_old : 0.f) + bias_sum;
+            else atomic_add_f32(&a.g_bias[bias_c], bias_sum);
+        }
+        DLWP_STAMP_IF(blockIdx.x == 0 && tb == 0, 15);
+    }
+    // 2: tout_s complete.  Role B is finished: it touches no LDS behind this barrier and must not wait for its slab stores in
+    // front of one (__syncthreads() is a fence as well: vmcnt(0)); it only arrives, here and at the third.
+    if (role_a) __syncthreads(); else __builtin_amdgcn_s_barrier();
+    DLWP_STAMP(7);
+
+    if (role_a) {
+        for (int idx = tid; idx < a.C * W4; idx += NTA) {
+            const int c = idx / W4, x4 = idx % W4;
+            *reinterpret_cast<float4*>(&a.out[(((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4]) =
+                *reinterpret_cast<const float4*>(&tout_s[c * LDP + 4 * x4]);
+        }
+        DLWP_STAMP(8);
+        if (a.x1_out) tile_rows_dft<NCB, NBN>(tout_s, ft, x1s, LDP, a.NP, nwb, a.x1_act != 0);
+        DLWP_STAMP(9);
+    }
+    // 3: x1s complete
+    if (role_a) __syncthreads(); else __builtin_amdgcn_s_barrier();
+    DLWP_STAMP(11);
+    if (role_a && a.x1_out) store_x1_nt<NTA>(x1s, a.x1_out, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
+    DLWP_STAMP(12);
+    DLWP_STAMP_WAVE(24);
+    DLWP_SPAN_END();
+}
+
 // ------------------------------------------------------------------------------------------
 // Per-mode stage.  One 512-thread workgroup per kept mode (j,kx).  Everything it reads is issued
 // as batched independent loads up front (the mode's [C][C] weight slice as 16-byte loads straight
@@ -1054,23 +1434,35 @@ int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hip
     a.dC = make_fastdiv(p->C);
     a.C = p->C; a.H = p->H; a.W = p->W; a.m1 = p->m1; a.m2c = p->m2c; a.C_pad = p->C_pad; a.NP = p->NP;
     const int LDP = p->W + 4;
-    size_t dead = (size_t)p->NP * LDP + (size_t)p->C_pad * (p->C_pad + 4) + (size_t)p->C_pad * (p->NP + 4);
-    if (dead < (size_t)4 * p->C_pad * p->C_pad) dead = (size_t)4 * p->C_pad * p->C_pad;
-    const size_t lds = sizeof(float) * ((size_t)3 * p->C_pad * LDP + (size_t)p->NP * LDP +
-                                        (size_t)4 * p->C_pad * p->NP + p->C_pad + dead);
-    const dim3 grid(s->B * p->H), block(256);
+    const size_t gemm_ops = (size_t)p->NP * LDP + (size_t)p->C_pad * (p->C_pad + 4) + (size_t)p->C_pad * (p->NP + 4);   // gs, ks, s1
+    const size_t gks = (size_t)4 * p->C_pad * p->C_pad;
+    const size_t live = (size_t)3 * p->C_pad * LDP + (size_t)p->NP * LDP + (size_t)4 * p->C_pad * p->NP;
+    const size_t lds = sizeof(float) * (live + p->C_pad + (gemm_ops > gks ? gemm_ops : gks));
+    // two-role form of the backward kernel: gks next to gs / ks / s1 instead of over them
+    const size_t lds_roles = sizeof(float) * (live + gemm_ops + gks);
+    const dim3 grid(s->B * p->H);
     int rc;
     const int mode = !a.is_bwd ? 0 : (a.act_prev ? 1 : 2);
-#define LAUNCH_MODE(N, M, MD)                                                                     \
-    if ((rc = set_lds(fno_spatial_kernel<N, M, MD>, lds, "fno_spatial")) != DLWP_OK) return rc; \
-    hipLaunchKernelGGL((fno_spatial_kernel<N, M, MD>), grid, block, lds, stream, a);
-#define LAUNCH(N, M)                                   \
-    if (mode == 0) { LAUNCH_MODE(N, M, 0) }            \
-    else if (mode == 1) { LAUNCH_MODE(N, M, 1) }       \
-    else { LAUNCH_MODE(N, M, 2) }
+    // The by-products get waves of their own when the backward launch has a skip-weight gradient to form and the larger
+    // footprint fits the 160 KiB of a CU: on 64-wide rows C_pad 16 / 32 / 48 (65 KiB at C_pad 32), on 32-wide rows C_pad 64 too.
+    // It does not fit for C_pad 64 on 64-wide rows (161.5 KiB: C 49 .. 64 at the published grid) nor for C_pad 32 on 256-wide
+    // rows (161 KiB): those shapes keep the four-wave kernel, as does a backward launch without g_wskip / slab.
+    const bool roles = a.is_bwd && (a.g_wskip || a.gslab) && lds_roles <= (size_t)160 * 1024;
+#define LAUNCH_KERNEL(K, NT, BYTES)                                              \
+    if ((rc = set_lds(K, BYTES, "fno_spatial")) != DLWP_OK) return rc;           \
+    hipLaunchKernelGGL(K, grid, dim3(NT), BYTES, stream, a);
+#define LAUNCH(N, M)                                                                       \
+    if (mode == 0) { LAUNCH_KERNEL((fno_spatial_kernel<N, M, 0>), 256, lds) }              \
+    else if (mode == 1) {                                                                  \
+        if (roles) { LAUNCH_KERNEL((fno_spatial_roles_kernel<N, M, 1>), 512, lds_roles) }  \
+        else { LAUNCH_KERNEL((fno_spatial_kernel<N, M, 1>), 256, lds) }                    \
+    } else {                                                                               \
+        if (roles) { LAUNCH_KERNEL((fno_spatial_roles_kernel<N, M, 2>), 512, lds_roles) }  \
+        else { LAUNCH_KERNEL((fno_spatial_kernel<N, M, 2>), 256, lds) }                    \
+    }
     DISPATCH_NCB_NBN(p->C_pad / 16, p->NP / 16, LAUNCH)
 #undef LAUNCH
-#undef LAUNCH_MODE
+#undef LAUNCH_KERNEL
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
@@ -1108,6 +1500,39 @@ extern "C" int dlwp_fno_block_bwd(const dlwp_fno_plan* p, const float* x, int ac
     s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
     s.out = g_x; s.g_wskip = g_wskip; s.g_bias = g_bias; s.inverse_adjoint = 1; s.B = B;
     return dlwp_fno_spatial(p, &s, stream);
+}
+
+extern "C" long long dlwp_fno_block_slab_floats(const dlwp_fno_plan* p, int B) {
+    return p && B > 0 ? (long long)B * p->H * dlwp_fno_gslab_stride(p->C) : 0;
+}
+
+extern "C" int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                       const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                                       float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
+                                       void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && slab && workspace && B > 0,
+                 DLWP_E_INVALID, "fno_block_bwd_slab: NULL argument or B<=0");
+    DLWP_REQUIRE(!dlwp_fno_is_wide(p), DLWP_E_UNSUPPORTED, "fno_block_bwd_slab: narrow layers only (hidden_channels <= 64, 2-D plan)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    float2* g1 = static_cast<float2*>(workspace);
+    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
+    int rc;
+    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
+    if ((rc = dlwp_fno_mix_bwd(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat),
+                               gxhat, reinterpret_cast<float2*>(g_wspec), B, stream))) return rc;
+    dlwp_fno_spatial_args s{};
+    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
+    s.out = g_x; s.gslab = slab; s.gslab_accumulate = slab_accumulate; s.inverse_adjoint = 1; s.B = B;
+    return dlwp_fno_spatial(p, &s, stream);
+}
+
+extern "C" int dlwp_fno_block_slab_fold(const dlwp_fno_plan* p, const float* slab, float* g_wskip, float* g_bias, int B,
+                                        void* stream) {
+    DLWP_REQUIRE(p && slab && g_wskip && g_bias && B > 0, DLWP_E_INVALID, "fno_block_slab_fold: NULL argument or B<=0");
+    dlwp_fold_job q{};
+    q.slab = slab; q.nslab = B * p->H; q.stride = dlwp_fno_gslab_stride(p->C);
+    q.d1 = g_wskip; q.n1 = (long long)p->C * p->C; q.d2 = g_bias; q.n2 = p->C;
+    return dlwp_fold_slabs(&q, 1, static_cast<hipStream_t>(stream));
 }
 
 #ifdef DLWP_STAMPS

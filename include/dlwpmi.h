@@ -136,6 +136,17 @@ int dlwp_fno_block_bwd(const dlwp_fno_plan* plan, const float* x, int act_in, co
                        const float* wskip, const float* g_pre, const float* xhat, float* g_x,
                        float* g_wspec, float* g_wskip, float* g_bias, int B, void* workspace,
                        void* stream);
+/* The same backward as the rollout trainer runs it (narrow layers, hidden_channels <= 64): the skip-weight and bias    */
+/* gradients go into a per-workgroup partial slab of dlwp_fno_block_slab_floats() floats (plain stores when           */
+/* slab_accumulate == 0, read-modify-write by the owning workgroup otherwise: deterministic, no same-address float     */
+/* atomics) and dlwp_fno_block_slab_fold ACCUMULATES the folded slab into g_wskip / g_bias.                            */
+long long dlwp_fno_block_slab_floats(const dlwp_fno_plan* plan, int B);
+int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* plan, const float* x, int act_in, const float* wspec,
+                            const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                            float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
+                            void* stream);
+int dlwp_fno_block_slab_fold(const dlwp_fno_plan* plan, const float* slab, float* g_wskip, float* g_bias,
+                             int B, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Training-step pieces (nsbench/scripts/train.py:113-131: MSELoss, Adam).               */
