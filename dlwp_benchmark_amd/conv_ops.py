@@ -1,0 +1,235 @@
+"""3 x 3 convolutions and the ConvLSTM cell over libdlwpmi (csrc/conv3x3.hip; include/dlwpmi.h dlwp_conv3x3_* / dlwp_convlstm_*).
+
+Activations are channels-last fp32 `[B, H, W, C]`.  The padding is a pair of per-axis modes (height, width), each "zeros" or
+"circular"; it is resolved inside the kernels, so neither a padded tensor nor `cat(x, h_prev)` is ever written.  The weight
+stays `nn.Conv2d`'s `[Cout, Cin, 3, 3]` parameter; the kernels read packed images of it (`pack_weight`), which a model refreshes
+once per forward pass and shares between its time steps.  There is no CPU or torch fallback.
+"""
+import torch
+import torch.nn as nn
+
+from . import lib as L
+from .token_ops import _grad_slot
+
+PAD = {"zeros": 0, "circular": 1}
+ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2}
+IMG_FWD, IMG_GATES, IMG_DGRAD = 0, 1, 2
+
+
+def _pad_codes(padding):
+    if isinstance(padding, str):
+        padding = (padding, padding)
+    try:
+        return PAD[padding[0]], PAD[padding[1]]
+    except (KeyError, IndexError, TypeError):
+        raise ValueError(f"padding must be 'zeros' / 'circular' or a (height, width) pair of them, not {padding!r}") from None
+
+
+def _check_weight(weight):
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"a [Cout, Cin, 3, 3] weight is needed, not {tuple(weight.shape)}")
+
+
+def pack_weight(weight, kind):
+    """The image of a `[Cout, Cin, 3, 3]` weight that the kernels read: IMG_FWD (forward), IMG_GATES (forward of a cell weight)
+    or IMG_DGRAD (input gradient).  One launch; no gradient flows through it (the Functions below route it to `weight`)."""
+    _check_weight(weight)
+    lib = L.load()
+    cout, cin = weight.shape[0], weight.shape[1]
+    n = lib.dlwp_conv3x3_image_floats(cin, cout, kind)
+    if n < 0:
+        L.check(int(n))
+    w = weight.detach()
+    img = torch.empty(n, device=w.device)
+    L.check(lib.dlwp_conv3x3_pack(L.ptr(w.contiguous()), L.ptr(img), cin, cout, kind, L.stream()))
+    return img
+
+
+class PackedWeight:
+    """Forward and input-gradient images of one weight, packed at construction (two launches)."""
+
+    def __init__(self, weight, cell=False, need_grad=True):
+        self.fwd = pack_weight(weight, IMG_GATES if cell else IMG_FWD)
+        self.dgrad = pack_weight(weight, IMG_DGRAD) if need_grad else None
+
+
+def _cl(t, what):
+    if t.dtype != torch.float32:
+        raise L.DlwpError(f"{what}: fp32 needed, not {t.dtype}")
+    return t.contiguous()
+
+
+def _weight_grad(x1, x2, dz, weight_shape, wslot, bslot, has_bias, pads):
+    """gW, gb of a convolution: straight into the gradient slots where they exist (returns None for those)."""
+    lib = L.load()
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[-1] if x2 is not None else 0
+    cout = weight_shape[0]
+    gw = wslot if wslot is not None else torch.zeros(weight_shape, device=dz.device)
+    gb = None
+    if has_bias:
+        gb = bslot if bslot is not None else torch.zeros(cout, device=dz.device)
+    n = lib.dlwp_conv3x3_wgrad_ws_floats(B, H, W, C1 + C2, cout)
+    if n < 0:
+        L.check(int(n))
+    ws = torch.empty(n, device=dz.device)
+    L.check(lib.dlwp_conv3x3_wgrad(L.ptr(x1), L.ptr(x2), L.ptr(dz), L.ptr(ws), L.ptr(gw), L.ptr(gb), B, H, W, C1, C2, cout,
+                                   pads[0], pads[1], L.stream()))
+    return (None if wslot is not None else gw), (None if (bslot is not None or not has_bias) else gb)
+
+
+class _Conv3x3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x1, x2, weight, bias, packed, pad_h, pad_w, act):
+        lib = L.load()
+        x1 = _cl(x1, "conv3x3")
+        x2 = _cl(x2, "conv3x3") if x2 is not None else None
+        B, H, W, C1 = x1.shape
+        C2 = x2.shape[-1] if x2 is not None else 0
+        cout = weight.shape[0]
+        if weight.shape[1] != C1 + C2 or (x2 is not None and x2.shape[:3] != x1.shape[:3]):
+            raise L.DlwpError(f"conv3x3: weight {tuple(weight.shape)} does not fit inputs with {C1} + {C2} channels")
+        y = torch.empty(B, H, W, cout, device=x1.device)
+        L.check(lib.dlwp_conv3x3_fwd(L.ptr(x1), L.ptr(x2), L.ptr(packed.fwd), L.ptr(bias), L.ptr(y), None, B, H, W, C1, C2, cout, 0,
+                                     pad_h, pad_w, act, L.stream()))
+        ctx.save_for_backward(x1, x2, y if act else None)
+        ctx.packed, ctx.pads, ctx.act = packed, (pad_h, pad_w), act
+        ctx.wshape, ctx.has_bias = weight.shape, bias is not None
+        ctx.wslot = _grad_slot(weight)
+        ctx.bslot = _grad_slot(bias) if bias is not None else None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = L.load()
+        x1, x2, y = ctx.saved_tensors
+        B, H, W, C1 = x1.shape
+        C2 = x2.shape[-1] if x2 is not None else 0
+        cout = ctx.wshape[0]
+        dz = _cl(gy, "conv3x3 backward")
+        if ctx.act:
+            g = dz
+            dz = torch.empty_like(g)
+            L.check(lib.dlwp_conv3x3_act_bwd(L.ptr(y), L.ptr(g), L.ptr(dz), g.numel(), ctx.act, L.stream()))
+        need1, need2 = ctx.needs_input_grad[0], (x2 is not None and ctx.needs_input_grad[1])
+        g1 = torch.empty_like(x1) if need1 else None
+        g2 = torch.empty_like(x2) if need2 else None
+        if need1 or need2:
+            if ctx.packed.dgrad is None:
+                raise L.DlwpError("conv3x3: this weight was packed without its input-gradient image")
+            L.check(lib.dlwp_conv3x3_fwd(L.ptr(dz), None, L.ptr(ctx.packed.dgrad), None, L.ptr(g1), L.ptr(g2), B, H, W, cout, 0, C1, C2,
+                                         ctx.pads[0], ctx.pads[1], 0, L.stream()))
+        gw = gb = None
+        if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
+            gw, gb = _weight_grad(x1, x2, dz, ctx.wshape, ctx.wslot, ctx.bslot, ctx.has_bias, ctx.pads)
+        return g1, g2, gw, gb, None, None, None, None
+
+
+def conv3x3(x, weight, bias=None, padding="zeros", act=None, x2=None, packed=None):
+    """`act(conv2d(cat(x, x2), weight, bias))`, 3 x 3, stride 1, same size, on channels-last `[B, H, W, C]` tensors.
+    padding: "zeros" / "circular" or a (height, width) pair; act: None / "tanh" / "relu"; packed: the weight's PackedWeight
+    (built here when absent: two more launches)."""
+    _check_weight(weight)
+    ph, pw = _pad_codes(padding)
+    if act not in ACT:
+        raise ValueError(f"act must be None, 'tanh' or 'relu', not {act!r}")
+    if packed is None:
+        packed = PackedWeight(weight, need_grad=torch.is_grad_enabled())
+    return _Conv3x3Fn.apply(x, x2, weight, bias, packed, ph, pw, ACT[act])
+
+
+class _ConvLSTMCellFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, h_prev, c_prev, weight, bias, packed, pad_h, pad_w):
+        lib = L.load()
+        x = _cl(x, "convlstm_cell")
+        h_prev = _cl(h_prev, "convlstm_cell") if h_prev is not None else None
+        c_prev = _cl(c_prev, "convlstm_cell") if c_prev is not None else None
+        B, H, W, Cx = x.shape
+        hid = weight.shape[0] // 4
+        if weight.shape[0] != 4 * hid or weight.shape[1] != Cx + hid:
+            raise L.DlwpError(f"convlstm_cell: weight {tuple(weight.shape)} does not fit {Cx} input and {hid} hidden channels")
+        for s in (h_prev, c_prev):
+            if s is not None and tuple(s.shape) != (B, H, W, hid):
+                raise L.DlwpError(f"convlstm_cell: state {tuple(s.shape)} where {(B, H, W, hid)} is needed")
+        keep = any(ctx.needs_input_grad)
+        h = torch.empty(B, H, W, hid, device=x.device)
+        c = torch.empty_like(h)
+        gates = torch.empty(B, H, W, 4 * hid, device=x.device) if keep else None
+        L.check(lib.dlwp_convlstm_cell_fwd(L.ptr(x), L.ptr(h_prev), L.ptr(packed.fwd), L.ptr(bias), L.ptr(c_prev), L.ptr(h), L.ptr(c),
+                                           L.ptr(gates), B, H, W, Cx, hid, pad_h, pad_w, L.stream()))
+        if keep:
+            ctx.save_for_backward(x, h_prev, c_prev, c, gates)
+        ctx.packed, ctx.pads, ctx.wshape, ctx.has_bias = packed, (pad_h, pad_w), weight.shape, bias is not None
+        ctx.wslot = _grad_slot(weight)
+        ctx.bslot = _grad_slot(bias) if bias is not None else None
+        return h, c
+
+    @staticmethod
+    def backward(ctx, gh, gc):
+        lib = L.load()
+        x, h_prev, c_prev, c, gates = ctx.saved_tensors
+        B, H, W, Cx = x.shape
+        hid = c.shape[-1]
+        gh = _cl(gh, "convlstm_cell backward") if gh is not None else None
+        gc = _cl(gc, "convlstm_cell backward") if gc is not None else None
+        dz = torch.empty_like(gates)
+        dc_prev = torch.empty_like(c)
+        L.check(lib.dlwp_convlstm_gate_bwd(L.ptr(gh), L.ptr(gc), L.ptr(gates), L.ptr(c_prev), L.ptr(c), L.ptr(dz), L.ptr(dc_prev),
+                                           B * H * W, hid, L.stream()))
+        needx, needh = ctx.needs_input_grad[0], (h_prev is not None and ctx.needs_input_grad[1])
+        gx = torch.empty_like(x) if needx else None
+        ghp = torch.empty_like(h_prev) if needh else None
+        if needx or needh:
+            if ctx.packed.dgrad is None:
+                raise L.DlwpError("convlstm_cell: this weight was packed without its input-gradient image")
+            L.check(lib.dlwp_conv3x3_fwd(L.ptr(dz), None, L.ptr(ctx.packed.dgrad), None, L.ptr(gx), L.ptr(ghp), B, H, W, 4 * hid, 0, Cx,
+                                         hid, ctx.pads[0], ctx.pads[1], 0, L.stream()))
+        gw = gb = None
+        if ctx.needs_input_grad[3] or (ctx.has_bias and ctx.needs_input_grad[4]):
+            if h_prev is None:
+                # zero state: the recurrent half of the weight gets no gradient -- the product runs over cat(x, 0)
+                h_prev = torch.zeros_like(c)
+            gw, gb = _weight_grad(x, h_prev, dz, ctx.wshape, ctx.wslot, ctx.bslot, ctx.has_bias, ctx.pads)
+        return gx, ghp, (dc_prev if (c_prev is not None and ctx.needs_input_grad[2]) else None), gw, gb, None, None, None
+
+
+def convlstm_cell(x, h_prev, c_prev, weight, bias=None, padding="circular", packed=None):
+    """One ConvLSTM step on channels-last tensors: `z = conv3x3(cat(x, h_prev), weight) + bias` with the output channels
+    (input, i, f, o) in blocks of `hidden`; `c = sigmoid(f) * c_prev + sigmoid(i) * tanh(input)`, `h = sigmoid(o) * tanh(c)`.
+    Returns (h, c).  h_prev / c_prev None = zero state.  Under `torch.no_grad()` nothing is kept for a backward pass."""
+    _check_weight(weight)
+    ph, pw = _pad_codes(padding)
+    if packed is None:
+        packed = PackedWeight(weight, cell=True, need_grad=torch.is_grad_enabled())
+    return _ConvLSTMCellFn.apply(x, h_prev, c_prev, weight, bias, packed, ph, pw)
+
+
+class Conv3x3(nn.Conv2d):
+    """`nn.Conv2d(cin, cout, 3, padding=1)` on the hand-written kernel: parameter names and shapes are nn.Conv2d's, so a
+    checkpoint of the torch layer loads as it is.  `forward` takes and returns channels-FIRST `[B, C, H, W]` like nn.Conv2d
+    (two permute copies); `forward_cl` is the channels-last form the models chain.  `pad_modes`: per-axis (height, width)
+    padding, default from `padding_mode` ("zeros" / "circular" on both axes)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, padding_mode="zeros", bias=True, pad_modes=None,
+                 act=None, **kw):
+        ks = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
+        if ks != 3 or padding not in (1, (1, 1)) or padding_mode not in PAD:
+            raise ValueError("Conv3x3: kernel_size 3, padding 1 and padding_mode 'zeros' / 'circular' only")
+        super().__init__(in_channels, out_channels, 3, padding=1, padding_mode=padding_mode, bias=bias, **kw)
+        if tuple(self.stride) != (1, 1) or tuple(self.dilation) != (1, 1) or self.groups != 1:
+            raise ValueError("Conv3x3: stride 1, dilation 1, groups 1 only")
+        self.pad_modes = tuple(pad_modes) if pad_modes is not None else (padding_mode, padding_mode)
+        _pad_codes(self.pad_modes)
+        if act not in ACT:
+            raise ValueError(f"act must be None, 'tanh' or 'relu', not {act!r}")
+        self.act = act
+
+    def pack(self, cell=False):
+        return PackedWeight(self.weight, cell=cell, need_grad=torch.is_grad_enabled())
+
+    def forward_cl(self, x, x2=None, packed=None):
+        return conv3x3(x, self.weight, self.bias, self.pad_modes, self.act, x2=x2, packed=packed)
+
+    def forward(self, x):
+        return self.forward_cl(x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)

@@ -1,0 +1,517 @@
+// 3 x 3 convolutions (stride 1, "same" size) as implicit GEMMs on the exact-fp32 MFMA, and the ConvLSTM cell built on them.
+// Reference call sites: every nn.Conv2d(kernel_size=3, padding=1) of src/nsbench/models/convlstm/convlstm.py (:31-39, :105-128,
+// circular padding on both axes) and of src/dlwpbench/models/convlstm/convlstm.py (CylinderPad: circular in longitude, zeros
+// in latitude), and the cell update of ConvLSTMCell.forward (:67-80).
+//
+// Layout: activations are channels-last fp32 [B][H][W][C].  M = B*H*W pixels, N = Cout, K = 9*Cin.
+//
+// One workgroup (4 waves) owns an 8 x 16 pixel tile and NS*16 output columns.  Per chunk of 16 input channels it stages the
+// haloed 10 x 18 tile ONCE in LDS and uses it for all nine taps; the halo is resolved while staging (wrap or zeros per axis),
+// so no padded copy of a tensor exists anywhere.  The input channels may come from two tensors (x | h_prev): the chunk loop
+// runs over the concatenated axis and picks the source per channel, so cat(x, h_prev) is never written either.  K and N are
+// zero-filled up to the instruction shape in LDS and in the packed weight image only.
+//
+// MFMA (common.hip.h mfma16_chunk): lane (r, g) supplies A[pixel r][channels 4g..4g+3] and B[channels 4g..4g+3][column r] and
+// receives D[pixels 4g..4g+3][column r]: wave w owns the tile rows 2w and 2w+1 (one 16-pixel row segment per MFMA tile).
+//
+// Weight images (dlwp_conv3x3_pack) are [column block][channel chunk][tap][g][column][4 channels]: the B fragment of a lane is
+// one 16-byte LDS read and a chunk's image is one contiguous copy.  kind 1 reorders the columns of a cell weight so that the
+// four gate pre-activations of a hidden channel are the four column tiles of ONE lane; kind 2 is the flipped, transposed image
+// that turns the same kernel into the input-gradient product.
+#include "common.hip.h"
+#include "dlwpmi_internal.h"
+
+namespace {
+
+constexpr int TH = 8, TW = 16;            // pixel tile
+constexpr int HR = TH + 2, HC = TW + 2;   // with halo
+constexpr int KC = 16;                    // channels per chunk
+constexpr int AP = 20;                    // LDS floats per haloed pixel in the forward kernel (16 + 4: conflict-free 16-byte reads)
+constexpr int NPIX_H = HR * HC;           // 180
+constexpr int STAGE_IT = (NPIX_H + 15) / 16;
+constexpr int ZP = 80;                    // LDS floats per pixel of the dz tile in the weight-gradient kernel (64 + 16)
+
+enum { PAD_ZEROS = 0, PAD_CIRCULAR = 1 };
+enum { ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2 };
+enum { IMG_FWD = 0, IMG_GATES = 1, IMG_DGRAD = 2 };
+
+struct ConvArgs {
+    const float *x1, *x2;      // [B][H][W][C1], [B][H][W][C2] (x2 nullable with C2 = 0)
+    const float* wimg;
+    const float* bias;         // [N] nullable
+    float *y1, *y2;            // columns [0, N1) -> y1 [..][N1], [N1, N1 + N2) -> y2 [..][N2]; either may be NULL (not written)
+    const float* c_prev;       // cell: [B][H][W][hid] nullable (zeros)
+    float *c_out, *gates;      // cell: c [..][hid], activated gates [..][4 hid] (nullable)
+    int C1, C2, N1, N2, act;
+    int B, H, W, pad_h, pad_w, tiles_h, tiles_w;
+    int nchunks, img_chunks;   // chunks walked; chunks per column block of the image (>= nchunks)
+};
+
+// source pixel of haloed position (pr, pc) of the tile at (y0, x0): its index b*H*W + y*W + x, or -1 for a zero
+__device__ __forceinline__ int halo_pixel(int b, int y0, int x0, int pr, int pc, int H, int W, int pad_h, int pad_w) {
+    int yy = y0 - 1 + pr, xx = x0 - 1 + pc;
+    if (yy > H || xx > W) return -1;                       // beyond what any pixel of the image reads
+    if (yy < 0 || yy == H) { if (pad_h != PAD_CIRCULAR) return -1; yy = yy < 0 ? H - 1 : 0; }
+    if (xx < 0 || xx == W) { if (pad_w != PAD_CIRCULAR) return -1; xx = xx < 0 ? W - 1 : 0; }
+    return (b * H + yy) * W + xx;
+}
+
+__device__ __forceinline__ float sigmoid_f(float z) { return 1.0f / (1.0f + expf(-z)); }
+
+// CELL = false: y = act(conv + bias) to one or two destinations.  CELL = true (NS = 4, image kind 1): the LSTM update.
+template <int NS, bool CELL>
+__global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
+    extern __shared__ float lds[];
+    float* As = lds;                          // [180][AP]
+    float* Ws = lds + NPIX_H * AP;            // [9][4][NS*16][4]
+    constexpr int WIMG = 9 * 4 * NS * 16 * 4;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+    int t = blockIdx.x;
+    const int tx = t % a.tiles_w; t /= a.tiles_w;
+    const int ty = t % a.tiles_h;
+    const int b = t / a.tiles_h;
+    const int y0 = ty * TH, x0 = tx * TW, nblk = blockIdx.y;
+    const int Cin = a.C1 + a.C2;
+
+    // this thread stages channel (tid & 15) of the haloed pixels (tid >> 4) + 16 i
+    int src[STAGE_IT];
+#pragma unroll
+    for (int i = 0; i < STAGE_IT; ++i) {
+        const int p = (tid >> 4) + 16 * i;
+        const int pr = p / HC, pc = p - pr * HC;
+        src[i] = p < NPIX_H ? halo_pixel(b, y0, x0, pr, pc, a.H, a.W, a.pad_h, a.pad_w) : -2;
+    }
+    f32x4 acc[2][NS];
+#pragma unroll
+    for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+        for (int ns = 0; ns < NS; ++ns) acc[ms][ns] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const float* wsrc = a.wimg + (long long)nblk * a.img_chunks * WIMG;
+    constexpr int WIT = (WIMG / 4 + 255) / 256;
+    float v[STAGE_IT];
+    float4 wv[WIT];
+    // chunk kc's activations and weight image, global -> registers (issued one chunk ahead: in flight during the MFMAs)
+    auto fetch = [&](int kc) {
+        const int c = kc * KC + (tid & 15);
+        const float* xs = c < a.C1 ? a.x1 + c : (c < Cin ? a.x2 + (c - a.C1) : nullptr);
+        const int cs = c < a.C1 ? a.C1 : a.C2;
+#pragma unroll
+        for (int i = 0; i < STAGE_IT; ++i) v[i] = (xs && src[i] >= 0) ? xs[(long long)src[i] * cs] : 0.f;
+        const float4* w4 = reinterpret_cast<const float4*>(wsrc + (long long)kc * WIMG);
+#pragma unroll
+        for (int i = 0; i < WIT; ++i) {
+            const int u = tid + 256 * i;
+            wv[i] = u < WIMG / 4 ? w4[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    fetch(0);
+    for (int kc = 0; kc < a.nchunks; ++kc) {
+        if (kc) __syncthreads();              // the previous chunk's fragments have been read
+#pragma unroll
+        for (int i = 0; i < STAGE_IT; ++i)
+            if (src[i] != -2) As[((tid >> 4) + 16 * i) * AP + (tid & 15)] = v[i];
+#pragma unroll
+        for (int i = 0; i < WIT; ++i) {
+            const int u = tid + 256 * i;
+            if (u < WIMG / 4) reinterpret_cast<float4*>(Ws)[u] = wv[i];
+        }
+        __syncthreads();
+        if (kc + 1 < a.nchunks) fetch(kc + 1);      // after the barrier: __syncthreads() waits for loads in flight
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int dy = tap / 3, dx = tap % 3;
+            f32x4 af[2];
+#pragma unroll
+            for (int ms = 0; ms < 2; ++ms)
+                af[ms] = *reinterpret_cast<const f32x4*>(&As[((2 * w + ms + dy) * HC + r + dx) * AP + 4 * g]);
+#pragma unroll
+            for (int ns = 0; ns < NS; ++ns) {
+                const f32x4 bf = *reinterpret_cast<const f32x4*>(&Ws[((tap * 4 + g) * (NS * 16) + ns * 16 + r) * 4]);
+#pragma unroll
+                for (int ms = 0; ms < 2; ++ms) acc[ms][ns] = mfma16_chunk(af[ms], bf, acc[ms][ns]);
+            }
+        }
+    }
+
+    // epilogue: lane (r, g) holds pixels (row 2w + ms, columns 4g + j) of column tile ns, column r
+#pragma unroll
+    for (int ms = 0; ms < 2; ++ms) {
+        const int yy = y0 + 2 * w + ms;
+        if (yy >= a.H) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int xx = x0 + 4 * g + j;
+            if (xx >= a.W) continue;
+            const long long pix = ((long long)b * a.H + yy) * a.W + xx;
+            if constexpr (CELL) {
+                const int hid = a.N1, ch = nblk * 16 + r;
+                if (ch >= hid) continue;
+                float z[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) z[q] = acc[ms][q][j] + (a.bias ? a.bias[q * hid + ch] : 0.f);
+                const float gi = tanhf(z[0]), ig = sigmoid_f(z[1]), fg = sigmoid_f(z[2]), og = sigmoid_f(z[3]);
+                const float cp = a.c_prev ? a.c_prev[pix * hid + ch] : 0.f;
+                const float cn = fg * cp + ig * gi;
+                a.c_out[pix * hid + ch] = cn;
+                a.y1[pix * hid + ch] = og * tanhf(cn);
+                if (a.gates) {
+                    float* gp = a.gates + pix * 4 * hid + ch;
+                    gp[0] = gi; gp[hid] = ig; gp[2 * hid] = fg; gp[3 * hid] = og;
+                }
+            } else {
+#pragma unroll
+                for (int ns = 0; ns < NS; ++ns) {
+                    const int n = (nblk * NS + ns) * 16 + r;
+                    if (n >= a.N1 + a.N2) continue;
+                    float v = acc[ms][ns][j] + (a.bias ? a.bias[n] : 0.f);
+                    if (a.act == ACT_TANH) v = tanhf(v);
+                    else if (a.act == ACT_RELU) v = fmaxf(v, 0.f);
+                    if (n < a.N1) { if (a.y1) a.y1[pix * a.N1 + n] = v; }
+                    else if (a.y2) a.y2[pix * a.N2 + (n - a.N1)] = v;
+                }
+            }
+        }
+    }
+}
+
+// ---- weight images
+__host__ __device__ inline int img_ns(int ncols) { return ncols <= 16 ? 1 : 4; }
+
+struct PackArgs {
+    const float* w;       // [Cout][Cin][3][3]
+    float* img;
+    int Cin, Cout, kind, NS, nblk, nchunks;
+};
+
+__global__ __launch_bounds__(256) void conv3x3_pack_kernel(const PackArgs p) {
+    const long long total = (long long)p.nblk * p.nchunks * 9 * 4 * p.NS * 16 * 4;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    long long q = e;
+    const int s = q & 3; q >>= 2;
+    const int n = q % (p.NS * 16); q /= p.NS * 16;
+    const int g = q & 3; q >>= 2;
+    const int tap = q % 9; q /= 9;
+    const int kc = q % p.nchunks;
+    const int nblk = (int)(q / p.nchunks);
+    const int k = kc * KC + 4 * g + s;
+    float v = 0.f;
+    if (p.kind == IMG_DGRAD) {                      // K axis = output channels, columns = input channels, taps mirrored
+        const int ci = nblk * p.NS * 16 + n;
+        if (k < p.Cout && ci < p.Cin) v = p.w[((long long)k * p.Cin + ci) * 9 + (8 - tap)];
+    } else {
+        int co;
+        if (p.kind == IMG_GATES) {
+            const int hid = p.Cout / 4, ch = nblk * 16 + (n & 15);
+            co = ch < hid ? (n >> 4) * hid + ch : p.Cout;
+        } else {
+            co = nblk * p.NS * 16 + n;
+        }
+        if (k < p.Cin && co < p.Cout) v = p.w[((long long)co * p.Cin + k) * 9 + tap];
+    }
+    p.img[e] = v;
+}
+
+// columns, K extent and column tiles per workgroup of an image
+inline bool image_geometry(int Cin, int Cout, int kind, int* NS, int* nblk, int* nchunks) {
+    if (kind == IMG_FWD) { *NS = img_ns(Cout); *nblk = ceil_div(Cout, *NS * 16); *nchunks = ceil_div(Cin, KC); }
+    else if (kind == IMG_GATES) { *NS = 4; *nblk = ceil_div(Cout / 4, 16); *nchunks = ceil_div(Cin, KC); }
+    else if (kind == IMG_DGRAD) { *NS = img_ns(Cin); *nblk = ceil_div(Cin, *NS * 16); *nchunks = ceil_div(Cout, KC); }
+    else return false;
+    return true;
+}
+
+// ---- gate backward of the cell (element-wise).  A kernel of its own: dz is read by TWO products (input and weight gradient),
+// so it is formed once instead of in the operand-load stage of each.
+__global__ __launch_bounds__(256) void convlstm_gate_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ dc_in,
+                                                                const float* __restrict__ gates, const float* __restrict__ c_prev,
+                                                                const float* __restrict__ c, float* __restrict__ dz,
+                                                                float* __restrict__ dc_prev, long long npix, int hid) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npix * hid) return;
+    const long long pix = e / hid;
+    const int ch = (int)(e - pix * hid);
+    const float* gp = gates + pix * 4 * hid + ch;
+    const float gi = gp[0], ig = gp[hid], fg = gp[2 * hid], og = gp[3 * hid];
+    const float tc = tanhf(c[e]);
+    const float gh = dh ? dh[e] : 0.f;
+    const float dc = (dc_in ? dc_in[e] : 0.f) + gh * og * (1.f - tc * tc);
+    const float cp = c_prev ? c_prev[e] : 0.f;
+    float* zp = dz + pix * 4 * hid + ch;
+    zp[0] = dc * ig * (1.f - gi * gi);
+    zp[hid] = dc * gi * ig * (1.f - ig);
+    zp[2 * hid] = dc * cp * fg * (1.f - fg);
+    zp[3 * hid] = gh * tc * og * (1.f - og);
+    dc_prev[e] = dc * fg;
+}
+
+// dz = gy * act'(y) from the activation's OUTPUT y (tanh: 1 - y^2, relu: y > 0)
+__global__ __launch_bounds__(256) void conv3x3_act_bwd_kernel(const float* __restrict__ y, const float* __restrict__ gy,
+                                                              float* __restrict__ dz, long long n, int act) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const float yv = y[e];
+    dz[e] = act == ACT_TANH ? gy[e] * (1.f - yv * yv) : (yv > 0.f ? gy[e] : 0.f);
+}
+
+// ---- weight and bias gradient.  dW[co][ci][tap] = sum_p in[p + tap][ci] dz[p][co]: per tap a GEMM with M = input channels,
+// N = output channels, K = pixels.  Workgroup (ci block of 16, co block of 64, split s) walks the pixel tiles s, s + S, ...
+// with the haloed input tile and the dz tile in LDS; wave w owns output channels 16w..16w+15 and the nine taps (nine
+// independent accumulators).  The partial sums go to ws [S][9][Cin_pad][Cout_pad] and are folded in the fixed order s = 0..S-1
+// by the fold kernel (no atomics: two launches on the same operands are bit-identical).  The bias gradient rides along as input
+// channel Cin, which is staged as the constant 1: its centre tap is sum_p dz[p][co].
+struct WgradArgs {
+    const float *x1, *x2, *dz;
+    float* ws;
+    int C1, C2, Cout, B, H, W, pad_h, pad_w, tiles_h, tiles_w, ntiles, S, cin_pad, cout_pad;
+};
+
+__global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(const WgradArgs a) {
+    __shared__ float As[NPIX_H * KC];
+    __shared__ float Zs[TH * TW * ZP];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+    const int Cin = a.C1 + a.C2;
+    const int c = blockIdx.x * KC + (tid & 15);
+    const float* xs = c < a.C1 ? a.x1 + c : (c < Cin ? a.x2 + (c - a.C1) : nullptr);
+    const int cs = c < a.C1 ? a.C1 : a.C2;
+    const float fill = c == Cin ? 1.f : 0.f;
+    const int co0 = blockIdx.y * 64;
+    f32x4 acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    float v[STAGE_IT];
+    float zv[TH * TW / 4];
+    const int co = co0 + (tid & 63);
+    // tile t's haloed input channel and dz columns, global -> registers (issued one tile ahead)
+    auto fetch = [&](int t) {
+        int q = t;
+        const int tx = q % a.tiles_w; q /= a.tiles_w;
+        const int ty = q % a.tiles_h;
+        const int b = q / a.tiles_h;
+        const int y0 = ty * TH, x0 = tx * TW;
+#pragma unroll
+        for (int i = 0; i < STAGE_IT; ++i) {
+            const int p = (tid >> 4) + 16 * i;
+            const int pr = p / HC, pc = p - pr * HC;
+            const int sp = p < NPIX_H ? halo_pixel(b, y0, x0, pr, pc, a.H, a.W, a.pad_h, a.pad_w) : -1;
+            v[i] = xs ? (sp >= 0 ? xs[(long long)sp * cs] : 0.f) : fill;
+        }
+        // dz tile: thread -> column (tid & 63), pixels (tid >> 6) + 4 i
+#pragma unroll
+        for (int i = 0; i < TH * TW / 4; ++i) {
+            const int m = (tid >> 6) + 4 * i;
+            const int yy = y0 + (m >> 4), xx = x0 + (m & 15);
+            zv[i] = (yy < a.H && xx < a.W && co < a.Cout) ? a.dz[(((long long)b * a.H + yy) * a.W + xx) * a.Cout + co] : 0.f;
+        }
+    };
+    if ((int)blockIdx.z < a.ntiles) fetch(blockIdx.z);
+    for (int t = blockIdx.z; t < a.ntiles; t += a.S) {
+        __syncthreads();                      // the previous tile has been consumed
+#pragma unroll
+        for (int i = 0; i < STAGE_IT; ++i) {
+            const int p = (tid >> 4) + 16 * i;
+            if (p < NPIX_H) As[p * KC + (tid & 15)] = v[i];
+        }
+#pragma unroll
+        for (int i = 0; i < TH * TW / 4; ++i) Zs[((tid >> 6) + 4 * i) * ZP + (tid & 63)] = zv[i];
+        __syncthreads();
+        if (t + a.S < a.ntiles) fetch(t + a.S);
+#pragma unroll 4
+        for (int i = 0; i < TH * TW / 4; ++i) {
+            const int m = 4 * i + g, row = m >> 4, col = m & 15;
+            const float bz = Zs[m * ZP + 16 * w + r];
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap)
+                acc[tap] = mfma16(As[((row + tap / 3) * HC + col + tap % 3) * KC + r], bz, acc[tap]);
+        }
+    }
+    // lane (r, g) register j: input channel 4g + j of the block, output channel 16w + r
+    float* dst = a.ws + (long long)blockIdx.z * 9 * a.cin_pad * a.cout_pad;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            dst[((long long)tap * a.cin_pad + blockIdx.x * KC + 4 * g + j) * a.cout_pad + co0 + 16 * w + r] = acc[tap][j];
+}
+
+// gw[co][ci][tap] += sum_s ws[s][tap][ci][co];  gb[co] += sum_s ws[s][centre][Cin][co]
+__global__ __launch_bounds__(256) void conv3x3_wgrad_fold_kernel(const float* __restrict__ ws, float* gw, float* gb, int Cin,
+                                                                 int Cout, int S, int cin_pad, int cout_pad) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;      // (tap, ci <= Cin, co), co fastest
+    if (e >= (long long)9 * (Cin + 1) * Cout) return;
+    const int co = (int)(e % Cout);
+    const int ci = (int)((e / Cout) % (Cin + 1));
+    const int tap = (int)(e / ((long long)Cout * (Cin + 1)));
+    if (ci == Cin && (tap != 4 || !gb)) return;
+    const long long stride = (long long)9 * cin_pad * cout_pad;
+    const float* p = ws + ((long long)tap * cin_pad + ci) * cout_pad + co;
+    float s = 0.f;
+    for (int i = 0; i < S; ++i) s += p[i * stride];
+    if (ci == Cin) gb[co] += s;
+    else gw[((long long)co * Cin + ci) * 9 + tap] += s;
+}
+
+inline void wgrad_geometry(int B, int H, int W, int Cin, int Cout, int* cin_pad, int* cout_pad, int* ntiles, int* S) {
+    *cin_pad = round_up(Cin + 1, KC);
+    *cout_pad = round_up(Cout, 64);
+    *ntiles = B * ceil_div(H, TH) * ceil_div(W, TW);
+    const int blocks = (*cin_pad / KC) * (*cout_pad / 64);
+    int s = ceil_div(512, blocks);
+    if (s > 32) s = 32;
+    if (s > *ntiles) s = *ntiles;
+    *S = s;
+}
+
+bool pad_ok(int p) { return p == PAD_ZEROS || p == PAD_CIRCULAR; }
+
+template <int NS, bool CELL>
+int launch_conv(const ConvArgs& a, int nblk, hipStream_t s) {
+    const size_t lds = (size_t)(NPIX_H * AP + 9 * 4 * NS * 16 * 4) * sizeof(float);
+    int rc = dlwp_ensure_lds((const void*)conv3x3_kernel<NS, CELL>, lds, "conv3x3");
+    if (rc) return rc;
+    hipLaunchKernelGGL((conv3x3_kernel<NS, CELL>), dim3(a.B * a.tiles_h * a.tiles_w, nblk), dim3(256), lds, s, a);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+}  // namespace
+
+extern "C" long long dlwp_conv3x3_image_floats(int Cin, int Cout, int kind) {
+    int NS, nblk, nchunks;
+    if (Cin <= 0 || Cout <= 0 || !image_geometry(Cin, Cout, kind, &NS, &nblk, &nchunks) || (kind == IMG_GATES && Cout % 4)) {
+        dlwp_set_error("conv3x3_image_floats: bad argument (Cin %d, Cout %d, kind %d)", Cin, Cout, kind);
+        return DLWP_E_INVALID;
+    }
+    return (long long)nblk * nchunks * 9 * 4 * NS * 16 * 4;
+}
+
+extern "C" int dlwp_conv3x3_pack(const float* w, float* img, int Cin, int Cout, int kind, void* stream_) {
+    DLWP_REQUIRE(w && img, DLWP_E_INVALID, "conv3x3_pack: NULL argument");
+    DLWP_REQUIRE(Cin > 0 && Cout > 0, DLWP_E_INVALID, "conv3x3_pack: channel counts must be positive (Cin %d, Cout %d)", Cin, Cout);
+    PackArgs p{w, img, Cin, Cout, kind, 0, 0, 0};
+    DLWP_REQUIRE(image_geometry(Cin, Cout, kind, &p.NS, &p.nblk, &p.nchunks), DLWP_E_INVALID, "conv3x3_pack: unknown image kind %d",
+                 kind);
+    DLWP_REQUIRE(kind != IMG_GATES || Cout % 4 == 0, DLWP_E_INVALID, "conv3x3_pack: a cell weight has 4 * hidden output channels");
+    const long long total = (long long)p.nblk * p.nchunks * 9 * 4 * p.NS * 16 * 4;
+    hipStream_t s = (hipStream_t)stream_;
+    dlwp_prof_scope ps(s, 0.0, 4.0 * (9.0 * Cin * Cout + total), "conv3x3_pack");
+    hipLaunchKernelGGL(conv3x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+extern "C" int dlwp_conv3x3_fwd(const float* x1, const float* x2, const float* wimg, const float* bias, float* y1, float* y2, int B,
+                                int H, int W, int C1, int C2, int N1, int N2, int pad_h, int pad_w, int act, void* stream_) {
+    DLWP_REQUIRE(x1 && wimg && (y1 || y2), DLWP_E_INVALID, "conv3x3_fwd: NULL argument");
+    DLWP_REQUIRE(B > 0 && H > 0 && W > 0 && C1 > 0 && C2 >= 0 && N1 >= 0 && N2 >= 0 && N1 + N2 > 0, DLWP_E_INVALID,
+                 "conv3x3_fwd: bad shape (B %d, H %d, W %d, C %d + %d, N %d + %d)", B, H, W, C1, C2, N1, N2);
+    DLWP_REQUIRE((C2 == 0) == (x2 == nullptr), DLWP_E_INVALID, "conv3x3_fwd: the second input and its channel count go together");
+    DLWP_REQUIRE((!y1 || N1 > 0) && (!y2 || N2 > 0), DLWP_E_INVALID, "conv3x3_fwd: a destination without columns");
+    DLWP_REQUIRE(pad_ok(pad_h) && pad_ok(pad_w), DLWP_E_INVALID, "conv3x3_fwd: unknown padding code (%d, %d)", pad_h, pad_w);
+    DLWP_REQUIRE(act >= ACT_NONE && act <= ACT_RELU, DLWP_E_INVALID, "conv3x3_fwd: unknown activation code %d", act);
+    DLWP_REQUIRE((long long)B * H * W < (1ll << 31), DLWP_E_UNSUPPORTED, "conv3x3_fwd: more than 2^31 pixels");
+    ConvArgs a{};
+    a.x1 = x1; a.x2 = x2; a.wimg = wimg; a.bias = bias; a.y1 = y1; a.y2 = y2;
+    a.C1 = C1; a.C2 = C2; a.N1 = N1; a.N2 = N2; a.act = act;
+    a.B = B; a.H = H; a.W = W; a.pad_h = pad_h; a.pad_w = pad_w;
+    a.tiles_h = ceil_div(H, TH); a.tiles_w = ceil_div(W, TW);
+    int NS, nblk;
+    image_geometry(C1 + C2, N1 + N2, IMG_FWD, &NS, &nblk, &a.nchunks);
+    a.img_chunks = a.nchunks;
+    hipStream_t s = (hipStream_t)stream_;
+    const double px = (double)B * H * W;
+    dlwp_prof_scope ps(s, 2.0 * px * 9 * (C1 + C2) * (N1 + N2), 4.0 * (px * (C1 + C2 + N1 + N2) + 9.0 * (C1 + C2) * (N1 + N2)),
+                       NS == 1 ? "conv3x3_n16" : "conv3x3_n64");
+    return NS == 1 ? launch_conv<1, false>(a, nblk, s) : launch_conv<4, false>(a, nblk, s);
+}
+
+extern "C" int dlwp_convlstm_cell_fwd(const float* x, const float* h_prev, const float* wimg, const float* bias, const float* c_prev,
+                                      float* h, float* c, float* gates, int B, int H, int W, int Cx, int hid, int pad_h, int pad_w,
+                                      void* stream_) {
+    DLWP_REQUIRE(x && wimg && h && c, DLWP_E_INVALID, "convlstm_cell_fwd: NULL argument");
+    DLWP_REQUIRE(B > 0 && H > 0 && W > 0 && Cx > 0 && hid > 0, DLWP_E_INVALID, "convlstm_cell_fwd: bad shape (B %d, H %d, W %d, Cx %d, hidden %d)",
+                 B, H, W, Cx, hid);
+    DLWP_REQUIRE(pad_ok(pad_h) && pad_ok(pad_w), DLWP_E_INVALID, "convlstm_cell_fwd: unknown padding code (%d, %d)", pad_h, pad_w);
+    DLWP_REQUIRE((long long)B * H * W < (1ll << 31), DLWP_E_UNSUPPORTED, "convlstm_cell_fwd: more than 2^31 pixels");
+    ConvArgs a{};
+    a.x1 = x; a.x2 = h_prev; a.wimg = wimg; a.bias = bias; a.y1 = h; a.c_prev = c_prev; a.c_out = c; a.gates = gates;
+    a.C1 = Cx; a.C2 = h_prev ? hid : 0; a.N1 = hid;
+    a.B = B; a.H = H; a.W = W; a.pad_h = pad_h; a.pad_w = pad_w;
+    a.tiles_h = ceil_div(H, TH); a.tiles_w = ceil_div(W, TW);
+    int NS, nblk;
+    image_geometry(Cx + hid, 4 * hid, IMG_GATES, &NS, &nblk, &a.img_chunks);   // the image always spans x | h_prev
+    // zero state (h_prev NULL): the chunks beyond x add nothing; one that straddles x | h_prev reads zeros for the absent half
+    a.nchunks = h_prev ? a.img_chunks : ceil_div(Cx, KC);
+    hipStream_t s = (hipStream_t)stream_;
+    const double px = (double)B * H * W;
+    dlwp_prof_scope ps(s, 2.0 * px * 9 * (Cx + a.C2) * 4 * hid, 4.0 * (px * (Cx + a.C2 + 3 * hid + (gates ? 4 * hid : 0)) + 36.0 * (Cx + hid) * hid),
+                       "convlstm_cell_fwd");
+    return launch_conv<4, true>(a, nblk, s);
+}
+
+extern "C" int dlwp_convlstm_gate_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev, const float* c,
+                                      float* dz, float* dc_prev, long long npix, int hid, void* stream_) {
+    DLWP_REQUIRE(gates && c && dz && dc_prev && (dh || dc), DLWP_E_INVALID, "convlstm_gate_bwd: NULL argument");
+    DLWP_REQUIRE(npix > 0 && hid > 0, DLWP_E_INVALID, "convlstm_gate_bwd: bad shape (%lld pixels, hidden %d)", npix, hid);
+    hipStream_t s = (hipStream_t)stream_;
+    const double n = (double)npix * hid;
+    dlwp_prof_scope ps(s, 30.0 * n, 4.0 * n * 13, "convlstm_gate_bwd");
+    hipLaunchKernelGGL(convlstm_gate_bwd_kernel, dim3((unsigned)((npix * hid + 255) / 256)), dim3(256), 0, s, dh, dc, gates, c_prev, c,
+                       dz, dc_prev, npix, hid);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+extern "C" int dlwp_conv3x3_act_bwd(const float* y, const float* gy, float* dz, long long n, int act, void* stream_) {
+    DLWP_REQUIRE(y && gy && dz, DLWP_E_INVALID, "conv3x3_act_bwd: NULL argument");
+    DLWP_REQUIRE(n > 0, DLWP_E_INVALID, "conv3x3_act_bwd: bad element count %lld", n);
+    DLWP_REQUIRE(act == ACT_TANH || act == ACT_RELU, DLWP_E_INVALID, "conv3x3_act_bwd: unknown activation code %d", act);
+    hipStream_t s = (hipStream_t)stream_;
+    dlwp_prof_scope ps(s, 3.0 * n, 12.0 * n, "conv3x3_act_bwd");
+    hipLaunchKernelGGL(conv3x3_act_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, gy, dz, n, act);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+extern "C" long long dlwp_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) {
+        dlwp_set_error("conv3x3_wgrad_ws_floats: bad shape (B %d, H %d, W %d, Cin %d, Cout %d)", B, H, W, Cin, Cout);
+        return DLWP_E_INVALID;
+    }
+    int cin_pad, cout_pad, ntiles, S;
+    wgrad_geometry(B, H, W, Cin, Cout, &cin_pad, &cout_pad, &ntiles, &S);
+    return (long long)S * 9 * cin_pad * cout_pad;
+}
+
+extern "C" int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float* dz, float* ws, float* gw, float* gb, int B, int H,
+                                  int W, int C1, int C2, int Cout, int pad_h, int pad_w, void* stream_) {
+    DLWP_REQUIRE(x1 && dz && ws && gw, DLWP_E_INVALID, "conv3x3_wgrad: NULL argument");
+    DLWP_REQUIRE(B > 0 && H > 0 && W > 0 && C1 > 0 && C2 >= 0 && Cout > 0, DLWP_E_INVALID,
+                 "conv3x3_wgrad: bad shape (B %d, H %d, W %d, C %d + %d, Cout %d)", B, H, W, C1, C2, Cout);
+    DLWP_REQUIRE((C2 == 0) == (x2 == nullptr), DLWP_E_INVALID, "conv3x3_wgrad: the second input and its channel count go together");
+    DLWP_REQUIRE(pad_ok(pad_h) && pad_ok(pad_w), DLWP_E_INVALID, "conv3x3_wgrad: unknown padding code (%d, %d)", pad_h, pad_w);
+    DLWP_REQUIRE((long long)B * H * W < (1ll << 31), DLWP_E_UNSUPPORTED, "conv3x3_wgrad: more than 2^31 pixels");
+    WgradArgs a{};
+    a.x1 = x1; a.x2 = x2; a.dz = dz; a.ws = ws;
+    a.C1 = C1; a.C2 = C2; a.Cout = Cout; a.B = B; a.H = H; a.W = W; a.pad_h = pad_h; a.pad_w = pad_w;
+    a.tiles_h = ceil_div(H, TH); a.tiles_w = ceil_div(W, TW);
+    wgrad_geometry(B, H, W, C1 + C2, Cout, &a.cin_pad, &a.cout_pad, &a.ntiles, &a.S);
+    hipStream_t s = (hipStream_t)stream_;
+    const double px = (double)B * H * W;
+    const int Cin = C1 + C2;
+    {
+        dlwp_prof_scope ps(s, 2.0 * px * 9 * Cin * Cout, 4.0 * (px * (Cin + Cout) + (double)a.S * 9 * a.cin_pad * a.cout_pad), "conv3x3_wgrad");
+        hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3(a.cin_pad / KC, a.cout_pad / 64, a.S), dim3(256), 0, s, a);
+        DLWP_LAUNCH_CHECK();
+    }
+    {
+        const long long n = (long long)9 * (Cin + 1) * Cout;
+        dlwp_prof_scope ps(s, (double)a.S * n, 4.0 * (a.S + 2.0) * n, "conv3x3_wgrad_fold");
+        hipLaunchKernelGGL(conv3x3_wgrad_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, gw, gb, Cin, Cout, a.S,
+                           a.cin_pad, a.cout_pad);
+        DLWP_LAUNCH_CHECK();
+    }
+    return DLWP_OK;
+}

@@ -190,7 +190,15 @@ SIGNATURES = {
     "dlwp_comm_destroy": (None, [_V]),
     "dlwp_comm_allreduce": (_I, [_V, _V, _L, _V]),
     "dlwp_comm_broadcast": (_I, [_V, _V, _L, _I, _V]),
-    "dlwp_fno_mix_fwd_probe": (_I, [_V, _V, _V, _V, _V, _I, _V]),
+    "dlwp_conv3x3_image_floats": (_L, [_I, _I, _I]),
+    "dlwp_conv3x3_pack": (_I, [_V, _V, _I, _I, _I, _V]),
+    "dlwp_conv3x3_fwd": (_I, [_V] * 6 + [_I] * 10 + [_V]),
+    "dlwp_convlstm_cell_fwd": (_I, [_V] * 8 + [_I] * 7 + [_V]),
+    "dlwp_convlstm_gate_bwd": (_I, [_V] * 7 + [_L, _I, _V]),
+    "dlwp_conv3x3_act_bwd": (_I, [_V, _V, _V, _L, _I, _V]),
+    "dlwp_conv3x3_wgrad_ws_floats": (_L, [_I] * 5),
+    "dlwp_conv3x3_wgrad": (_I, [_V] * 6 + [_I] * 8 + [_V]),
+    "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),
     "dlwp_debug_null_kernels": (_I, [_I, _I, _V]),
     "dlwp_debug_spin_kernels": (_I, [_I, _I, _I, _I, _I, _V]),
     "dlwp_debug_clock_probe": (_I, [_V, _I, _I, _V]),

@@ -955,6 +955,50 @@ int dlwp_comm_allreduce(dlwp_comm* comm, float* buf, long long n, void* stream);
 /* buf[0:n] <- root's buf (initial parameters, Adam state on resume)                       */
 int dlwp_comm_broadcast(dlwp_comm* comm, float* buf, long long n, int root, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* 3 x 3 convolutions (stride 1, same size) and the ConvLSTM cell (csrc/conv3x3.hip).  Replace every       */
+/* nn.Conv2d(kernel_size=3, padding=1, padding_mode="circular") of src/nsbench/models/convlstm/convlstm.py */
+/* (:31-39, :105-128) and the CylinderPad + nn.Conv2d pairs of src/dlwpbench/models/convlstm/convlstm.py.   */
+/* Activations are channels-last fp32 [B][H][W][C]; fp32 operands on the exact-fp32 MFMA, fp32 sums.        */
+/* Codes: padding per axis 0 = zeros, 1 = circular; activation 0 = none, 1 = tanh, 2 = relu;                */
+/* image kind 0 = forward, 1 = forward of a cell weight (gate columns interleaved), 2 = input gradient.    */
+/* No padded tensor and no cat(x, h_prev) is ever written: the halo is resolved while a tile is staged.    */
+/*                                                                                                         */
+/* Floats of the packed image of a weight [Cout][Cin][3][3] (negative: bad argument).                      */
+long long dlwp_conv3x3_image_floats(int Cin, int Cout, int kind);
+/* img <- the image of w [Cout][Cin][3][3] (nn.Conv2d's layout, which stays the parameter); written whole. */
+int dlwp_conv3x3_pack(const float* w, float* img, int Cin, int Cout, int kind, void* stream);
+/* y = act(conv3x3(cat(x1 [..][C1], x2 [..][C2]), w) + bias): output columns [0, N1) are WRITTEN to        */
+/* y1 [..][N1], columns [N1, N1 + N2) to y2 [..][N2]; x2 (with C2 = 0), bias, and one of y1 / y2 may be    */
+/* NULL (that destination is skipped).  wimg: kind 0 image of [N1 + N2][C1 + C2][3][3].  With the kind 2    */
+/* image of a weight [C1][N1 + N2][3][3] the same call is the INPUT GRADIENT of that convolution: x1 = dz,   */
+/* y1 = gradient of its first input, y2 = gradient of its second (the cell: dx and dh_prev).                */
+int dlwp_conv3x3_fwd(const float* x1, const float* x2, const float* wimg, const float* bias, float* y1,
+                     float* y2, int B, int H, int W, int C1, int C2, int N1, int N2, int pad_h, int pad_w,
+                     int act, void* stream);
+/* One ConvLSTM cell step (convlstm.py:67-80): z = conv3x3(cat(x [..][Cx], h_prev [..][hid])) + bias with   */
+/* output channels (input, i, f, o) in blocks of hid; c = sig(f) c_prev + sig(i) tanh(input),                */
+/* h = sig(o) tanh(c).  wimg: kind 1 image of [4 hid][Cx + hid][3][3].  WRITES h, c [..][hid] and (unless    */
+/* NULL) the activated gates [..][4 hid] for the backward pass; the pre-activations never reach memory.      */
+/* h_prev / c_prev NULL = zero state (the recurrent half of the product is skipped).                         */
+int dlwp_convlstm_cell_fwd(const float* x, const float* h_prev, const float* wimg, const float* bias,
+                           const float* c_prev, float* h, float* c, float* gates, int B, int H, int W, int Cx,
+                           int hid, int pad_h, int pad_w, void* stream);
+/* Gate backward of the cell, element-wise: from dh, dc (either may be NULL = zero), the stored gates,      */
+/* c_prev (NULL = zero) and c it WRITES dz [npix][4 hid] (pre-activation gradient, the weight's channel       */
+/* order) and dc_prev [npix][hid].                                                                          */
+int dlwp_convlstm_gate_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev,
+                           const float* c, float* dz, float* dc_prev, long long npix, int hid, void* stream);
+/* dz = gy * act'(y) from the activation's OUTPUT y (1: 1 - y^2, 2: y > 0); written.                       */
+int dlwp_conv3x3_act_bwd(const float* y, const float* gy, float* dz, long long n, int act, void* stream);
+/* Weight and bias gradient: gw [Cout][C1 + C2][3][3] += sum_pixels in[p + tap][ci] dz[p][co] with the       */
+/* forward's halo rules, gb [Cout] += sum_pixels dz (NULL: none).  Both are ACCUMULATED into.  ws: scratch    */
+/* of dlwp_conv3x3_wgrad_ws_floats floats (per-workgroup partial sums, folded in a fixed order: no atomics,   */
+/* repeated launches are bit-identical).                                                                    */
+long long dlwp_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout);
+int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float* dz, float* ws, float* gw, float* gb, int B,
+                       int H, int W, int C1, int C2, int Cout, int pad_h, int pad_w, void* stream);
+
 /* bench probe: ONE forward `spatial` launch of an inner FNO block as the rollout issues it     */
 /* (x = previous pre-activation, GELU on load; spec = [B][m1][m2c][C][2] mixed modes; fused      */
 /* W-axis DFT of gelu(pre) into x1_out [B][H][m2c][C][2]).                                       */
