@@ -264,12 +264,20 @@ __device__ __forceinline__ int matload_units(int rows, int cols, bool vec_ok, in
     const int cap = maxu * (int)blockDim.x;
     return n4 < cap ? n4 : cap;
 }
-template <bool TR>
+// Stride of a loop that the threads of a workgroup share: blockDim.x, or NT where the first NT threads of a larger workgroup
+// share it (stage_matrix_tail, zero_padding, store_x1).  A compile-time parameter, and each form keeps its own type: a run-time
+// stride changed the registers of every caller.
+template <int NT>
+__device__ __forceinline__ auto wg_stride() {
+    if constexpr (NT != 0) return NT;
+    else return (unsigned)blockDim.x;
+}
+template <bool TR, int NT = 0>
 __device__ __forceinline__ void stage_matrix_tail(float* dst, int ld, const float* __restrict__ src, int rows, int cols,
                                                   FastDiv dcols, int done4) {
     const int n = rows * cols;
 #pragma unroll 4
-    for (int e = 4 * done4 + threadIdx.x; e < n; e += blockDim.x) {
+    for (int e = 4 * done4 + threadIdx.x; e < n; e += wg_stride<NT>()) {
         const int rr = fastdiv(e, dcols);
         const int cc = e - rr * cols;
         dst[TR ? cc * ld + rr : rr * ld + cc] = src[e];
@@ -277,12 +285,13 @@ __device__ __forceinline__ void stage_matrix_tail(float* dst, int ld, const floa
 }
 
 // zero the padding of an LDS image holding a [rows][cols] matrix inside [rows_pad][cols_pad] (row stride ld)
+template <int NT = 0>
 __device__ __forceinline__ void zero_padding(float* dst, int ld, int rows, int cols, int rows_pad, int cols_pad) {
     if (cols_pad > cols)
-        for (int rr = threadIdx.x; rr < rows; rr += blockDim.x)
+        for (int rr = threadIdx.x; rr < rows; rr += wg_stride<NT>())
             for (int cc = cols; cc < cols_pad; ++cc) dst[rr * ld + cc] = 0.f;
     for (int rr = rows; rr < rows_pad; ++rr)
-        for (int cc = threadIdx.x; cc < cols_pad; cc += blockDim.x) dst[rr * ld + cc] = 0.f;
+        for (int cc = threadIdx.x; cc < cols_pad; cc += wg_stride<NT>()) dst[rr * ld + cc] = 0.f;
 }
 
 // ---- in-kernel phase stamps (diagnostic build only: -DDLWP_STAMPS; never in the shipped library)

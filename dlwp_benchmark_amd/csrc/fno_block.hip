@@ -63,55 +63,81 @@ __global__ __launch_bounds__(256) void fno_rows_kernel(RowsDev a) {
     store_x1(x1s, a.x1, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
 }
 
-// MODE 0: forward (+bias); 1: backward with GELU' of the block input; 2: backward, input was not activated
-template <int NCB, int NBN, int MODE>
-__global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int LDP = a.W + 4, LDK = a.C_pad + 4, LDS1 = a.NP + 4;
-    float* tin_s = smem;                          // [C_pad][LDP]
-    float* tout_s = tin_s + a.C_pad * LDP;        // [C_pad][LDP]
-    float* pprev_s = tout_s + a.C_pad * LDP;      // [C_pad][LDP]    (bwd)
-    float* ft = pprev_s + a.C_pad * LDP;          // [NP][LDP]
-    float* x1s = ft + a.NP * LDP;                 // [4 waves][C_pad][NP]
-    float* bias_s = x1s + 4 * a.C_pad * a.NP;     // [C_pad]
-    float* gs = bias_s + a.C_pad;                 // [NP][LDP]       dead after the main GEMM
-    float* ks = gs + a.NP * LDP;                  // [C_pad][LDK]    dead after the main GEMM
-    float* s1 = ks + a.C_pad * LDK;               // [C_pad][LDS1]   dead after the main GEMM
-    float* gks = gs;                              // [4 waves][C_pad][C_pad] (bwd) aliases gs/ks/s1
+// ------------------------------------------------------------------------------------------
+// The `spatial` chain: one image row (b,h) from its inputs to `out` and, fused, the next stage's row DFT.  256 threads (four
+// waves) run it: the whole workgroup of fno_spatial_kernel, role A (waves 0-3) of fno_spatial_roles_kernel.  The phases below are
+// its only copy, so the two kernels share thread-to-element mapping and arithmetic by construction; each kernel calls them in
+// order and keeps the three barriers between them at its own top level.  Every stride is SPATIAL_NT, never blockDim.x.
+constexpr int SPATIAL_NT = 256;
+constexpr int SPATIAL_MJ = 16;   // H-step operands a thread holds in registers (modes j < 16; a larger m1 loops)
 
-    const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
-    const int r = lane & 15, g = lane >> 4;
-    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
-    const int W4 = a.W / 4, nwb = a.W / 16;
-    const bool need_prev = a.is_bwd && (a.act_prev || a.g_wskip || a.gslab);
-    DLWP_SPAN_BEGIN();
-    DLWP_STAMP(0);
-    // ---- issue phase: the first chunk of every independent input goes into registers before any LDS
-    // write, so the workgroup pays one global latency for all of them (larger shapes loop afterwards)
+// LDS of the two kernels.  ROLES is the only place where the layouts differ: the four-wave kernel has the forward's bias_s, and
+// its gks (bwd) lies over gs / ks / s1, which are dead after the main GEMM; in the two-role kernel role B fills gks while role A
+// fills gs / ks / s1, so it is a region of its own (`lds` / `lds_roles` in dlwp_fno_spatial).
+struct SpatialLds {
+    float *tin_s, *tout_s, *pprev_s;   // [C_pad][LDP] each; pprev_s: bwd
+    float* ft;                         // [NP][LDP]
+    float* x1s;                        // [4 waves][C_pad][NP]
+    float* bias_s;                     // [C_pad]          four-wave layout only
+    float *gs, *ks, *s1;               // [NP][LDP], [C_pad][LDK], [C_pad][LDS1]: the operands of the main GEMM
+    float* gks;                        // [4 waves][C_pad][C_pad]
+    int LDP, LDK, LDS1;
+};
+template <bool ROLES>
+__device__ __forceinline__ SpatialLds carve_spatial_lds(float* smem, const SpatialDev& a) {
+    SpatialLds L;
+    L.LDP = a.W + 4; L.LDK = a.C_pad + 4; L.LDS1 = a.NP + 4;
+    L.tin_s = smem;
+    L.tout_s = L.tin_s + a.C_pad * L.LDP;
+    L.pprev_s = L.tout_s + a.C_pad * L.LDP;
+    L.ft = L.pprev_s + a.C_pad * L.LDP;
+    L.x1s = L.ft + a.NP * L.LDP;
+    L.bias_s = ROLES ? nullptr : L.x1s + 4 * a.C_pad * a.NP;
+    L.gs = L.x1s + 4 * a.C_pad * a.NP + (ROLES ? 0 : a.C_pad);
+    L.ks = L.gs + a.NP * L.LDP;
+    L.s1 = L.ks + a.C_pad * L.LDK;
+    L.gks = ROLES ? L.s1 + a.C_pad * L.LDS1 : L.gs;
+    return L;
+}
+
+// what the issue phase leaves in registers for the commit phase and the H-step
+struct SpatialLoads {
+    float4 tv[2], pv[2], gv, fv;
+    MatLoad<1> lk;
+    int nk;
+    float2 sv[SPATIAL_MJ], twl;
+    float bias_v;
+};
+
+// Issue phase: the first chunk of every independent input goes into registers before any LDS write, so the workgroup pays one
+// global latency for all of them (larger shapes loop afterwards).  MODE 0 is the only one with a bias.
+template <int MODE>
+__device__ __forceinline__ void spatial_issue(const SpatialDev& a, int b, int h, bool need_prev, SpatialLoads& R) {
+    const int tid = threadIdx.x, lane = lane_id(), W4 = a.W / 4;
     const int tile_units = a.C_pad * W4, tab_units = a.NP * W4;
-    float4 tv[2], pv[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int u = tid + 256 * k, c = u / W4, x4 = u - c * W4;
-        tv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        pv[k] = tv[k];
+        const int u = tid + SPATIAL_NT * k, c = u / W4, x4 = u - c * W4;
+        R.tv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        R.pv[k] = R.tv[k];
         if (u < tile_units && c < a.C) {
             const long long off = (((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4;
-            tv[k] = *reinterpret_cast<const float4*>(&a.tin[off]);
-            if (need_prev) pv[k] = *reinterpret_cast<const float4*>(&a.pprev[off]);
+            R.tv[k] = *reinterpret_cast<const float4*>(&a.tin[off]);
+            if (need_prev) R.pv[k] = *reinterpret_cast<const float4*>(&a.pprev[off]);
         }
     }
-    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), fv = gv;
+    R.gv = make_float4(0.f, 0.f, 0.f, 0.f);
+    R.fv = R.gv;
     if (tid < tab_units) {
-        gv = reinterpret_cast<const float4*>(a.G)[tid];
-        if (a.x1_out) fv = reinterpret_cast<const float4*>(a.FT)[tid];
+        R.gv = reinterpret_cast<const float4*>(a.G)[tid];
+        if (a.x1_out) R.fv = reinterpret_cast<const float4*>(a.FT)[tid];
     }
-    MatLoad<1> lk;
-    const int nk = matload_units(a.C, a.C, a.vec_w != 0, 1);
-    lk.issue(a.wskip, nk);
+    // wskip: one 16-byte unit per thread, the rest in the tail loop of the commit phase.  The unit count is written out, not
+    // matload_units(): that caps by blockDim.x, which is 512 in the two-role kernel.  MatLoad itself indexes unit k with
+    // k * blockDim.x: harmless here only because MAXU is 1 (k = 0)
+    R.nk = a.vec_w ? min((a.C * a.C) >> 2, SPATIAL_NT) : 0;
+    R.lk.issue(a.wskip, R.nk);
     // inverse H-axis step operands for this row: spec[b][j][kx][o], j < min(m1, 16)
-    constexpr int MJ = 16;
-    float2 sv[MJ];
     const int d_kx = tid / a.C_pad, d_o = tid - d_kx * a.C_pad;
     const bool d_valid = tid < a.C_pad * (a.NP / 2) && d_kx < a.m2c && d_o < a.C;
     // unconditional loads from clamped (always valid) addresses: a select right behind each load would
@@ -119,39 +145,35 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
     const float2* sp = a.spec + (((long long)b * a.m1) * a.m2c + (d_valid ? d_kx : 0)) * a.C + (d_valid ? d_o : 0);
     const long long jstride = (long long)a.m2c * a.C;
 #pragma unroll
-    for (int j = 0; j < MJ; ++j) sv[j] = sp[(j < a.m1 ? j : a.m1 - 1) * jstride];
+    for (int j = 0; j < SPATIAL_MJ; ++j) R.sv[j] = sp[(j < a.m1 ? j : a.m1 - 1) * jstride];
     // twiddles of this row: lane j (mod 16) holds tw[j]; a uniform index would become a chain of scalar loads
     // with a wait each.  Broadcast with shuffles at use.
     const int twj = (lane & 15) < a.m1 ? (lane & 15) : a.m1 - 1;
-    const float2 twl = a.twH[twj * a.H + h];
-    const float bias_raw = a.bias ? a.bias[tid < a.C ? tid : 0] : 0.f;
-    const float bias_v = tid < a.C ? bias_raw : 0.f;
-    // running partials of this workgroup's gradient slab (read-modify-write across net calls): fetched here, with every
-    // other input, instead of in front of the final store (a dependent global round trip at the very end of the kernel)
-    constexpr int SLQ = 4;
-    float slab_old[SLQ], slab_b_old = 0.f;
-#pragma unroll
-    for (int k = 0; k < SLQ; ++k) slab_old[k] = 0.f;
-    const long long slab_off = (long long)blockIdx.x * (((long long)a.C * a.C + a.C + 3) & ~3LL);
-    if (a.is_bwd && a.gslab && a.gslab_accumulate) {
-#pragma unroll
-        for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tid + 256 * k, a.C * a.C - 1)];
-        slab_b_old = a.gslab[slab_off + a.C * a.C + min(tid, a.C - 1)];
+    R.twl = a.twH[twj * a.H + h];
+    R.bias_v = 0.f;
+    if (MODE == 0) {
+        const float bias_raw = a.bias ? a.bias[tid < a.C ? tid : 0] : 0.f;
+        R.bias_v = tid < a.C ? bias_raw : 0.f;
     }
-    DLWP_STAMP(1);
+}
 
-    // ---- commit phase
+// Commit phase: the tile (tin, pprev), the tables (G, FT), Wskip and, in MODE 0, the bias into LDS
+template <int MODE>
+__device__ __forceinline__ void spatial_commit(const SpatialDev& a, const SpatialLds& L, int b, int h, bool need_prev,
+                                               const SpatialLoads& R) {
+    const int tid = threadIdx.x, W4 = a.W / 4, LDP = L.LDP;
+    const int tile_units = a.C_pad * W4, tab_units = a.NP * W4;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const int u = tid + 256 * k, c = u / W4, x4 = u - c * W4;
+        const int u = tid + SPATIAL_NT * k, c = u / W4, x4 = u - c * W4;
         if (u < tile_units) {
-            float4 v = tv[k];
+            float4 v = R.tv[k];
             if (a.act_tin) { const f32x4 ga = gelu4(f32x4{v.x, v.y, v.z, v.w}); v = make_float4(ga[0], ga[1], ga[2], ga[3]); }
-            *reinterpret_cast<float4*>(&tin_s[c * LDP + 4 * x4]) = v;
-            if (need_prev) *reinterpret_cast<float4*>(&pprev_s[c * LDP + 4 * x4]) = pv[k];
+            *reinterpret_cast<float4*>(&L.tin_s[c * LDP + 4 * x4]) = v;
+            if (need_prev) *reinterpret_cast<float4*>(&L.pprev_s[c * LDP + 4 * x4]) = R.pv[k];
         }
     }
-    for (int idx = tid + 512; idx < tile_units; idx += 256) {
+    for (int idx = tid + 2 * SPATIAL_NT; idx < tile_units; idx += SPATIAL_NT) {
         const int c = idx / W4, x4 = idx % W4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f), pvv = v;
         if (c < a.C) {
@@ -160,45 +182,52 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
             if (a.act_tin) { const f32x4 ga = gelu4(f32x4{v.x, v.y, v.z, v.w}); v = make_float4(ga[0], ga[1], ga[2], ga[3]); }
             if (need_prev) pvv = *reinterpret_cast<const float4*>(&a.pprev[off]);
         }
-        *reinterpret_cast<float4*>(&tin_s[c * LDP + 4 * x4]) = v;
-        if (need_prev) *reinterpret_cast<float4*>(&pprev_s[c * LDP + 4 * x4]) = pvv;
+        *reinterpret_cast<float4*>(&L.tin_s[c * LDP + 4 * x4]) = v;
+        if (need_prev) *reinterpret_cast<float4*>(&L.pprev_s[c * LDP + 4 * x4]) = pvv;
     }
     DLWP_STAMP(2);
     if (tid < tab_units) {
         const int n = tid / W4, x4 = tid - n * W4;
-        *reinterpret_cast<float4*>(&gs[n * LDP + 4 * x4]) = gv;
-        if (a.x1_out) *reinterpret_cast<float4*>(&ft[n * LDP + 4 * x4]) = fv;
+        *reinterpret_cast<float4*>(&L.gs[n * LDP + 4 * x4]) = R.gv;
+        if (a.x1_out) *reinterpret_cast<float4*>(&L.ft[n * LDP + 4 * x4]) = R.fv;
     }
-    for (int idx = tid + 256; idx < tab_units; idx += 256) {
+    for (int idx = tid + SPATIAL_NT; idx < tab_units; idx += SPATIAL_NT) {
         const int n = idx / W4, x4 = idx % W4;
-        *reinterpret_cast<float4*>(&gs[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.G[n * a.W + 4 * x4]);
+        *reinterpret_cast<float4*>(&L.gs[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.G[n * a.W + 4 * x4]);
         if (a.x1_out)
-            *reinterpret_cast<float4*>(&ft[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.FT[n * a.W + 4 * x4]);
+            *reinterpret_cast<float4*>(&L.ft[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.FT[n * a.W + 4 * x4]);
     }
     if (a.transpose_w) {
-        lk.commit<true>(ks, LDK, a.C, a.dC, nk);
-        stage_matrix_tail<true>(ks, LDK, a.wskip, a.C, a.C, a.dC, nk);
+        R.lk.commit<true>(L.ks, L.LDK, a.C, a.dC, R.nk);
+        stage_matrix_tail<true, SPATIAL_NT>(L.ks, L.LDK, a.wskip, a.C, a.C, a.dC, R.nk);
     } else {
-        lk.commit<false>(ks, LDK, a.C, a.dC, nk);
-        stage_matrix_tail<false>(ks, LDK, a.wskip, a.C, a.C, a.dC, nk);
+        R.lk.commit<false>(L.ks, L.LDK, a.C, a.dC, R.nk);
+        stage_matrix_tail<false, SPATIAL_NT>(L.ks, L.LDK, a.wskip, a.C, a.C, a.dC, R.nk);
     }
-    zero_padding(ks, LDK, a.C, a.C, a.C_pad, a.C_pad);
-    if (tid < a.C_pad) bias_s[tid] = bias_v;
-    for (int idx = tid + 256; idx < a.C_pad; idx += 256) bias_s[idx] = (a.bias && idx < a.C) ? a.bias[idx] : 0.f;
-    DLWP_STAMP(3);
-    // inverse H-axis step for this row: s1[o][2kx(+1)] = sum_j spec[b][j][kx][o] * conj(twH[j][h])
+    zero_padding<SPATIAL_NT>(L.ks, L.LDK, a.C, a.C, a.C_pad, a.C_pad);
+    if (MODE == 0) {
+        if (tid < a.C_pad) L.bias_s[tid] = R.bias_v;
+        for (int idx = tid + SPATIAL_NT; idx < a.C_pad; idx += SPATIAL_NT) L.bias_s[idx] = (a.bias && idx < a.C) ? a.bias[idx] : 0.f;
+    }
+}
+
+// Inverse H-axis step for this row: s1[o][2kx(+1)] = sum_j spec[b][j][kx][o] * conj(twH[j][h])
+__device__ __forceinline__ void spatial_hstep(const SpatialDev& a, const SpatialLds& L, int b, int h, const SpatialLoads& R) {
+    constexpr int MJ = SPATIAL_MJ;
+    const int tid = threadIdx.x;
+    const long long jstride = (long long)a.m2c * a.C;
     float twx[MJ], twy[MJ];   // broadcast the lane-held twiddles (every lane is active here)
 #pragma unroll
-    for (int j = 0; j < MJ; ++j) { twx[j] = __shfl(twl.x, j, 16); twy[j] = __shfl(twl.y, j, 16); }
-    for (int idx = tid; idx < a.C_pad * (a.NP / 2); idx += 256) {
+    for (int j = 0; j < MJ; ++j) { twx[j] = __shfl(R.twl.x, j, 16); twy[j] = __shfl(R.twl.y, j, 16); }
+    for (int idx = tid; idx < a.C_pad * (a.NP / 2); idx += SPATIAL_NT) {
         const int kx = idx / a.C_pad, o = idx - kx * a.C_pad;
         float re = 0.f, im = 0.f;
         if (idx == tid) {   // first chunk: operands already in registers
 #pragma unroll
             for (int j = 0; j < MJ; ++j) {
                 if (j < a.m1) {
-                    re += sv[j].x * twx[j] + sv[j].y * twy[j];   // v * conj(t)
-                    im += sv[j].y * twx[j] - sv[j].x * twy[j];
+                    re += R.sv[j].x * twx[j] + R.sv[j].y * twy[j];   // v * conj(t)
+                    im += R.sv[j].y * twx[j] - R.sv[j].x * twy[j];
                 }
             }
         }
@@ -212,14 +241,16 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
             }
         }
         const bool ok = kx < a.m2c && o < a.C;
-        s1[o * LDS1 + 2 * kx] = ok ? re : 0.f;
-        s1[o * LDS1 + 2 * kx + 1] = ok ? im : 0.f;
+        L.s1[o * L.LDS1 + 2 * kx] = ok ? re : 0.f;
+        L.s1[o * L.LDS1 + 2 * kx + 1] = ok ? im : 0.f;
     }
-    DLWP_STAMP(4);
-    __syncthreads();
-    DLWP_STAMP(5);
+}
 
-    // main concatenated-K GEMM: acc[o][w] = sum_i ks[o][i] tin[i][w] + sum_n s1[o][n] gs[n][w]
+// Main concatenated-K GEMM of wave w (0-3): acc[o][w] = sum_i ks[o][i] tin[i][w] + sum_n s1[o][n] gs[n][w], epilogue into tout_s
+template <int NCB, int NBN, int MODE>
+__device__ __forceinline__ void spatial_gemm(const SpatialDev& a, const SpatialLds& L, int w) {
+    const int lane = lane_id(), r = lane & 15, g = lane >> 4;
+    const int nwb = a.W / 16, LDP = L.LDP;
     for (int wb = w; wb < nwb; wb += 4) {
         f32x4 acc[NCB];
 #pragma unroll
@@ -228,10 +259,10 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
         for (int kc = 0; kc < NCB; ++kc) {
             f32x4 b4;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) b4[s] = tin_s[(kc * 16 + 4 * g + s) * LDP + wb * 16 + r];
+            for (int s = 0; s < 4; ++s) b4[s] = L.tin_s[(kc * 16 + 4 * g + s) * LDP + wb * 16 + r];
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                const f32x4 a4 = *reinterpret_cast<const f32x4*>(&ks[(cb * 16 + r) * LDK + kc * 16 + 4 * g]);
+                const f32x4 a4 = *reinterpret_cast<const f32x4*>(&L.ks[(cb * 16 + r) * L.LDK + kc * 16 + 4 * g]);
                 acc[cb] = mfma16_chunk(a4, b4, acc[cb]);
             }
         }
@@ -239,10 +270,10 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
         for (int nc = 0; nc < NBN; ++nc) {
             f32x4 b4;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) b4[s] = gs[(nc * 16 + 4 * g + s) * LDP + wb * 16 + r];
+            for (int s = 0; s < 4; ++s) b4[s] = L.gs[(nc * 16 + 4 * g + s) * LDP + wb * 16 + r];
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                const f32x4 a4 = *reinterpret_cast<const f32x4*>(&s1[(cb * 16 + r) * LDS1 + nc * 16 + 4 * g]);
+                const f32x4 a4 = *reinterpret_cast<const f32x4*>(&L.s1[(cb * 16 + r) * L.LDS1 + nc * 16 + 4 * g]);
                 acc[cb] = mfma16_chunk(a4, b4, acc[cb]);
             }
         }
@@ -253,7 +284,7 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int o = cb * 16 + 4 * g + j, x = wb * 16 + r;
-                ep[cb][j] = MODE == 0 ? bias_s[o] : (MODE == 1 ? pprev_s[o * LDP + x] : 0.f);
+                ep[cb][j] = MODE == 0 ? L.bias_s[o] : (MODE == 1 ? L.pprev_s[o * LDP + x] : 0.f);
             }
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
@@ -262,22 +293,78 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
             if (MODE == 0) v4 += e4;
             else if (MODE == 1) v4 *= gelu_grad4(e4);              // packed fp32 polynomial
 #pragma unroll
-            for (int j = 0; j < 4; ++j) tout_s[(cb * 16 + 4 * g + j) * LDP + wb * 16 + r] = v4[j];
+            for (int j = 0; j < 4; ++j) L.tout_s[(cb * 16 + 4 * g + j) * LDP + wb * 16 + r] = v4[j];
         }
     }
-    DLWP_STAMP(6);
-    __syncthreads();
-    DLWP_STAMP(7);
+}
 
-    for (int idx = tid; idx < a.C * W4; idx += 256) {
+// tout_s to `out`, then the next stage's row DFT on it (per-wave partials into x1s; store_x1 sums them behind a barrier)
+template <int NCB, int NBN>
+__device__ __forceinline__ void spatial_out_dft(const SpatialDev& a, const SpatialLds& L, int b, int h) {
+    const int W4 = a.W / 4;
+    for (int idx = threadIdx.x; idx < a.C * W4; idx += SPATIAL_NT) {
         const int c = idx / W4, x4 = idx % W4;
         *reinterpret_cast<float4*>(&a.out[(((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4]) =
-            *reinterpret_cast<const float4*>(&tout_s[c * LDP + 4 * x4]);
+            *reinterpret_cast<const float4*>(&L.tout_s[c * L.LDP + 4 * x4]);
     }
     DLWP_STAMP(8);
-    if (a.x1_out) tile_rows_dft<NCB, NBN>(tout_s, ft, x1s, LDP, a.NP, nwb, a.x1_act != 0);
+    if (a.x1_out) tile_rows_dft<NCB, NBN>(L.tout_s, L.ft, L.x1s, L.LDP, a.NP, a.W / 16, a.x1_act != 0);
+}
+
+// The backward's by-products (skip-weight and bias gradient) are formed per kernel; only how an element leaves is shared.
+// Slab of this workgroup: {g_wskip[C*C], g_bias[C]} partials, stride C*C+C padded to 4
+__device__ __forceinline__ long long spatial_slab_off(const SpatialDev& a) {
+    return (long long)blockIdx.x * (((long long)a.C * a.C + a.C + 3) & ~3LL);
+}
+// element `e` of the slab becomes old + v (old: its running partial across net calls, 0.f on a first call); without a slab v is
+// added to *dst with a float atomic (all workgroups hit the same words: slow, API path only)
+__device__ __forceinline__ void spatial_flush(const SpatialDev& a, long long e, float* dst, float old, float v) {
+    if (a.gslab) a.gslab[e] = old + v;
+    else atomic_add_f32(dst, v);
+}
+
+// MODE 0: forward (+bias); 1: backward with GELU' of the block input; 2: backward, input was not activated
+template <int NCB, int NBN, int MODE>
+__global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const SpatialLds L = carve_spatial_lds<false>(smem, a);
+    const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
+    const int r = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+    const int nwb = a.W / 16;
+    const bool need_prev = a.is_bwd && (a.act_prev || a.g_wskip || a.gslab);
+    DLWP_SPAN_BEGIN();
+    DLWP_STAMP(0);
+    SpatialLoads R;
+    spatial_issue<MODE>(a, b, h, need_prev, R);
+    // running partials of this workgroup's gradient slab (read-modify-write across net calls): fetched here, with every
+    // other input, instead of in front of the final store (a dependent global round trip at the very end of the kernel)
+    constexpr int SLQ = 4;
+    float slab_old[SLQ], slab_b_old = 0.f;
+#pragma unroll
+    for (int k = 0; k < SLQ; ++k) slab_old[k] = 0.f;
+    const long long slab_off = spatial_slab_off(a);
+    const bool slab_acc = a.is_bwd && a.gslab && a.gslab_accumulate;
+    if (slab_acc) {
+#pragma unroll
+        for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tid + 256 * k, a.C * a.C - 1)];
+        slab_b_old = a.gslab[slab_off + a.C * a.C + min(tid, a.C - 1)];
+    }
+    DLWP_STAMP(1);
+    spatial_commit<MODE>(a, L, b, h, need_prev, R);
+    DLWP_STAMP(3);
+    spatial_hstep(a, L, b, h, R);
+    DLWP_STAMP(4);
+    __syncthreads();   // 1: tin_s, pprev_s, gs, ks, s1 complete
+    DLWP_STAMP(5);
+    spatial_gemm<NCB, NBN, MODE>(a, L, w);
+    DLWP_STAMP(6);
+    __syncthreads();   // 2: tout_s complete; gs / ks / s1 dead
+    DLWP_STAMP(7);
+    spatial_out_dft<NCB, NBN>(a, L, b, h);
     DLWP_STAMP(9);
 
+    // by-products, behind the chain on the same four waves: from LDS, the partial tiles over the dead GEMM operands
     if (a.is_bwd && (a.g_wskip || a.gslab)) {
         // gK[o][i] += sum_w g_pre[o][w] * act(x)[i][w]
         f32x4 kacc[NCB][NCB];
@@ -288,13 +375,13 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
         for (int kc = w; kc < nwb; kc += 4) {
 #pragma unroll
             for (int ib = 0; ib < NCB; ++ib) {
-                f32x4 b4 = *reinterpret_cast<const f32x4*>(&pprev_s[(ib * 16 + r) * LDP + kc * 16 + 4 * g]);
+                f32x4 b4 = *reinterpret_cast<const f32x4*>(&L.pprev_s[(ib * 16 + r) * L.LDP + kc * 16 + 4 * g]);
                 if (a.act_prev) {
                     b4 = gelu4(b4);
                 }
 #pragma unroll
                 for (int ob = 0; ob < NCB; ++ob) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&tin_s[(ob * 16 + r) * LDP + kc * 16 + 4 * g]);
+                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&L.tin_s[(ob * 16 + r) * L.LDP + kc * 16 + 4 * g]);
                     kacc[ob][ib] = mfma16_chunk(a4, b4, kacc[ob][ib]);
                 }
             }
@@ -305,87 +392,42 @@ __global__ __launch_bounds__(256) void fno_spatial_kernel(SpatialDev a) {
             for (int ib = 0; ib < NCB; ++ib)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    gks[((w * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
+                    L.gks[((w * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
     }
     DLWP_STAMP(10);
-    __syncthreads();
+    __syncthreads();   // 3: x1s and the gK partials complete
     DLWP_STAMP(11);
-    if (a.x1_out) store_x1(x1s, a.x1_out, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
+    if (a.x1_out) store_x1<SPATIAL_NT>(L.x1s, a.x1_out, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
     if (a.is_bwd && (a.g_wskip || a.gslab)) {
         int kq = 0;
         for (int idx = tid; idx < a.C * a.C; idx += 256, ++kq) {
             const int o = fastdiv(idx, a.dC), i = idx - o * a.C;
             float v = 0.f;
 #pragma unroll
-            for (int w2 = 0; w2 < 4; ++w2) v += gks[(w2 * a.C_pad + o) * a.C_pad + i];
-            if (a.gslab) {
-                float* sl = a.gslab + slab_off + idx;
-                float old = 0.f;
-                if (a.gslab_accumulate) {
-                    old = kq == 0 ? slab_old[0] : kq == 1 ? slab_old[1] : kq == 2 ? slab_old[2] : kq == 3 ? slab_old[3] : *sl;
-                }
-                *sl = old + v;
-            } else {
-                atomic_add_f32(&a.g_wskip[idx], v);   // all workgroups hit the same C*C words: slow, API path only
+            for (int w2 = 0; w2 < 4; ++w2) v += L.gks[(w2 * a.C_pad + o) * a.C_pad + i];
+            float old = 0.f;
+            if (slab_acc) {
+                old = kq == 0 ? slab_old[0] : kq == 1 ? slab_old[1] : kq == 2 ? slab_old[2] : kq == 3 ? slab_old[3]
+                                                                                                        : a.gslab[slab_off + idx];
             }
+            spatial_flush(a, slab_off + idx, &a.g_wskip[idx], old, v);
         }
     }
     if (a.is_bwd && (a.g_bias || a.gslab) && tid < a.C) {
         float s = 0.f;
-        for (int x = 0; x < a.W; ++x) s += tin_s[tid * LDP + x];
-        if (a.gslab) {
-            a.gslab[slab_off + a.C * a.C + tid] = (a.gslab_accumulate ? slab_b_old : 0.f) + s;
-        } else {
-            atomic_add_f32(&a.g_bias[tid], s);
-        }
+        for (int x = 0; x < a.W; ++x) s += L.tin_s[tid * L.LDP + x];
+        spatial_flush(a, slab_off + a.C * a.C + tid, &a.g_bias[tid], slab_b_old, s);
     }
     DLWP_STAMP(12);
     DLWP_SPAN_END();
-}
-
-// The staging helpers of common.hip.h and store_x1 stride by blockDim.x.  Role A of the two-role kernel below is the first NT
-// threads of a larger workgroup: the same loops with the stride spelled out (same elements per thread, same order of additions).
-template <int NT, bool TR>
-__device__ __forceinline__ void stage_matrix_tail_nt(float* dst, int ld, const float* __restrict__ src, int rows, int cols,
-                                                     FastDiv dcols, int done4) {
-    const int n = rows * cols;
-#pragma unroll 4
-    for (int e = 4 * done4 + threadIdx.x; e < n; e += NT) {
-        const int rr = fastdiv(e, dcols);
-        const int cc = e - rr * cols;
-        dst[TR ? cc * ld + rr : rr * ld + cc] = src[e];
-    }
-}
-template <int NT>
-__device__ __forceinline__ void zero_padding_nt(float* dst, int ld, int rows, int cols, int rows_pad, int cols_pad) {
-    if (cols_pad > cols)
-        for (int rr = threadIdx.x; rr < rows; rr += NT)
-            for (int cc = cols; cc < cols_pad; ++cc) dst[rr * ld + cc] = 0.f;
-    for (int rr = rows; rr < rows_pad; ++rr)
-        for (int cc = threadIdx.x; cc < cols_pad; cc += NT) dst[rr * ld + cc] = 0.f;
-}
-template <int NT>
-__device__ __forceinline__ void store_x1_nt(const float* x1s, float2* x1_out, int b, int h, int H, int m2c, int C, int C_pad,
-                                            int NP) {
-    float2* dst = x1_out + ((long long)(b * H + h) * m2c) * C;
-    for (int idx = threadIdx.x; idx < m2c * C; idx += NT) {
-        const int kx = idx / C, c = idx % C;
-        float re = 0.f, im = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            re += x1s[(w * C_pad + c) * NP + 2 * kx];
-            im += x1s[(w * C_pad + c) * NP + 2 * kx + 1];
-        }
-        dst[idx] = make_float2(re, im);
-    }
 }
 
 // Backward `spatial` (MODE 1 / 2 with a gradient destination) as TWO ROLES in one workgroup of eight waves.  The by-products of
 // the backward pass -- skip-weight gradient, bias gradient -- feed neither `out` nor `x1_out` and depend only on tin_s / pprev_s,
 // which are complete at the first barrier; in fno_spatial_kernel they run behind the row DFT on the same four waves (one wave per
 // SIMD, nothing to hide a wait behind) and the next launch of the chain waits for them.  Here
-//   role A, waves 0-3: the chain.  Exactly fno_spatial_kernel up to store_x1: same thread-to-element mapping (every stride is 256),
-//           same arithmetic, same three barriers.
+//   role A, waves 0-3: the chain.  The phase functions fno_spatial_kernel calls, in the same order between the same three
+//           barriers: same mapping and same arithmetic by construction (need_prev is always true here, and there is no bias).
 //   role B, waves 4-7: the by-products.  While role A stages (up to barrier 1, where the SIMDs mostly wait for global memory):
 //           the old slab values, and the four per-wave partial tiles of gK -- its MFMA fragments are 16 contiguous bytes of a row
 //           of `tin` / `pprev`, so they are read straight from global memory -- into an LDS region of their own (gks cannot alias
@@ -394,25 +436,15 @@ __device__ __forceinline__ void store_x1_nt(const float* x1s, float2* x1_out, in
 // All eight waves meet at the same three barriers, on every path: each is at the top level of the kernel.  Role A's count is that
 // of fno_spatial_kernel.  (Measured, profiles/r08_experiments.md: with role B's GEMM next to the main GEMM both slow down -- MFMA
 // and VALU of one SIMD do not overlap -- and a dependent chain of additions next to MFMAs waits for one MFMA per addition.)
-// Results are bit for bit those of fno_spatial_kernel: partial w2 is one mfma16_chunk chain from zero over the chunks kc = w2,
-// w2 + 4, ... of the same values; the partials are summed w2 = 0 .. 3 from 0.f, then old + v; the bias gradient is the sequential
-// sum over x = 0 .. W-1 from 0.f (16-byte LDS reads), then old + s.
+// The by-products are bit for bit those of fno_spatial_kernel: partial w2 is one mfma16_chunk chain from zero over the chunks
+// kc = w2, w2 + 4, ... of the same values; the partials are summed w2 = 0 .. 3 from 0.f, then old + v; the bias gradient is the
+// sequential sum over x = 0 .. W-1 from 0.f (16-byte LDS reads), then old + s.
 template <int NCB, int NBN, int MODE>
 __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
     static_assert(MODE == 1 || MODE == 2, "backward modes only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int NTA = 256;                      // threads of role A (and of role B)
-    const int LDP = a.W + 4, LDK = a.C_pad + 4, LDS1 = a.NP + 4;
-    float* tin_s = smem;                          // [C_pad][LDP]
-    float* tout_s = tin_s + a.C_pad * LDP;        // [C_pad][LDP]
-    float* pprev_s = tout_s + a.C_pad * LDP;      // [C_pad][LDP]
-    float* ft = pprev_s + a.C_pad * LDP;          // [NP][LDP]
-    float* x1s = ft + a.NP * LDP;                 // [4 waves][C_pad][NP]
-    float* gs = x1s + 4 * a.C_pad * a.NP;         // [NP][LDP]
-    float* ks = gs + a.NP * LDP;                  // [C_pad][LDK]
-    float* s1 = ks + a.C_pad * LDK;               // [C_pad][LDS1]
-    float* gks = s1 + a.C_pad * LDS1;             // [4 waves][C_pad][C_pad]   role B's own
-
+    constexpr int NTA = SPATIAL_NT;               // threads of role A (and of role B)
+    const SpatialLds L = carve_spatial_lds<true>(smem, a);
     const int tid = threadIdx.x, lane = lane_id();
     const int w = __builtin_amdgcn_readfirstlane(wave_id());   // wave-uniform: the role branches are scalar branches
     const bool role_a = w < 4;
@@ -420,53 +452,23 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
     const int r = lane & 15, g = lane >> 4;
     const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
     const int W4 = a.W / 4, nwb = a.W / 16;
-    const int tile_units = a.C_pad * W4, tab_units = a.NP * W4;
     DLWP_SPAN_BEGIN();
     DLWP_STAMP(0);
-    // ---- issue phase (role A: as fno_spatial_kernel; role B: the running partials of this workgroup's gradient slab)
-    float4 tv[2], pv[2];
-    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), fv = gv;
-    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);   // wskip: one 16-byte unit per role-A thread, the rest in the tail loop
-    int nk = 0;
-    constexpr int MJ = 16;
-    float2 sv[MJ];
-    float2 twl = make_float2(0.f, 0.f);
-    const long long jstride = (long long)a.m2c * a.C;
+    // ---- issue phase (role A: the chain's; role B: the running partials of this workgroup's gradient slab)
+    SpatialLoads R;
     constexpr int SLQ = 4;
     float slab_old[SLQ], slab_b_old = 0.f;
 #pragma unroll
     for (int k = 0; k < SLQ; ++k) slab_old[k] = 0.f;
-    const long long slab_off = (long long)blockIdx.x * (((long long)a.C * a.C + a.C + 3) & ~3LL);
+    const long long slab_off = spatial_slab_off(a);
+    const bool slab_acc = a.gslab && a.gslab_accumulate;
     const int bias_c = 4 * lane + w2;             // role B: bias-gradient channel of this lane (lanes 0-15 of each wave)
     constexpr int BQ = 16;                        // ... its row pieces read ahead (a whole row at W = 64)
     const bool bias_on = !role_a && (a.g_bias || a.gslab) && lane < 16 && bias_c < a.C;
     if (role_a) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int u = tid + NTA * k, c = u / W4, x4 = u - c * W4;
-            tv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            pv[k] = tv[k];
-            if (u < tile_units && c < a.C) {
-                const long long off = (((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4;
-                tv[k] = *reinterpret_cast<const float4*>(&a.tin[off]);
-                pv[k] = *reinterpret_cast<const float4*>(&a.pprev[off]);
-            }
-        }
-        if (tid < tab_units) {
-            gv = reinterpret_cast<const float4*>(a.G)[tid];
-            if (a.x1_out) fv = reinterpret_cast<const float4*>(a.FT)[tid];
-        }
-        nk = a.vec_w ? min((a.C * a.C) >> 2, NTA) : 0;
-        if (tid < nk) kv = reinterpret_cast<const float4*>(a.wskip)[tid];
-        const int d_kx = tid / a.C_pad, d_o = tid - d_kx * a.C_pad;
-        const bool d_valid = tid < a.C_pad * (a.NP / 2) && d_kx < a.m2c && d_o < a.C;
-        const float2* sp = a.spec + (((long long)b * a.m1) * a.m2c + (d_valid ? d_kx : 0)) * a.C + (d_valid ? d_o : 0);
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) sv[j] = sp[(j < a.m1 ? j : a.m1 - 1) * jstride];
-        const int twj = (lane & 15) < a.m1 ? (lane & 15) : a.m1 - 1;
-        twl = a.twH[twj * a.H + h];
+        spatial_issue<MODE>(a, b, h, true, R);
     } else {
-        if (a.gslab && a.gslab_accumulate) {
+        if (slab_acc) {
 #pragma unroll
             for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tb + NTA * k, a.C * a.C - 1)];
             slab_b_old = a.gslab[slab_off + a.C * a.C + min(bias_c, a.C - 1)];
@@ -511,145 +513,29 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
             for (int ib = 0; ib < NCB; ++ib)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    gks[((w2 * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
+                    L.gks[((w2 * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
         DLWP_STAMP_IF(blockIdx.x == 0 && tb == 0, 13);
     }
     DLWP_STAMP(1);
 
-    // ---- commit phase (role A)
     if (role_a) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int u = tid + NTA * k, c = u / W4, x4 = u - c * W4;
-            if (u < tile_units) {
-                float4 v = tv[k];
-                if (a.act_tin) { const f32x4 ga = gelu4(f32x4{v.x, v.y, v.z, v.w}); v = make_float4(ga[0], ga[1], ga[2], ga[3]); }
-                *reinterpret_cast<float4*>(&tin_s[c * LDP + 4 * x4]) = v;
-                *reinterpret_cast<float4*>(&pprev_s[c * LDP + 4 * x4]) = pv[k];
-            }
-        }
-        for (int idx = tid + 2 * NTA; idx < tile_units; idx += NTA) {
-            const int c = idx / W4, x4 = idx % W4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f), pvv = v;
-            if (c < a.C) {
-                const long long off = (((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4;
-                v = *reinterpret_cast<const float4*>(&a.tin[off]);
-                if (a.act_tin) { const f32x4 ga = gelu4(f32x4{v.x, v.y, v.z, v.w}); v = make_float4(ga[0], ga[1], ga[2], ga[3]); }
-                pvv = *reinterpret_cast<const float4*>(&a.pprev[off]);
-            }
-            *reinterpret_cast<float4*>(&tin_s[c * LDP + 4 * x4]) = v;
-            *reinterpret_cast<float4*>(&pprev_s[c * LDP + 4 * x4]) = pvv;
-        }
-        DLWP_STAMP(2);
-        if (tid < tab_units) {
-            const int n = tid / W4, x4 = tid - n * W4;
-            *reinterpret_cast<float4*>(&gs[n * LDP + 4 * x4]) = gv;
-            if (a.x1_out) *reinterpret_cast<float4*>(&ft[n * LDP + 4 * x4]) = fv;
-        }
-        for (int idx = tid + NTA; idx < tab_units; idx += NTA) {
-            const int n = idx / W4, x4 = idx % W4;
-            *reinterpret_cast<float4*>(&gs[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.G[n * a.W + 4 * x4]);
-            if (a.x1_out)
-                *reinterpret_cast<float4*>(&ft[n * LDP + 4 * x4]) = *reinterpret_cast<const float4*>(&a.FT[n * a.W + 4 * x4]);
-        }
-        if (tid < nk) {
-            const float vv[4] = {kv.x, kv.y, kv.z, kv.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e = 4 * tid + q, rr = fastdiv(e, a.dC), cc = e - rr * a.C;
-                ks[a.transpose_w ? cc * LDK + rr : rr * LDK + cc] = vv[q];
-            }
-        }
-        if (a.transpose_w) stage_matrix_tail_nt<NTA, true>(ks, LDK, a.wskip, a.C, a.C, a.dC, nk);
-        else stage_matrix_tail_nt<NTA, false>(ks, LDK, a.wskip, a.C, a.C, a.dC, nk);
-        zero_padding_nt<NTA>(ks, LDK, a.C, a.C, a.C_pad, a.C_pad);
+        spatial_commit<MODE>(a, L, b, h, true, R);
         DLWP_STAMP(3);
-        // inverse H-axis step for this row: s1[o][2kx(+1)] = sum_j spec[b][j][kx][o] * conj(twH[j][h])
-        float twx[MJ], twy[MJ];
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) { twx[j] = __shfl(twl.x, j, 16); twy[j] = __shfl(twl.y, j, 16); }
-        for (int idx = tid; idx < a.C_pad * (a.NP / 2); idx += NTA) {
-            const int kx = idx / a.C_pad, o = idx - kx * a.C_pad;
-            float re = 0.f, im = 0.f;
-            if (idx == tid) {   // first chunk: operands already in registers
-#pragma unroll
-                for (int j = 0; j < MJ; ++j) {
-                    if (j < a.m1) {
-                        re += sv[j].x * twx[j] + sv[j].y * twy[j];   // v * conj(t)
-                        im += sv[j].y * twx[j] - sv[j].x * twy[j];
-                    }
-                }
-            }
-            if (kx < a.m2c && o < a.C) {
-                const float2* sp2 = a.spec + (((long long)b * a.m1) * a.m2c + kx) * a.C + o;
-                for (int j = (idx == tid ? MJ : 0); j < a.m1; ++j) {
-                    const float2 v = sp2[j * jstride];
-                    const float2 t = a.twH[j * a.H + h];
-                    re += v.x * t.x + v.y * t.y;
-                    im += v.y * t.x - v.x * t.y;
-                }
-            }
-            const bool ok = kx < a.m2c && o < a.C;
-            s1[o * LDS1 + 2 * kx] = ok ? re : 0.f;
-            s1[o * LDS1 + 2 * kx + 1] = ok ? im : 0.f;
-        }
+        spatial_hstep(a, L, b, h, R);
         DLWP_STAMP(4);
     }
     __syncthreads();   // 1: tin_s, pprev_s, gs, ks, s1 complete (role A); the four gK partials complete (role B)
     DLWP_STAMP(5);
 
     if (role_a) {
-        // main concatenated-K GEMM: acc[o][w] = sum_i ks[o][i] tin[i][w] + sum_n s1[o][n] gs[n][w]
-        for (int wb = w; wb < nwb; wb += 4) {
-            f32x4 acc[NCB];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kc = 0; kc < NCB; ++kc) {
-                f32x4 b4;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) b4[s] = tin_s[(kc * 16 + 4 * g + s) * LDP + wb * 16 + r];
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&ks[(cb * 16 + r) * LDK + kc * 16 + 4 * g]);
-                    acc[cb] = mfma16_chunk(a4, b4, acc[cb]);
-                }
-            }
-#pragma unroll
-            for (int nc = 0; nc < NBN; ++nc) {
-                f32x4 b4;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) b4[s] = gs[(nc * 16 + 4 * g + s) * LDP + wb * 16 + r];
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&s1[(cb * 16 + r) * LDS1 + nc * 16 + 4 * g]);
-                    acc[cb] = mfma16_chunk(a4, b4, acc[cb]);
-                }
-            }
-            float ep[NCB][4];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int o = cb * 16 + 4 * g + j, x = wb * 16 + r;
-                    ep[cb][j] = MODE == 1 ? pprev_s[o * LDP + x] : 0.f;
-                }
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                f32x4 v4 = acc[cb];
-                const f32x4 e4 = f32x4{ep[cb][0], ep[cb][1], ep[cb][2], ep[cb][3]};
-                if (MODE == 1) v4 *= gelu_grad4(e4);              // packed fp32 polynomial
-#pragma unroll
-                for (int j = 0; j < 4; ++j) tout_s[(cb * 16 + 4 * g + j) * LDP + wb * 16 + r] = v4[j];
-            }
-        }
+        spatial_gemm<NCB, NBN, MODE>(a, L, w);
         DLWP_STAMP(6);
     } else {
         // cross-wave sum of the gK partials (w2 = 0 .. 3 from 0.f), then old + v into the slab, or the atomics.  The first SLQ
         // elements of a thread: all LDS reads first, then the sums (a read-then-use loop pays the LDS latency per element)
         // Bias gradient: channel 4 lane + w2 on lanes 0-15 of every wave, its row of tin_s as 16-byte reads (the first BQ issued
         // here, in front of the sums), additions in the order x = 0 .. W-1 from 0.f.
-        const float4* brow = reinterpret_cast<const float4*>(&tin_s[min(bias_c, a.C_pad - 1) * LDP]);
+        const float4* brow = reinterpret_cast<const float4*>(&L.tin_s[min(bias_c, a.C_pad - 1) * L.LDP]);
         float4 bq[BQ];
         if (bias_on) {
 #pragma unroll
@@ -660,7 +546,7 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
         for (int k = 0; k < SLQ; ++k) {
             const int idx = min(tb + NTA * k, a.C * a.C - 1), o = fastdiv(idx, a.dC), i = idx - o * a.C;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) pq[k][q] = gks[(q * a.C_pad + o) * a.C_pad + i];
+            for (int q = 0; q < 4; ++q) pq[k][q] = L.gks[(q * a.C_pad + o) * a.C_pad + i];
         }
 #pragma unroll
         for (int k = 0; k < SLQ; ++k) {
@@ -668,22 +554,14 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
             float v = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) v += pq[k][q];
-            if (idx < a.C * a.C) {
-                if (a.gslab) a.gslab[slab_off + idx] = (a.gslab_accumulate ? slab_old[k] : 0.f) + v;
-                else atomic_add_f32(&a.g_wskip[idx], v);   // all workgroups hit the same C*C words: slow, API path only
-            }
+            if (idx < a.C * a.C) spatial_flush(a, slab_off + idx, &a.g_wskip[idx], slab_old[k], v);
         }
         for (int idx = tb + NTA * SLQ; idx < a.C * a.C; idx += NTA) {
             const int o = fastdiv(idx, a.dC), i = idx - o * a.C;
             float v = 0.f;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v += gks[(q * a.C_pad + o) * a.C_pad + i];
-            if (a.gslab) {
-                float* sl = a.gslab + slab_off + idx;
-                *sl = (a.gslab_accumulate ? *sl : 0.f) + v;
-            } else {
-                atomic_add_f32(&a.g_wskip[idx], v);
-            }
+            for (int q = 0; q < 4; ++q) v += L.gks[(q * a.C_pad + o) * a.C_pad + i];
+            spatial_flush(a, slab_off + idx, &a.g_wskip[idx], slab_acc ? a.gslab[slab_off + idx] : 0.f, v);
         }
         if (bias_on) {
             float bias_sum = 0.f;
@@ -694,8 +572,7 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
                 const float4 v = brow[x4];
                 bias_sum += v.x; bias_sum += v.y; bias_sum += v.z; bias_sum += v.w;
             }
-            if (a.gslab) a.gslab[slab_off + a.C * a.C + bias_c] = (a.gslab_accumulate ? slab_b_old : 0.f) + bias_sum;
-            else atomic_add_f32(&a.g_bias[bias_c], bias_sum);
+            spatial_flush(a, slab_off + a.C * a.C + bias_c, &a.g_bias[bias_c], slab_b_old, bias_sum);
         }
         DLWP_STAMP_IF(blockIdx.x == 0 && tb == 0, 15);
     }
@@ -705,19 +582,13 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
     DLWP_STAMP(7);
 
     if (role_a) {
-        for (int idx = tid; idx < a.C * W4; idx += NTA) {
-            const int c = idx / W4, x4 = idx % W4;
-            *reinterpret_cast<float4*>(&a.out[(((long long)b * a.C + c) * a.H + h) * a.W + 4 * x4]) =
-                *reinterpret_cast<const float4*>(&tout_s[c * LDP + 4 * x4]);
-        }
-        DLWP_STAMP(8);
-        if (a.x1_out) tile_rows_dft<NCB, NBN>(tout_s, ft, x1s, LDP, a.NP, nwb, a.x1_act != 0);
+        spatial_out_dft<NCB, NBN>(a, L, b, h);
         DLWP_STAMP(9);
     }
     // 3: x1s complete
     if (role_a) __syncthreads(); else __builtin_amdgcn_s_barrier();
     DLWP_STAMP(11);
-    if (role_a && a.x1_out) store_x1_nt<NTA>(x1s, a.x1_out, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
+    if (role_a && a.x1_out) store_x1<NTA>(L.x1s, a.x1_out, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
     DLWP_STAMP(12);
     DLWP_STAMP_WAVE(24);
     DLWP_SPAN_END();

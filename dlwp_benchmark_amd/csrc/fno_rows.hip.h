@@ -38,10 +38,12 @@ __device__ __forceinline__ void tile_rows_dft(const float* tile, const float* ft
                 x1s[((w * NCB + cb) * 16 + 4 * g + j) * NP + nb * 16 + r] = xacc[cb][nb][j];
 }
 
+// NT: see wg_stride (common.hip.h)
+template <int NT = 0>
 __device__ __forceinline__ void store_x1(const float* x1s, float2* x1_out, int b, int h, int H, int m2c,
                                          int C, int C_pad, int NP) {
     float2* dst = x1_out + ((long long)(b * H + h) * m2c) * C;
-    for (int idx = threadIdx.x; idx < m2c * C; idx += blockDim.x) {
+    for (int idx = threadIdx.x; idx < m2c * C; idx += wg_stride<NT>()) {
         const int kx = idx / C, c = idx % C;
         float re = 0.f, im = 0.f;
 #pragma unroll
