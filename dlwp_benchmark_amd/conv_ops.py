@@ -1,4 +1,5 @@
-"""3 x 3 convolutions and the ConvLSTM cell over libdlwpmi (csrc/conv3x3.hip; include/dlwpmi.h dlwp_conv3x3_* / dlwp_convlstm_*).
+"""3 x 3 convolutions and the ConvLSTM cell over libdlwpmi (csrc/conv3x3.hip; include/dlwpmi.h dlwp_conv3x3_* / dlwp_convlstm_*),
+and the other U-Net layers (csrc/unet_ops.hip): 2 x 2 average pool, 2 x 2 stride-2 up-convolution, 1 x 1 convolution.
 
 Activations are channels-last fp32 `[B, H, W, C]`.  The padding is a pair of per-axis modes (height, width), each "zeros" or
 "circular"; it is resolved inside the kernels, so neither a padded tensor nor `cat(x, h_prev)` is ever written.  The weight
@@ -230,6 +231,156 @@ class Conv3x3(nn.Conv2d):
 
     def forward_cl(self, x, x2=None, packed=None):
         return conv3x3(x, self.weight, self.bias, self.pad_modes, self.act, x2=x2, packed=packed)
+
+    def forward(self, x):
+        return self.forward_cl(x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+
+
+# ---- the U-Net layers that are not 3 x 3 convolutions (csrc/unet_ops.hip)
+class _AvgPool2x2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _cl(x, "avg_pool2x2")
+        if x.dim() != 4:
+            raise L.DlwpError(f"avg_pool2x2: a [B, H, W, C] tensor is needed, not {tuple(x.shape)}")
+        B, H, W, C = x.shape
+        y = torch.empty(B, H // 2, W // 2, C, device=x.device)
+        L.check(L.load().dlwp_avgpool2x2_fwd(L.ptr(x), L.ptr(y), B, H, W, C, L.stream()))
+        ctx.shape = (B, H, W, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        B, H, W, C = ctx.shape
+        gy = _cl(gy, "avg_pool2x2 backward")
+        gx = torch.empty(B, H, W, C, device=gy.device)
+        L.check(L.load().dlwp_avgpool2x2_bwd(L.ptr(gy), L.ptr(gx), B, H, W, C, L.stream()))
+        return gx
+
+
+def avg_pool2x2(x):
+    """`avg_pool2d(x, 2, 2)` on a channels-last `[B, H, W, C]` tensor (H and W even) -> `[B, H/2, W/2, C]`."""
+    return _AvgPool2x2Fn.apply(x)
+
+
+def _pixel_weight_grad(up, x, dy, weight_shape, wslot, bslot, has_bias):
+    """gW, gb of a 1 x 1 convolution or (up) a 2 x 2 up-convolution: straight into the gradient slots where they exist
+    (returns None for those)."""
+    lib = L.load()
+    B, H, W, cin = x.shape
+    cout = weight_shape[1] if up else weight_shape[0]
+    gw = wslot if wslot is not None else torch.zeros(weight_shape, device=dy.device)
+    gb = None
+    if has_bias:
+        gb = bslot if bslot is not None else torch.zeros(cout, device=dy.device)
+    n = lib.dlwp_upconv2x2_wgrad_ws_floats(B, H, W, cin, cout) if up else lib.dlwp_conv1x1_wgrad_ws_floats(B * H * W, cin, cout)
+    if n < 0:
+        L.check(int(n))
+    ws = torch.empty(n, device=dy.device)
+    if up:
+        L.check(lib.dlwp_upconv2x2_wgrad(L.ptr(x), L.ptr(dy), L.ptr(ws), L.ptr(gw), L.ptr(gb), B, H, W, cin, cout, L.stream()))
+    else:
+        L.check(lib.dlwp_conv1x1_wgrad(L.ptr(x), L.ptr(dy), L.ptr(ws), L.ptr(gw), L.ptr(gb), B * H * W, cin, cout, L.stream()))
+    return (None if wslot is not None else gw), (None if (bslot is not None or not has_bias) else gb)
+
+
+class _PixelConvFn(torch.autograd.Function):
+    """up = False: the 1 x 1 convolution; up = True: the 2 x 2 stride-2 transposed convolution (one kernel family)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, up):
+        lib = L.load()
+        what = "upconv2x2" if up else "conv1x1"
+        x = _cl(x, what)
+        w = _cl(weight.detach(), what)
+        if x.dim() != 4 or weight.shape[0 if up else 1] != x.shape[-1]:
+            raise L.DlwpError(f"{what}: weight {tuple(weight.shape)} does not fit an input of shape {tuple(x.shape)}")
+        B, H, W, cin = x.shape
+        if up:
+            cout = weight.shape[1]
+            y = torch.empty(B, 2 * H, 2 * W, cout, device=x.device)
+            L.check(lib.dlwp_upconv2x2_fwd(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), B, H, W, cin, cout, L.stream()))
+        else:
+            cout = weight.shape[0]
+            y = torch.empty(B, H, W, cout, device=x.device)
+            L.check(lib.dlwp_conv1x1_fwd(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), B * H * W, cin, cout, L.stream()))
+        ctx.save_for_backward(x, w)
+        ctx.up, ctx.cout, ctx.wshape, ctx.has_bias = up, cout, weight.shape, bias is not None
+        ctx.wslot = _grad_slot(weight)
+        ctx.bslot = _grad_slot(bias) if bias is not None else None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = L.load()
+        x, w = ctx.saved_tensors
+        B, H, W, cin = x.shape
+        gy = _cl(gy, "upconv2x2 backward" if ctx.up else "conv1x1 backward")
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            if ctx.up:
+                L.check(lib.dlwp_upconv2x2_dgrad(L.ptr(gy), L.ptr(w), L.ptr(gx), B, H, W, cin, ctx.cout, L.stream()))
+            else:
+                L.check(lib.dlwp_conv1x1_dgrad(L.ptr(gy), L.ptr(w), L.ptr(gx), B * H * W, cin, ctx.cout, L.stream()))
+        gw = gb = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = _pixel_weight_grad(ctx.up, x, gy, ctx.wshape, ctx.wslot, ctx.bslot, ctx.has_bias)
+        return gx, gw, gb, None
+
+
+def upconv2x2(x, weight, bias=None):
+    """`conv_transpose2d(x, weight, bias, stride=2)` with a `[Cin, Cout, 2, 2]` weight on a channels-last `[B, H, W, Cin]`
+    tensor -> `[B, 2H, 2W, Cout]`.  The kernels read the parameter's own layout: nothing is packed."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (2, 2):
+        raise ValueError(f"a [Cin, Cout, 2, 2] weight is needed, not {tuple(weight.shape)}")
+    return _PixelConvFn.apply(x, weight, bias, True)
+
+
+def conv1x1(x, weight, bias=None):
+    """`conv2d(x, weight, bias)` with a `[Cout, Cin, 1, 1]` weight on a channels-last `[B, H, W, Cin]` tensor."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1):
+        raise ValueError(f"a [Cout, Cin, 1, 1] weight is needed, not {tuple(weight.shape)}")
+    return _PixelConvFn.apply(x, weight, bias, False)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+class UpConv2x2(nn.ConvTranspose2d):
+    """`nn.ConvTranspose2d(cin, cout, kernel_size=2, stride=2)` on the hand-written kernel; parameter names and shapes are
+    torch's.  `forward` is channels-first like the torch layer (two permute copies), `forward_cl` channels-last."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, bias=True, **kw):
+        if _pair(kernel_size) != (2, 2) or _pair(stride) != (2, 2):
+            raise ValueError("UpConv2x2: kernel_size 2 and stride 2 only")
+        super().__init__(in_channels, out_channels, 2, stride=2, bias=bias, **kw)
+        if (tuple(self.padding) != (0, 0) or tuple(self.output_padding) != (0, 0) or tuple(self.dilation) != (1, 1) or self.groups != 1
+                or self.padding_mode != "zeros"):
+            raise ValueError("UpConv2x2: padding 0, output_padding 0, dilation 1, groups 1 only")
+
+    def forward_cl(self, x):
+        return upconv2x2(x, self.weight, self.bias)
+
+    def forward(self, x, output_size=None):
+        if output_size is not None:
+            raise ValueError("UpConv2x2: the output size is always twice the input size")
+        return self.forward_cl(x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+
+
+class Conv1x1(nn.Conv2d):
+    """`nn.Conv2d(cin, cout, kernel_size=1)` on the hand-written kernel; parameter names and shapes are torch's."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=1, bias=True, **kw):
+        if _pair(kernel_size) != (1, 1):
+            raise ValueError("Conv1x1: kernel_size 1 only")
+        super().__init__(in_channels, out_channels, 1, bias=bias, **kw)
+        if (tuple(self.stride) != (1, 1) or self.padding not in (0, (0, 0)) or tuple(self.dilation) != (1, 1) or self.groups != 1):
+            raise ValueError("Conv1x1: stride 1, padding 0, dilation 1, groups 1 only")
+
+    def forward_cl(self, x):
+        return conv1x1(x, self.weight, self.bias)
 
     def forward(self, x):
         return self.forward_cl(x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)

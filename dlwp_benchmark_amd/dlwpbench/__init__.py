@@ -5,6 +5,7 @@ from .fourcastnet import AFNONet, FourCastNet, FourCastNetv2, SFNONet  # noqa: F
 from .panguweather import PanguWeather  # noqa: F401
 from .sfno import SFNO2DModule  # noqa: F401
 from .swin_transformer import SwinTransformer  # noqa: F401
+from .unet import UNet, UNetHPX  # noqa: F401
 
 __all__ = ["FNO2DModule", "TFNO2DModule", "SFNO2DModule", "AFNONet", "FourCastNet", "FourCastNetv2", "SFNONet", "PanguWeather",
-           "SwinTransformer", "ConvLSTM"]
+           "SwinTransformer", "ConvLSTM", "UNet", "UNetHPX"]

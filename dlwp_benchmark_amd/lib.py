@@ -198,6 +198,16 @@ SIGNATURES = {
     "dlwp_conv3x3_act_bwd": (_I, [_V, _V, _V, _L, _I, _V]),
     "dlwp_conv3x3_wgrad_ws_floats": (_L, [_I] * 5),
     "dlwp_conv3x3_wgrad": (_I, [_V] * 6 + [_I] * 8 + [_V]),
+    "dlwp_avgpool2x2_fwd": (_I, [_V, _V] + [_I] * 4 + [_V]),
+    "dlwp_avgpool2x2_bwd": (_I, [_V, _V] + [_I] * 4 + [_V]),
+    "dlwp_conv1x1_fwd": (_I, [_V] * 4 + [_L, _I, _I, _V]),
+    "dlwp_conv1x1_dgrad": (_I, [_V] * 3 + [_L, _I, _I, _V]),
+    "dlwp_upconv2x2_fwd": (_I, [_V] * 4 + [_I] * 5 + [_V]),
+    "dlwp_upconv2x2_dgrad": (_I, [_V] * 3 + [_I] * 5 + [_V]),
+    "dlwp_conv1x1_wgrad_ws_floats": (_L, [_L, _I, _I]),
+    "dlwp_conv1x1_wgrad": (_I, [_V] * 5 + [_L, _I, _I, _V]),
+    "dlwp_upconv2x2_wgrad_ws_floats": (_L, [_I] * 5),
+    "dlwp_upconv2x2_wgrad": (_I, [_V] * 5 + [_I] * 5 + [_V]),
     "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),
     "dlwp_debug_null_kernels": (_I, [_I, _I, _V]),
     "dlwp_debug_spin_kernels": (_I, [_I, _I, _I, _I, _I, _V]),

@@ -999,6 +999,38 @@ long long dlwp_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout);
 int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float* dz, float* ws, float* gw, float* gb, int B,
                        int H, int W, int C1, int C2, int Cout, int pad_h, int pad_w, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* The U-Net layers that are not 3 x 3 convolutions (csrc/unet_ops.hip): AvgPool2d(2, 2), ConvTranspose2d(2, 2)  */
+/* and the 1 x 1 output convolution of src/{nsbench,dlwpbench}/models/unet/unet.py.  Channels-last fp32           */
+/* [B][H][W][C] like the 3 x 3 kernels; the products run on the exact-fp32 MFMA.  No atomics anywhere: repeated   */
+/* launches on the same operands are bit-identical.                                                              */
+/*                                                                                                               */
+/* y [B][H/2][W/2][C] = 0.25 * (((a + b) + c) + d) over the 2 x 2 block (row-major order); H, W: the UNPOOLED     */
+/* size, both even (DLWP_E_UNSUPPORTED otherwise).  bwd WRITES dx [B][H][W][C] = 0.25 * dy at all four positions. */
+int dlwp_avgpool2x2_fwd(const float* x, float* y, int B, int H, int W, int C, void* stream);
+int dlwp_avgpool2x2_bwd(const float* dy, float* dx, int B, int H, int W, int C, void* stream);
+/* y [npix][Cout] = x [npix][Cin] . w^T + bias (nn.Conv2d's [Cout][Cin][1][1]; bias nullable); dgrad WRITES        */
+/* dx [npix][Cin] = dy [npix][Cout] . w.                                                                          */
+int dlwp_conv1x1_fwd(const float* x, const float* w, const float* bias, float* y, long long npix, int Cin, int Cout,
+                     void* stream);
+int dlwp_conv1x1_dgrad(const float* dy, const float* w, float* dx, long long npix, int Cin, int Cout, void* stream);
+/* ConvTranspose2d(Cin, Cout, kernel_size=2, stride=2): y [B][2H][2W][Cout], y[2i+di][2j+dj][co] =                 */
+/* sum_ci x[i][j][ci] w[ci][co][di][dj] + bias[co] with w the layer's own [Cin][Cout][2][2]; H, W: the INPUT size.  */
+/* dgrad WRITES dx [B][H][W][Cin] from dy [B][2H][2W][Cout].                                                       */
+int dlwp_upconv2x2_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
+                       int Cout, void* stream);
+int dlwp_upconv2x2_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Cout,
+                         void* stream);
+/* Weight and bias gradients of the two layers, ACCUMULATED into gw (the parameter's own layout) and gb [Cout]    */
+/* (NULL: none; for the up-convolution the sum of dy over all four positions).  ws: scratch of *_ws_floats floats  */
+/* (per-workgroup partial sums, folded in a fixed order).                                                         */
+long long dlwp_conv1x1_wgrad_ws_floats(long long npix, int Cin, int Cout);
+int dlwp_conv1x1_wgrad(const float* x, const float* dy, float* ws, float* gw, float* gb, long long npix, int Cin,
+                       int Cout, void* stream);
+long long dlwp_upconv2x2_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout);
+int dlwp_upconv2x2_wgrad(const float* x, const float* dy, float* ws, float* gw, float* gb, int B, int H, int W,
+                         int Cin, int Cout, void* stream);
+
 /* bench probe: ONE forward `spatial` launch of an inner FNO block as the rollout issues it     */
 /* (x = previous pre-activation, GELU on load; spec = [B][m1][m2c][C][2] mixed modes; fused      */
 /* W-axis DFT of gelu(pre) into x1_out [B][H][m2c][C][2]).                                       */
