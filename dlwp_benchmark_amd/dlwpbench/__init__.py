@@ -2,10 +2,11 @@
 from .convlstm import ConvLSTM  # noqa: F401
 from .fno import FNO2DModule, TFNO2DModule  # noqa: F401
 from .fourcastnet import AFNONet, FourCastNet, FourCastNetv2, SFNONet  # noqa: F401
+from .meshgraphnet import MeshGraphNet  # noqa: F401
 from .panguweather import PanguWeather  # noqa: F401
 from .sfno import SFNO2DModule  # noqa: F401
 from .swin_transformer import SwinTransformer  # noqa: F401
 from .unet import UNet, UNetHPX  # noqa: F401
 
 __all__ = ["FNO2DModule", "TFNO2DModule", "SFNO2DModule", "AFNONet", "FourCastNet", "FourCastNetv2", "SFNONet", "PanguWeather",
-           "SwinTransformer", "ConvLSTM", "UNet", "UNetHPX"]
+           "SwinTransformer", "ConvLSTM", "UNet", "UNetHPX", "MeshGraphNet"]

@@ -24,6 +24,18 @@ class FnoCfg(C.Structure):
         "projection", "n_layers", "m1", "m2c", "out_channels", "form", "constant_channels", "prescribed_channels", "m0")]
 
 
+class GraphMlpArgs(C.Structure):
+    """dlwp_graph_mlp_args (include/dlwpmi.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("mode", "B", "N", "E")] + [("rows", C.c_longlong)]
+                + [(n, C.c_void_p) for n in ("x", "v", "src", "dst", "in_ptr", "in_eid")]
+                + [(n, C.c_int) for n in ("De", "Dv", "hidden", "out", "hidden_layers", "residual", "mean")] + [("eps", C.c_float)]
+                + [("w", C.c_void_p * 4), ("b", C.c_void_p * 4), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p),
+                   ("hid", C.c_void_p * 3), ("xhat", C.c_void_p), ("rstd", C.c_void_p), ("agg", C.c_void_p)])
+
+
+GRAPH_MAX_WIDTH, GRAPH_MAX_HIDDEN_LAYERS = 128, 3      # DLWP_GRAPH_MAX_WIDTH, DLWP_GRAPH_MAX_HIDDEN_LAYERS
+GRAPH_ROWS, GRAPH_EDGE, GRAPH_NODE = 0, 1, 2
+
 # parameter kinds of the flat FNO parameter buffer (dlwpmi.h enum)
 P_LIFT_W1, P_LIFT_B1, P_LIFT_W2, P_LIFT_B2, P_PROJ_W1, P_PROJ_B1, P_PROJ_W2, P_PROJ_B2, \
     P_SPEC_W, P_SKIP_W, P_SPEC_B = range(11)
@@ -208,6 +220,14 @@ SIGNATURES = {
     "dlwp_conv1x1_wgrad": (_I, [_V] * 5 + [_L, _I, _I, _V]),
     "dlwp_upconv2x2_wgrad_ws_floats": (_L, [_I] * 5),
     "dlwp_upconv2x2_wgrad": (_I, [_V] * 5 + [_I] * 5 + [_V]),
+    "dlwp_graph_mlp_fwd": (_I, [C.POINTER(GraphMlpArgs), _V]),
+    "dlwp_graph_ln_bwd_ws_floats": (_L, [_L, _I]),
+    "dlwp_graph_ln_bwd": (_I, [_V] * 8 + [_L, _I, _V]),
+    "dlwp_graph_wgrad0_ws_floats": (_L, [_L, _I, _I]),
+    "dlwp_graph_wgrad0": (_I, [_I] + [_V] * 8 + [_I, _I, _I, _L, _I, _I, _I, _V]),
+    "dlwp_graph_dgrad0": (_I, [_I] + [_V] * 6 + [_I, _I, _I, _L, _I, _I, _I, _V]),
+    "dlwp_graph_gather_sum": (_I, [_V, _V, _V, _I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _V]),
+    "dlwp_graph_edge_gather": (_I, [_V] * 5 + [_I] * 4 + [_V]),
     "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),
     "dlwp_debug_null_kernels": (_I, [_I, _I, _V]),
     "dlwp_debug_spin_kernels": (_I, [_I, _I, _I, _I, _I, _V]),

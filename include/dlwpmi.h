@@ -1031,6 +1031,69 @@ long long dlwp_upconv2x2_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout)
 int dlwp_upconv2x2_wgrad(const float* x, const float* dy, float* ws, float* gw, float* gb, int B, int H, int W,
                          int Cin, int Cout, void* stream);
 
+/* ---- graph kernels of the MeshGraphNet baselines (csrc/graph_ops.hip) ------------------------------------------ */
+/* Reference: MeshGraphMLP / MeshEdgeBlock / MeshNodeBlock of src/{nsbench,dlwpbench}/models/graphcast/gnn_layers/    */
+/* (mesh_graph_mlp.py:171-194, mesh_edge_block.py:86-94, mesh_node_block.py:83-93; concat_efeat_dgl and              */
+/* agg_concat_dgl in utils.py:115-150, 340-380).  Activations are fp32 row-major [rows][width]; src, dst, the CSR    */
+/* offsets and edge ids are int32 DEVICE arrays of ONE sample's graph (N nodes, E edges) whose indices the caller    */
+/* has checked; sample b's node i is row b N + i, its edge k row b E + k.  No atomics: every launch is bit-          */
+/* reproducible.  Every width is 1..DLWP_GRAPH_MAX_WIDTH, 1..DLWP_GRAPH_MAX_HIDDEN_LAYERS hidden layers.             */
+#define DLWP_GRAPH_MAX_WIDTH 128
+#define DLWP_GRAPH_MAX_HIDDEN_LAYERS 3
+enum { DLWP_GRAPH_ROWS = 0, DLWP_GRAPH_EDGE = 1, DLWP_GRAPH_NODE = 2 };
+/* One launch: hidden_layers x (Linear + bias + ReLU), Linear + bias [, LayerNorm (biased variance, affine) when     */
+/* gamma != NULL] [, + residual] on the operand rows                                                                */
+/*   rows  A[r] = x[r]                                   (x [rows][De])                                              */
+/*   edge  A[r] = x[r] | v[b N + src[k]] | v[b N + dst[k]]   (x = e [B E][De], v [B N][Dv]; residual: + e[r])          */
+/*   node  A[r] = agg[r] | v[r],  agg[r] = sum (mean != 0: mean) of x[b E + in_eid[j]], in_ptr[i] <= j < in_ptr[i+1]   */
+/*         (x = e [B E][De]; a node without in-edges gets zeros; residual: + v[r])                                   */
+/* which are assembled while they are staged: the concatenation is never written.  w[l] [out_l][in_l] and b[l] are   */
+/* nn.Linear's own arrays (b[l] nullable); every hidden layer has `hidden` columns.  Stored for a backward pass,     */
+/* each unless NULL: hid[l] [rows][hidden] post-ReLU rows, xhat [rows][out] normalised rows, rstd [rows] 1 / sigma,   */
+/* agg [B N][De] (node mode).                                                                                        */
+typedef struct dlwp_graph_mlp_args {
+    int mode, B, N, E;
+    long long rows;                     /* rows mode only; edge: B E, node: B N */
+    const float *x, *v;
+    const int *src, *dst, *in_ptr, *in_eid;
+    int De, Dv, hidden, out, hidden_layers, residual, mean;
+    float eps;
+    const float* w[DLWP_GRAPH_MAX_HIDDEN_LAYERS + 1];
+    const float* b[DLWP_GRAPH_MAX_HIDDEN_LAYERS + 1];
+    const float *gamma, *beta;
+    float* y;
+    float* hid[DLWP_GRAPH_MAX_HIDDEN_LAYERS];
+    float *xhat, *rstd, *agg;
+} dlwp_graph_mlp_args;
+int dlwp_graph_mlp_fwd(const dlwp_graph_mlp_args* args, void* stream);
+/* LayerNorm backward from the stored rows: WRITES dz [rows][C]; ggamma / gbeta (each nullable) are ACCUMULATED      */
+/* into from per-workgroup column sums folded in workgroup order.  ws: dlwp_graph_ln_bwd_ws_floats floats.           */
+long long dlwp_graph_ln_bwd_ws_floats(long long rows, int C);
+int dlwp_graph_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* ws,
+                      float* ggamma, float* gbeta, long long rows, int C, void* stream);
+/* Weight and bias gradient of the FIRST Linear: gw [hidden][K0] += dz^T . A, gb [hidden] += column sums of dz      */
+/* (NULL: none), with A gathered as in the forward (K0 = De | De + 2 Dv | De + Dv; node mode: x = the stored agg).  */
+/* ws: dlwp_graph_wgrad0_ws_floats(rows, K0, hidden) floats of per-workgroup partial sums, folded in a fixed order.  */
+long long dlwp_graph_wgrad0_ws_floats(long long rows, int K0, int hidden);
+int dlwp_graph_wgrad0(int mode, const float* x, const float* v, const int* src, const int* dst, const float* dz, float* ws,
+                      float* gw, float* gb, int B, int N, int E, long long rows, int De, int Dv, int hidden, void* stream);
+/* Input gradient of the first Linear, dA = dz . w (w [hidden][K0]), WRITTEN in parts (each nullable):               */
+/*   rows  out0 = dx [rows][De]                                                                                      */
+/*   edge  out0 = de [B E][De] (+ res), out1 = per-edge d_src [B E][Dv], out2 = per-edge d_dst [B E][Dv]              */
+/*   node  out0 = d_agg [B N][De], out1 = dv [B N][Dv] (+ res)                                                        */
+/* res (nullable): the gradient arriving along the block's residual, in the layout of the part it is added to.       */
+int dlwp_graph_dgrad0(int mode, const float* dz, const float* w, const float* res, float* out0, float* out1, float* out2,
+                      int B, int N, int E, long long rows, int De, int Dv, int hidden, void* stream);
+/* out[b N + i] = [add[b N + i]] + sum_j in1[b E + eid1[j]] (ptr1[i] <= j < ptr1[i+1]; mean1 != 0: divided by the     */
+/* count) [+ sum_j in2[b E + eid2[j]] over the second list], rows of width C, summed in list order.  The forward     */
+/* aggregation on its own (in-edges), and dv of an edge block (out-edges of d_src, in-edges of d_dst).               */
+int dlwp_graph_gather_sum(const float* in1, const int* ptr1, const int* eid1, int mean1, const float* in2, const int* ptr2,
+                          const int* eid2, const float* add, float* out, int B, int N, int E, int C, void* stream);
+/* out[b E + k] = [add[b E + k]] + in[b N + dst[k]] (in_ptr != NULL: divided by the in-degree of dst[k]): de of a     */
+/* node block from d_agg.                                                                                            */
+int dlwp_graph_edge_gather(const float* in, const int* dst, const int* in_ptr, const float* add, float* out, int B, int N,
+                           int E, int C, void* stream);
+
 /* bench probe: ONE forward `spatial` launch of an inner FNO block as the rollout issues it     */
 /* (x = previous pre-activation, GELU on load; spec = [B][m1][m2c][C][2] mixed modes; fused      */
 /* W-axis DFT of gelu(pre) into x1_out [B][H][m2c][C][2]).                                       */
