@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
-from .token_ops import _grad_slot
+from .token_ops import _grad_buffer, _grad_slot
 
 PAD = {"zeros": 0, "circular": 1}
 ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2}
@@ -37,11 +37,8 @@ def pack_weight(weight, kind):
     _check_weight(weight)
     lib = L.load()
     cout, cin = weight.shape[0], weight.shape[1]
-    n = lib.dlwp_conv3x3_image_floats(cin, cout, kind)
-    if n < 0:
-        L.check(int(n))
     w = weight.detach()
-    img = torch.empty(n, device=w.device)
+    img = L.workspace(lib.dlwp_conv3x3_image_floats, cin, cout, kind, device=w.device)
     L.check(lib.dlwp_conv3x3_pack(L.ptr(w.contiguous()), L.ptr(img), cin, cout, kind, L.stream()))
     return img
 
@@ -66,17 +63,12 @@ def _weight_grad(x1, x2, dz, weight_shape, wslot, bslot, has_bias, pads):
     B, H, W, C1 = x1.shape
     C2 = x2.shape[-1] if x2 is not None else 0
     cout = weight_shape[0]
-    gw = wslot if wslot is not None else torch.zeros(weight_shape, device=dz.device)
-    gb = None
-    if has_bias:
-        gb = bslot if bslot is not None else torch.zeros(cout, device=dz.device)
-    n = lib.dlwp_conv3x3_wgrad_ws_floats(B, H, W, C1 + C2, cout)
-    if n < 0:
-        L.check(int(n))
-    ws = torch.empty(n, device=dz.device)
+    gw, gw_out = _grad_buffer(wslot, weight_shape, dz.device)
+    gb, gb_out = _grad_buffer(bslot, cout, dz.device) if has_bias else (None, None)
+    ws = L.workspace(lib.dlwp_conv3x3_wgrad_ws_floats, B, H, W, C1 + C2, cout, device=dz.device)
     L.check(lib.dlwp_conv3x3_wgrad(L.ptr(x1), L.ptr(x2), L.ptr(dz), L.ptr(ws), L.ptr(gw), L.ptr(gb), B, H, W, C1, C2, cout,
                                    pads[0], pads[1], L.stream()))
-    return (None if wslot is not None else gw), (None if (bslot is not None or not has_bias) else gb)
+    return gw_out, gb_out
 
 
 class _Conv3x3Fn(torch.autograd.Function):
@@ -269,19 +261,15 @@ def _pixel_weight_grad(up, x, dy, weight_shape, wslot, bslot, has_bias):
     lib = L.load()
     B, H, W, cin = x.shape
     cout = weight_shape[1] if up else weight_shape[0]
-    gw = wslot if wslot is not None else torch.zeros(weight_shape, device=dy.device)
-    gb = None
-    if has_bias:
-        gb = bslot if bslot is not None else torch.zeros(cout, device=dy.device)
-    n = lib.dlwp_upconv2x2_wgrad_ws_floats(B, H, W, cin, cout) if up else lib.dlwp_conv1x1_wgrad_ws_floats(B * H * W, cin, cout)
-    if n < 0:
-        L.check(int(n))
-    ws = torch.empty(n, device=dy.device)
+    gw, gw_out = _grad_buffer(wslot, weight_shape, dy.device)
+    gb, gb_out = _grad_buffer(bslot, cout, dy.device) if has_bias else (None, None)
     if up:
+        ws = L.workspace(lib.dlwp_upconv2x2_wgrad_ws_floats, B, H, W, cin, cout, device=dy.device)
         L.check(lib.dlwp_upconv2x2_wgrad(L.ptr(x), L.ptr(dy), L.ptr(ws), L.ptr(gw), L.ptr(gb), B, H, W, cin, cout, L.stream()))
     else:
+        ws = L.workspace(lib.dlwp_conv1x1_wgrad_ws_floats, B * H * W, cin, cout, device=dy.device)
         L.check(lib.dlwp_conv1x1_wgrad(L.ptr(x), L.ptr(dy), L.ptr(ws), L.ptr(gw), L.ptr(gb), B * H * W, cin, cout, L.stream()))
-    return (None if wslot is not None else gw), (None if (bslot is not None or not has_bias) else gb)
+    return gw_out, gb_out
 
 
 class _PixelConvFn(torch.autograd.Function):

@@ -18,18 +18,17 @@
 // one 16-byte LDS read and a chunk's image is one contiguous copy.  kind 1 reorders the columns of a cell weight so that the
 // four gate pre-activations of a hidden channel are the four column tiles of ONE lane; kind 2 is the flipped, transposed image
 // that turns the same kernel into the input-gradient product.
-#include "common.hip.h"
-#include "dlwpmi_internal.h"
+#include "row_gemm.hip.h"
 
 namespace {
 
 constexpr int TH = 8, TW = 16;            // pixel tile
 constexpr int HR = TH + 2, HC = TW + 2;   // with halo
-constexpr int KC = 16;                    // channels per chunk
-constexpr int AP = 20;                    // LDS floats per haloed pixel in the forward kernel (16 + 4: conflict-free 16-byte reads)
+using rowgemm::KC;                        // channels per chunk
+using rowgemm::AP;                        // LDS floats per haloed pixel in the forward kernel
+using rowgemm::ZP;                        // LDS floats per pixel of the dz tile in the weight-gradient kernel
 constexpr int NPIX_H = HR * HC;           // 180
 constexpr int STAGE_IT = (NPIX_H + 15) / 16;
-constexpr int ZP = 80;                    // LDS floats per pixel of the dz tile in the weight-gradient kernel (64 + 16)
 
 enum { PAD_ZEROS = 0, PAD_CIRCULAR = 1 };
 enum { ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2 };
@@ -259,8 +258,9 @@ __global__ __launch_bounds__(256) void conv3x3_act_bwd_kernel(const float* __res
 // N = output channels, K = pixels.  Workgroup (ci block of 16, co block of 64, split s) walks the pixel tiles s, s + S, ...
 // with the haloed input tile and the dz tile in LDS; wave w owns output channels 16w..16w+15 and the nine taps (nine
 // independent accumulators).  The partial sums go to ws [S][9][Cin_pad][Cout_pad] and are folded in the fixed order s = 0..S-1
-// by the fold kernel (no atomics: two launches on the same operands are bit-identical).  The bias gradient rides along as input
-// channel Cin, which is staged as the constant 1: its centre tap is sum_p dz[p][co].
+// by the fold kernel (no atomics: two launches on the same operands are bit-identical); S is row_gemm.hip.h's split_k_geometry, the
+// rule of the row kernels' weight gradients.  The bias gradient rides along as input channel Cin, which is staged as the constant
+// 1: its centre tap is sum_p dz[p][co].
 struct WgradArgs {
     const float *x1, *x2, *dz;
     float* ws;
@@ -354,14 +354,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_fold_kernel(const float* __
 }
 
 inline void wgrad_geometry(int B, int H, int W, int Cin, int Cout, int* cin_pad, int* cout_pad, int* ntiles, int* S) {
-    *cin_pad = round_up(Cin + 1, KC);
-    *cout_pad = round_up(Cout, 64);
     *ntiles = B * ceil_div(H, TH) * ceil_div(W, TW);
-    const int blocks = (*cin_pad / KC) * (*cout_pad / 64);
-    int s = ceil_div(512, blocks);
-    if (s > 32) s = 32;
-    if (s > *ntiles) s = *ntiles;
-    *S = s;
+    rowgemm::split_k_geometry(*ntiles, Cin + 1, Cout, cin_pad, cout_pad, S);
 }
 
 bool pad_ok(int p) { return p == PAD_ZEROS || p == PAD_CIRCULAR; }

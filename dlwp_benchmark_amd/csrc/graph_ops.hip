@@ -17,29 +17,27 @@
 //   NODE  A[r] = agg[r] | v[r],  agg[r] = sum (or mean) of e[b E + eid] over the in-edges of node r in CSR order
 // so cat(...) never exists in memory.  Hidden rows stay in LDS ([64][NS*16 + 4], rewritten in place: a wave reads and writes only
 // its own 16 rows); the weight tile [16][NS*16] of each chunk is staged straight from nn.Linear's [out][in] layout, zero-filled
-// beyond K and N (nothing in memory is padded).  Fragments as in pixel_gemm_kernel (common.hip.h mfma16_chunk, exact fp32).
+// beyond K and N (nothing in memory is padded).  The chunk loop is row_gemm.hip.h's (row_gemm_chunks) in a copy of this kernel's
+// own: its barrier at the top of a chunk also hands Hs from one layer to the next, and from the second layer on the A fragment
+// comes from Hs.
 // When a backward pass follows the launch also stores the post-ReLU hidden rows, the normalised rows, 1/sigma and (NODE) agg.
 //
 // Backward of the FIRST Linear (the others are Linears on stored rows: dlwp_conv1x1_dgrad / _wgrad):
-// * graph_wgrad0_kernel: gW0 = dz0^T . A with A gathered again exactly as in the forward (NODE reads the stored agg); partial sums
-//   per workgroup in ws [S][k_pad][n_pad], folded in the fixed order s = 0..S-1 INTO gw [hidden][K0] and gb (the bias rides along
-//   as operand column K0 = 1), as pixel_wgrad_kernel does;
-// * graph_dgrad0_kernel: dA = dz0 . W0, split while it is stored: EDGE -> de (+ the residual's dy), per-edge d_src, per-edge d_dst;
+// * graph_wgrad0_kernel: gW0 = dz0^T . A with A gathered again exactly as in the forward (NODE reads the stored agg), on
+//   row_gemm.hip.h's split-K tile walk and fold (row_wgrad_tiles: INTO gw [hidden][K0] and gb; the bias rides along as operand
+//   column K0 = 1);
+// * graph_dgrad0_kernel: dA = dz0 . W0 (row_gemm_chunks), split while it is stored: EDGE -> de (+ the residual's dy), per-edge d_src, per-edge d_dst;
 //   NODE -> d_agg, dv (+ the residual's dy); ROWS -> dx;
 // * graph_gather_sum_kernel: out[b N + i] = [add] + sum over CSR list 1 of in1 rows [/ degree] + sum over CSR list 2 of in2 rows, in
 //   list order (dv of an edge block: out-edges of d_src, in-edges of d_dst; also the forward aggregation on its own);
 // * graph_edge_gather_kernel: out[b E + k] = [add] + d_agg[b N + dst[k]] [/ in-degree] (de of a node block).
 // LayerNorm backward (graph_ln_bwd_kernel) works from the stored normalised rows and 1/sigma; the gamma / beta gradients are
 // per-workgroup column sums folded in workgroup order INTO the gradient buffers.
-#include "common.hip.h"
-#include "dlwpmi_internal.h"
+#include "row_gemm.hip.h"
 
 namespace {
 
-constexpr int TM = 64;        // rows per workgroup
-constexpr int KC = 16;        // K values per chunk
-constexpr int AP = 20;        // LDS floats per row of the staged operand tile (16 + 4: conflict-free 16-byte reads)
-constexpr int ZP = 80;        // LDS floats per row of the dz tile in the weight-gradient kernel (64 + 16)
+using namespace rowgemm;      // TM rows per workgroup, KC K values per chunk, AP
 constexpr int MAXW = DLWP_GRAPH_MAX_WIDTH;
 constexpr int MAXL = DLWP_GRAPH_MAX_HIDDEN_LAYERS;
 constexpr long long ROW_LIMIT = (1ll << 31) - 64;      // the kernels form row indices of a whole last 64-row tile in int
@@ -268,120 +266,39 @@ __device__ __forceinline__ float operand_bwd(const Grad0Args& a, int m, int c) {
     }
 }
 
-// gW0 = A^T . dz: workgroup (operand block of 16, dz column block of 64, split s) walks the row tiles s, s + S, ...
+// gW0 = A^T . dz: this thread stages operand column c and dz column col
 template <int MODE>
 __global__ __launch_bounds__(256) void graph_wgrad0_kernel(const Grad0Args a) {
-    __shared__ float As[TM * KC];
-    __shared__ float Zs[TM * ZP];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
-    const int c = blockIdx.x * KC + (tid & 15);           // operand column this thread stages
-    const int col = blockIdx.y * 64 + (tid & 63);         // dz column this thread stages
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    float v[4], zv[16];
-    auto fetch = [&](int t) {
-        const int m0 = t * TM;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + (tid >> 4) + 16 * i;
-            v[i] = m < a.R ? operand_bwd<MODE>(a, m, c) : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int m = m0 + (tid >> 6) + 4 * i;
-            zv[i] = (m < a.R && col < a.hidden) ? a.dz[(long long)m * a.hidden + col] : 0.f;
-        }
-    };
-    if ((int)blockIdx.z < a.ntiles) fetch(blockIdx.z);
-    for (int t = blockIdx.z; t < a.ntiles; t += a.S) {
-        __syncthreads();                          // the previous tile has been consumed
-#pragma unroll
-        for (int i = 0; i < 4; ++i) As[((tid >> 4) + 16 * i) * KC + (tid & 15)] = v[i];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) Zs[((tid >> 6) + 4 * i) * ZP + (tid & 63)] = zv[i];
-        __syncthreads();
-        if (t + a.S < a.ntiles) fetch(t + a.S);
-#pragma unroll 4
-        for (int i = 0; i < TM / 4; ++i) {
-            const int m = 4 * i + g;
-            acc = mfma16(As[m * KC + r], Zs[m * ZP + 16 * w + r], acc);
-        }
-    }
-    // lane (r, g) register j: operand column 4g + j of the block, dz column 16w + r of the block
-    float* dst = a.ws + (long long)blockIdx.z * a.k_pad * a.n_pad;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dst[(long long)(blockIdx.x * KC + 4 * g + j) * a.n_pad + blockIdx.y * 64 + 16 * w + r] = acc[j];
-}
-
-// gw[col][k] += sum_s ws[s][k][col],  gb[col] += sum_s ws[s][K0][col]
-__global__ __launch_bounds__(256) void graph_wgrad0_fold_kernel(const float* __restrict__ ws, float* gw, float* gb, int K0, int hidden,
-                                                                int S, int k_pad, int n_pad) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;      // (k <= K0, column), column fastest
-    if (e >= (long long)(K0 + 1) * hidden) return;
-    const int col = (int)(e % hidden), k = (int)(e / hidden);
-    const long long stride = (long long)k_pad * n_pad;
-    const float* p = ws + (long long)k * n_pad + col;
-    float s = 0.f;
-    for (int i = 0; i < S; ++i) s += p[i * stride];
-    if (k < K0) gw[(long long)col * K0 + k] += s;
-    else if (gb) gb[col] += s;
-}
-
-inline void wgrad0_geometry(long long R, int K0, int hidden, int* k_pad, int* n_pad, int* ntiles, int* S) {
-    *k_pad = round_up(K0 + 1, KC);
-    *n_pad = round_up(hidden, 64);
-    *ntiles = (int)((R + TM - 1) / TM);
-    const int blocks = (*k_pad / KC) * (*n_pad / 64);
-    int s = ceil_div(512, blocks);
-    if (s > 32) s = 32;
-    if (s > *ntiles) s = *ntiles;
-    *S = s;
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x * KC + (tid & 15);
+    const int col = blockIdx.y * 64 + (tid & 63);
+    row_wgrad_tiles(
+        a.ws, a.ntiles, a.S, a.k_pad, a.n_pad,
+        [&](int m) -> float { return m < a.R ? operand_bwd<MODE>(a, m, c) : 0.f; },
+        [&](int m) -> float { return (m < a.R && col < a.hidden) ? a.dz[(long long)m * a.hidden + col] : 0.f; });
 }
 
 // dA[R][K0] = dz[R][hidden] . W0[hidden][K0], one workgroup per (64 rows, 64 columns), stored in parts
 template <int MODE>
 __global__ __launch_bounds__(256) void graph_dgrad0_kernel(const Grad0Args a) {
     constexpr int NS = 4, NC = 64;
-    __shared__ float As[TM * AP];
-    __shared__ float Ws[KC * NC];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * TM, n0 = blockIdx.y * NC;
-    const int K = a.hidden;
+    const long long ldz = a.hidden;               // 64-bit here, once: widened inside the loader's condition it costs 4 instructions per load
     f32x4 acc[NS];
+    row_gemm_chunks<NS>(
+        a.hidden, acc,
+        [&](int k, bool ok, float (&v)[4]) {
 #pragma unroll
-    for (int ns = 0; ns < NS; ++ns) acc[ns] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float v[4], wv[NS];
-    auto fetch = [&](int kc) {
-        const int k = kc * KC + (tid & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + (tid >> 4) + 16 * i;
-            v[i] = (k < K && m < a.R) ? a.dz[(long long)m * K + k] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            const int u = tid + 256 * i;
-            const int s = u & 3, col = (u >> 2) % NC, gg = (u >> 2) / NC;
-            const int kk = kc * KC + 4 * gg + s, n = n0 + col;
-            wv[i] = (kk < K && n < a.K0) ? a.w[(long long)kk * a.K0 + n] : 0.f;
-        }
-    };
-    const int nchunks = (K + KC - 1) / KC;
-    fetch(0);
-    for (int kc = 0; kc < nchunks; ++kc) {
-        if (kc) __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) As[((tid >> 4) + 16 * i) * AP + (tid & 15)] = v[i];
-#pragma unroll
-        for (int i = 0; i < NS; ++i) Ws[tid + 256 * i] = wv[i];
-        __syncthreads();
-        if (kc + 1 < nchunks) fetch(kc + 1);
-        const f32x4 af = *reinterpret_cast<const f32x4*>(&As[(16 * w + r) * AP + 4 * g]);
-#pragma unroll
-        for (int ns = 0; ns < NS; ++ns) {
-            const f32x4 bf = *reinterpret_cast<const f32x4*>(&Ws[(g * NC + ns * 16 + r) * 4]);
-            acc[ns] = mfma16_chunk(af, bf, acc[ns]);
-        }
-    }
+            for (int i = 0; i < 4; ++i) {
+                const int m = m0 + (tid >> 4) + 16 * i;
+                v[i] = (ok && m < a.R) ? a.dz[m * ldz + k] : 0.f;
+            }
+        },
+        [&](int kk, int col, bool ok) -> float {
+            const int n = n0 + col;
+            return (ok && n < a.K0) ? a.w[(long long)kk * a.K0 + n] : 0.f;
+        });
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const long long m = m0 + 16 * w + 4 * g + j;
@@ -511,8 +428,8 @@ __global__ __launch_bounds__(256) void graph_ln_bwd_fold_kernel(const float* __r
 }
 
 inline int ln_bwd_blocks(long long rows) {
-    const long long ntiles = (rows + TM - 1) / TM;
-    return (int)(ntiles < 256 ? ntiles : 256);
+    const int ntiles = row_tiles(rows);
+    return ntiles < 256 ? ntiles : 256;
 }
 
 bool width_ok(int v) { return v >= 1 && v <= MAXW; }
@@ -592,9 +509,7 @@ extern "C" long long dlwp_graph_wgrad0_ws_floats(long long rows, int K0, int hid
         dlwp_set_error("graph_wgrad0_ws_floats: bad shape (%lld rows, operand width %d, hidden %d)", rows, K0, hidden);
         return DLWP_E_INVALID;
     }
-    int k_pad, n_pad, ntiles, S;
-    wgrad0_geometry(rows, K0, hidden, &k_pad, &n_pad, &ntiles, &S);
-    return (long long)S * k_pad * n_pad;
+    return row_wgrad_ws_floats(rows, K0, hidden);
 }
 
 extern "C" int dlwp_graph_wgrad0(int mode, const float* x, const float* v, const int* src, const int* dst, const float* dz, float* ws,
@@ -607,25 +522,10 @@ extern "C" int dlwp_graph_wgrad0(int mode, const float* x, const float* v, const
     Grad0Args a{};
     a.x = x; a.v = v; a.src = src; a.dst = dst; a.dz = dz; a.ws = ws;
     a.R = (int)rows; a.N = N; a.E = E; a.De = De; a.Dv = Dv; a.K0 = K0; a.hidden = hidden;
-    wgrad0_geometry(rows, K0, hidden, &a.k_pad, &a.n_pad, &a.ntiles, &a.S);
     hipStream_t s = (hipStream_t)stream_;
-    {
-        dlwp_prof_scope ps(s, 2.0 * rows * (K0 + 1.0) * hidden, 4.0 * ((double)rows * (K0 + hidden) + (double)a.S * a.k_pad * a.n_pad),
-                           "graph_wgrad0_%s", mode_name(mode));
-        const dim3 grid(a.k_pad / KC, a.n_pad / 64, a.S), block(256);
-        if (mode == ROWS) hipLaunchKernelGGL(graph_wgrad0_kernel<ROWS>, grid, block, 0, s, a);
-        else if (mode == EDGE) hipLaunchKernelGGL(graph_wgrad0_kernel<EDGE>, grid, block, 0, s, a);
-        else hipLaunchKernelGGL(graph_wgrad0_kernel<NODE>, grid, block, 0, s, a);
-        DLWP_LAUNCH_CHECK();
-    }
-    {
-        const long long n = (long long)(K0 + 1) * hidden;
-        dlwp_prof_scope ps(s, (double)a.S * n, 4.0 * (a.S + 2.0) * n, "graph_wgrad0_fold");
-        hipLaunchKernelGGL(graph_wgrad0_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, gw, gb, K0, hidden, a.S,
-                           a.k_pad, a.n_pad);
-        DLWP_LAUNCH_CHECK();
-    }
-    return DLWP_OK;
+    if (mode == ROWS) return launch_row_wgrad(graph_wgrad0_kernel<ROWS>, a, rows, K0, hidden, gw, gb, s, "graph_wgrad0_rows", "graph_wgrad0_fold");
+    if (mode == EDGE) return launch_row_wgrad(graph_wgrad0_kernel<EDGE>, a, rows, K0, hidden, gw, gb, s, "graph_wgrad0_edge", "graph_wgrad0_fold");
+    return launch_row_wgrad(graph_wgrad0_kernel<NODE>, a, rows, K0, hidden, gw, gb, s, "graph_wgrad0_node", "graph_wgrad0_fold");
 }
 
 extern "C" int dlwp_graph_dgrad0(int mode, const float* dz, const float* w, const float* res, float* out0, float* out1, float* out2,
@@ -699,7 +599,7 @@ extern "C" int dlwp_graph_ln_bwd(const float* dy, const float* xhat, const float
     {
         dlwp_prof_scope ps(s, 10.0 * rows * C, 4.0 * 3.0 * rows * C, "graph_ln_bwd");
         hipLaunchKernelGGL(graph_ln_bwd_kernel, dim3(nblk), dim3(256), 0, s, dy, xhat, rstd, gamma, dz, ws, (int)rows, C,
-                           (int)((rows + TM - 1) / TM));
+                           row_tiles(rows));
         DLWP_LAUNCH_CHECK();
     }
     {

@@ -15,19 +15,18 @@
 //   (2i + di, 2j + dj).  Wm[k][n] = w[k][co][di][dj] of nn.ConvTranspose2d's own [Cin][Cout][2][2].
 // * GATHER: its input gradient, dx[p][ci] = sum_{tap, co} dy[pixel(p, tap)][co] w[ci][co][tap]: K = 4 Cout with the same
 //   tap-major order, the operand load gathers from the four output pixels, Wm[k][n] = w[n][co][tap].
-// One workgroup (4 waves) owns 64 pixels x NS*16 columns; wave w owns pixels 16w..16w+15.  Per chunk of 16 K-values the
-// operand tile [64][16] and the weight tile [16][NS*16] are staged in LDS (zero-filled beyond K and N: nothing in memory is
-// padded), the weights straight from the parameter's layout.  Fragments as in conv3x3_kernel (common.hip.h mfma16_chunk).
+// One workgroup (4 waves) owns 64 pixels x NS*16 columns and runs the chunk loop of row_gemm.hip.h (row_gemm_chunks) on them: a
+// mode is a pair of loaders (the weights straight from the parameter's layout) and an epilogue.
 //
 // Weight gradients (pixel_wgrad_kernel): gW = X^T . dY with K = pixels, M = input channels, N = columns (Cout, or 4 Cout
-// tap-major for the up-convolution, gathered like GATHER).  Workgroup (ci block of 16, column block of 64, split s) walks the
-// 64-pixel tiles s, s + S, ...; the partial sums go to ws [S][cin_pad][ncol_pad] and the fold kernel adds them in the fixed
-// order s = 0..S-1 INTO gw and gb in the parameter's own layout.  The bias gradient rides along as input channel Cin, staged as
-// the constant 1 (for the up-convolution the fold adds its four tap columns, tap = 0..3).
-#include "common.hip.h"
-#include "dlwpmi_internal.h"
+// tap-major for the up-convolution, gathered like GATHER), on the split-K tile walk of row_gemm.hip.h (row_wgrad_tiles); the fold
+// adds the partial sums INTO gw and gb in the parameter's own layout.  The bias gradient rides along as input channel Cin, loaded
+// as the constant 1 (for the up-convolution the fold adds its four tap columns, tap = 0..3).
+#include "row_gemm.hip.h"
 
 namespace {
+
+using namespace rowgemm;
 
 // ---------------------------------------------------------------- average pool
 // VEC floats of one pooled pixel per thread: y = 0.25 * (((a + b) + c) + d), a..d = (2i, 2j), (2i, 2j+1), (2i+1, 2j), (2i+1, 2j+1)
@@ -86,11 +85,6 @@ __global__ __launch_bounds__(256) void avgpool2x2_bwd_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------- pixel GEMM
-constexpr int TM = 64;        // pixels per workgroup
-constexpr int KC = 16;        // K values per chunk
-constexpr int AP = 20;        // LDS floats per pixel of the operand tile (16 + 4: conflict-free 16-byte reads)
-constexpr int ZP = 80;        // LDS floats per pixel of the dy tile in the weight-gradient kernel (64 + 16)
-
 enum { PLAIN = 0, SCATTER = 1, GATHER = 2 };
 
 struct PixArgs {
@@ -114,77 +108,45 @@ __device__ __forceinline__ int tap_offset(int tap, int W) { return (tap >> 1) * 
 
 template <int MODE, int NS>
 __global__ __launch_bounds__(256) void pixel_gemm_kernel(const PixArgs a) {
-    __shared__ float As[TM * AP];
-    __shared__ float Ws[KC * NS * 16];            // [g][column][4 K values]
     constexpr int NC = NS * 16;
-    constexpr int WIT = (KC * NC + 255) / 256;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * TM, n0 = blockIdx.y * NC;
 
-    // this thread stages K value (tid & 15) of the pixels (tid >> 4) + 16 i
+    // staged pixel (tid >> 4) + 16 i: its row of x, or (GATHER) pixel (2i, 2j) of the large grid; -1 beyond M
     long long src[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = m0 + (tid >> 4) + 16 * i;
         src[i] = m >= a.M ? -1 : (MODE == GATHER ? up_base(m, a.H, a.W) : (long long)m);
     }
+    const long long ldx = a.K;                    // 64-bit here, once: widened inside the loader's condition it costs 4 instructions per load
     f32x4 acc[NS];
+    row_gemm_chunks<NS>(
+        a.K, acc,
+        [&](int k, bool ok, float (&v)[4]) {
+            if constexpr (MODE == GATHER) {                // k = tap * Cu + co
+                const int tap = k / a.Cu, co = k - tap * a.Cu;
+                const int off = tap_offset(tap, a.W);
 #pragma unroll
-    for (int ns = 0; ns < NS; ++ns) acc[ns] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    float v[4], wv[WIT];
-    // chunk kc's operand and weight tiles, global -> registers (issued one chunk ahead: in flight during the MFMAs)
-    auto fetch = [&](int kc) {
-        const int k = kc * KC + (tid & 15);
-        if constexpr (MODE == GATHER) {
-            const int tap = k / a.Cu, co = k - tap * a.Cu;
-            const int off = tap_offset(tap, a.W);
+                for (int i = 0; i < 4; ++i) v[i] = (ok && src[i] >= 0) ? a.x[(src[i] + off) * a.Cu + co] : 0.f;
+            } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = (k < a.K && src[i] >= 0) ? a.x[(src[i] + off) * a.Cu + co] : 0.f;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = (k < a.K && src[i] >= 0) ? a.x[src[i] * a.K + k] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < WIT; ++i) {
-            const int u = tid + 256 * i;                   // Ws index: ((g * NC + column) * 4 + s)
-            const int s = u & 3, col = (u >> 2) % NC, gg = (u >> 2) / NC;
-            const int kk = kc * KC + 4 * gg + s, n = n0 + col;
-            float val = 0.f;
-            if (u < KC * NC && kk < a.K && n < a.N) {
-                if constexpr (MODE == PLAIN) {
-                    val = a.w[kk * a.wsk + n * a.wsn];
-                } else if constexpr (MODE == SCATTER) {    // w[ci = kk][co][tap], n = tap * Cu + co
-                    const int tap = n / a.Cu, co = n - tap * a.Cu;
-                    val = a.w[((long long)kk * a.Cu + co) * 4 + tap];
-                } else {                                   // w[ci = n][co][tap], kk = tap * Cu + co
-                    const int tap = kk / a.Cu, co = kk - tap * a.Cu;
-                    val = a.w[((long long)n * a.Cu + co) * 4 + tap];
-                }
+                for (int i = 0; i < 4; ++i) v[i] = (ok && src[i] >= 0) ? a.x[src[i] * ldx + k] : 0.f;
             }
-            wv[i] = val;
-        }
-    };
-    const int nchunks = (a.K + KC - 1) / KC;
-    fetch(0);
-    for (int kc = 0; kc < nchunks; ++kc) {
-        if (kc) __syncthreads();                  // the previous chunk's fragments have been read
-#pragma unroll
-        for (int i = 0; i < 4; ++i) As[((tid >> 4) + 16 * i) * AP + (tid & 15)] = v[i];
-#pragma unroll
-        for (int i = 0; i < WIT; ++i) {
-            const int u = tid + 256 * i;
-            if (u < KC * NC) Ws[u] = wv[i];
-        }
-        __syncthreads();
-        if (kc + 1 < nchunks) fetch(kc + 1);
-        const f32x4 af = *reinterpret_cast<const f32x4*>(&As[(16 * w + r) * AP + 4 * g]);
-#pragma unroll
-        for (int ns = 0; ns < NS; ++ns) {
-            const f32x4 bf = *reinterpret_cast<const f32x4*>(&Ws[(g * NC + ns * 16 + r) * 4]);
-            acc[ns] = mfma16_chunk(af, bf, acc[ns]);
-        }
-    }
+        },
+        [&](int kk, int col, bool ok) -> float {
+            const int n = n0 + col;
+            if (!(ok && n < a.N)) return 0.f;
+            if constexpr (MODE == PLAIN) {
+                return a.w[kk * a.wsk + n * a.wsn];
+            } else if constexpr (MODE == SCATTER) {        // w[ci = kk][co][tap], n = tap * Cu + co
+                const int tap = n / a.Cu, co = n - tap * a.Cu;
+                return a.w[((long long)kk * a.Cu + co) * 4 + tap];
+            } else {                                       // w[ci = n][co][tap], kk = tap * Cu + co
+                const int tap = kk / a.Cu, co = kk - tap * a.Cu;
+                return a.w[((long long)n * a.Cu + co) * 4 + tap];
+            }
+        });
 
     // epilogue: lane (r, g) register j holds pixel m0 + 16w + 4g + j, column n0 + 16 ns + r
 #pragma unroll
@@ -221,119 +183,49 @@ int launch_pixel_gemm(const PixArgs& a, hipStream_t s) {
 // ---------------------------------------------------------------- weight and bias gradients
 struct PixWgradArgs {
     const float *x, *dy;      // x [M][Cin];  dy: [M][N] (plain) or [B][2H][2W][Cu] (UP, N = 4 Cu tap-major columns)
-    float* ws;                // [S][cin_pad][ncol_pad]
-    int M, Cin, N, H, W, Cu, ntiles, S, cin_pad, ncol_pad;
+    float* ws;                // [S][k_pad][n_pad]
+    int M, Cin, N, H, W, Cu, ntiles, S, k_pad, n_pad;
 };
 
 template <bool UP>
 __global__ __launch_bounds__(256) void pixel_wgrad_kernel(const PixWgradArgs a) {
-    __shared__ float As[TM * KC];
-    __shared__ float Zs[TM * ZP];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+    const int tid = threadIdx.x;
     const int c = blockIdx.x * KC + (tid & 15);           // input channel this thread stages; channel Cin is the constant 1
     const int col = blockIdx.y * 64 + (tid & 63);         // dy column this thread stages
     const int tap = UP ? col / a.Cu : 0, co = UP ? col - tap * a.Cu : col;
     const int toff = UP ? tap_offset(tap, a.W) : 0;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    float v[4], zv[16];
-    // tile t's input channels and dy columns, global -> registers (issued one tile ahead)
-    auto fetch = [&](int t) {
-        const int m0 = t * TM;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + (tid >> 4) + 16 * i;
-            v[i] = m < a.M ? (c < a.Cin ? a.x[(long long)m * a.Cin + c] : (c == a.Cin ? 1.f : 0.f)) : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int m = m0 + (tid >> 6) + 4 * i;
-            float z = 0.f;
-            if (m < a.M && col < a.N) {
-                if constexpr (UP) z = a.dy[(up_base(m, a.H, a.W) + toff) * a.Cu + co];
-                else z = a.dy[(long long)m * a.N + col];
-            }
-            zv[i] = z;
-        }
-    };
-    if ((int)blockIdx.z < a.ntiles) fetch(blockIdx.z);
-    for (int t = blockIdx.z; t < a.ntiles; t += a.S) {
-        __syncthreads();                          // the previous tile has been consumed
-#pragma unroll
-        for (int i = 0; i < 4; ++i) As[((tid >> 4) + 16 * i) * KC + (tid & 15)] = v[i];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) Zs[((tid >> 6) + 4 * i) * ZP + (tid & 63)] = zv[i];
-        __syncthreads();
-        if (t + a.S < a.ntiles) fetch(t + a.S);
-#pragma unroll 4
-        for (int i = 0; i < TM / 4; ++i) {
-            const int m = 4 * i + g;
-            acc = mfma16(As[m * KC + r], Zs[m * ZP + 16 * w + r], acc);
-        }
-    }
-    // lane (r, g) register j: input channel 4g + j of the block, column 16w + r of the block
-    float* dst = a.ws + (long long)blockIdx.z * a.cin_pad * a.ncol_pad;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        dst[(long long)(blockIdx.x * KC + 4 * g + j) * a.ncol_pad + blockIdx.y * 64 + 16 * w + r] = acc[j];
+    row_wgrad_tiles(
+        a.ws, a.ntiles, a.S, a.k_pad, a.n_pad,
+        [&](int m) -> float { return m < a.M ? (c < a.Cin ? a.x[(long long)m * a.Cin + c] : (c == a.Cin ? 1.f : 0.f)) : 0.f; },
+        [&](int m) -> float {
+            if (m >= a.M || col >= a.N) return 0.f;
+            if constexpr (UP) return a.dy[(up_base(m, a.H, a.W) + toff) * a.Cu + co];
+            else return a.dy[(long long)m * a.N + col];
+        });
 }
 
-// plain: gw[co][ci] += sum_s ws[s][ci][co],  gb[co] += sum_s ws[s][Cin][co]
-// UP:    gw[ci][co][tap] += sum_s ws[s][ci][tap * Cu + co],  gb[co] += sum_tap sum_s ws[s][Cin][tap * Cu + co]
-template <bool UP>
-__global__ __launch_bounds__(256) void pixel_wgrad_fold_kernel(const float* __restrict__ ws, float* gw, float* gb, int Cin, int N,
-                                                               int Cu, int S, int cin_pad, int ncol_pad) {
+// The up-convolution's fold (the plain one is row_wgrad_fold_kernel): N = 4 Cu tap-major columns into the parameter's own layout,
+// gw[ci][co][tap] += sum_s ws[s][ci][tap * Cu + co],  gb[co] += sum_tap sum_s ws[s][Cin][tap * Cu + co]
+__global__ __launch_bounds__(256) void upconv_wgrad_fold_kernel(const float* __restrict__ ws, float* gw, float* gb, int Cin, int N, int S,
+                                                                int k_pad, int n_pad) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;      // (ci <= Cin, column), column fastest
     if (e >= (long long)(Cin + 1) * N) return;
-    const int col = (int)(e % N), ci = (int)(e / N);
-    const long long stride = (long long)cin_pad * ncol_pad;
+    const int col = (int)(e % N), ci = (int)(e / N), Cu = N / 4;
+    const long long stride = (long long)k_pad * n_pad;
     if (ci < Cin) {
-        const float* p = ws + (long long)ci * ncol_pad + col;
+        const float* p = ws + (long long)ci * n_pad + col;
         float s = 0.f;
         for (int i = 0; i < S; ++i) s += p[i * stride];
-        if constexpr (UP) {
-            const int tap = col / Cu, co = col - tap * Cu;
-            gw[((long long)ci * Cu + co) * 4 + tap] += s;
-        } else {
-            gw[(long long)col * Cin + ci] += s;
-        }
-    } else if (gb && col < (UP ? Cu : N)) {
+        const int tap = col / Cu, co = col - tap * Cu;
+        gw[((long long)ci * Cu + co) * 4 + tap] += s;
+    } else if (gb && col < Cu) {
         float s = 0.f;
-        for (int tap = 0; tap < (UP ? 4 : 1); ++tap) {
-            const float* p = ws + (long long)Cin * ncol_pad + tap * Cu + col;
+        for (int tap = 0; tap < 4; ++tap) {
+            const float* p = ws + (long long)Cin * n_pad + tap * Cu + col;
             for (int i = 0; i < S; ++i) s += p[i * stride];
         }
         gb[col] += s;
     }
-}
-
-inline void pixel_wgrad_geometry(long long M, int Cin, int N, int* cin_pad, int* ncol_pad, int* ntiles, int* S) {
-    *cin_pad = round_up(Cin + 1, KC);
-    *ncol_pad = round_up(N, 64);
-    *ntiles = (int)((M + TM - 1) / TM);
-    const int blocks = (*cin_pad / KC) * (*ncol_pad / 64);
-    int s = ceil_div(512, blocks);
-    if (s > 32) s = 32;
-    if (s > *ntiles) s = *ntiles;
-    *S = s;
-}
-
-template <bool UP>
-int launch_pixel_wgrad(PixWgradArgs& a, float* gw, float* gb, hipStream_t s) {
-    pixel_wgrad_geometry(a.M, a.Cin, a.N, &a.cin_pad, &a.ncol_pad, &a.ntiles, &a.S);
-    {
-        dlwp_prof_scope ps(s, 2.0 * a.M * (a.Cin + 1.0) * a.N, 4.0 * ((double)a.M * (a.Cin + a.N) + (double)a.S * a.cin_pad * a.ncol_pad),
-                           "pixel_wgrad");
-        hipLaunchKernelGGL((pixel_wgrad_kernel<UP>), dim3(a.cin_pad / KC, a.ncol_pad / 64, a.S), dim3(256), 0, s, a);
-        DLWP_LAUNCH_CHECK();
-    }
-    {
-        const long long n = (long long)(a.Cin + 1) * a.N;
-        dlwp_prof_scope ps(s, (double)a.S * n, 4.0 * (a.S + 2.0) * n, "pixel_wgrad_fold");
-        hipLaunchKernelGGL((pixel_wgrad_fold_kernel<UP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.ws, gw, gb, a.Cin, a.N,
-                           a.Cu, a.S, a.cin_pad, a.ncol_pad);
-        DLWP_LAUNCH_CHECK();
-    }
-    return DLWP_OK;
 }
 
 constexpr long long PIX_LIMIT = 1ll << 31;
@@ -434,9 +326,7 @@ extern "C" long long dlwp_conv1x1_wgrad_ws_floats(long long npix, int Cin, int C
         dlwp_set_error("conv1x1_wgrad_ws_floats: bad shape (%lld pixels, Cin %d, Cout %d)", npix, Cin, Cout);
         return DLWP_E_INVALID;
     }
-    int cin_pad, ncol_pad, ntiles, S;
-    pixel_wgrad_geometry(npix, Cin, Cout, &cin_pad, &ncol_pad, &ntiles, &S);
-    return (long long)S * cin_pad * ncol_pad;
+    return row_wgrad_ws_floats(npix, Cin, Cout);
 }
 
 extern "C" long long dlwp_upconv2x2_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout) {
@@ -444,9 +334,7 @@ extern "C" long long dlwp_upconv2x2_wgrad_ws_floats(int B, int H, int W, int Cin
         dlwp_set_error("upconv2x2_wgrad_ws_floats: bad shape (B %d, H %d, W %d, Cin %d, Cout %d)", B, H, W, Cin, Cout);
         return DLWP_E_INVALID;
     }
-    int cin_pad, ncol_pad, ntiles, S;
-    pixel_wgrad_geometry((long long)B * H * W, Cin, 4 * Cout, &cin_pad, &ncol_pad, &ntiles, &S);
-    return (long long)S * cin_pad * ncol_pad;
+    return row_wgrad_ws_floats((long long)B * H * W, Cin, 4 * Cout);
 }
 
 extern "C" int dlwp_conv1x1_wgrad(const float* x, const float* dy, float* ws, float* gw, float* gb, long long npix, int Cin, int Cout,
@@ -455,7 +343,7 @@ extern "C" int dlwp_conv1x1_wgrad(const float* x, const float* dy, float* ws, fl
     CONV1X1_SHAPE("conv1x1_wgrad");
     PixWgradArgs a{};
     a.x = x; a.dy = dy; a.ws = ws; a.M = (int)npix; a.Cin = Cin; a.N = Cout; a.Cu = Cout;
-    return launch_pixel_wgrad<false>(a, gw, gb, (hipStream_t)stream_);
+    return launch_row_wgrad(pixel_wgrad_kernel<false>, a, a.M, Cin, a.N, gw, gb, (hipStream_t)stream_, "pixel_wgrad", "pixel_wgrad_fold");
 }
 
 extern "C" int dlwp_upconv2x2_wgrad(const float* x, const float* dy, float* ws, float* gw, float* gb, int B, int H, int W, int Cin,
@@ -464,5 +352,6 @@ extern "C" int dlwp_upconv2x2_wgrad(const float* x, const float* dy, float* ws, 
     UPCONV_SHAPE("upconv2x2_wgrad");
     PixWgradArgs a{};
     a.x = x; a.dy = dy; a.ws = ws; a.M = B * H * W; a.Cin = Cin; a.N = 4 * Cout; a.H = H; a.W = W; a.Cu = Cout;
-    return launch_pixel_wgrad<true>(a, gw, gb, (hipStream_t)stream_);
+    return launch_row_wgrad(pixel_wgrad_kernel<true>, a, a.M, Cin, a.N, gw, gb, (hipStream_t)stream_, "pixel_wgrad", "pixel_wgrad_fold",
+                            upconv_wgrad_fold_kernel);
 }

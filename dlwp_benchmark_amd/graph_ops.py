@@ -16,7 +16,8 @@ import torch
 
 from . import lib as L
 from . import mgn_graph
-from .token_ops import _grad_slot
+from .conv_ops import ACT
+from .token_ops import _grad_buffer, _grad_slot
 
 ROWS, EDGE, NODE = L.GRAPH_ROWS, L.GRAPH_EDGE, L.GRAPH_NODE
 AGGREGATIONS = ("sum", "mean")
@@ -90,11 +91,6 @@ def _check_params(what, params, norm, k0):
     if norm is not None and (len(norm) != 2 or any(tuple(t.shape) != (out,) for t in norm)):
         raise L.DlwpError(f"{what}: norm is (gamma, beta) of shape ({out},)")
     return nl, hidden, out
-
-
-def _param_grads(slots, grads, needs):
-    """what backward returns for the parameters: None where the kernel added into the slot (or no gradient is needed)"""
-    return tuple(None if (s is not None or not n) else g for s, g, n in zip(slots, grads, needs))
 
 
 class _GraphMlpFn(torch.autograd.Function):
@@ -171,42 +167,32 @@ class _GraphMlpFn(torch.autograd.Function):
         need = ctx.needs_input_grad            # mode, graph, mean, residual, grad, x, v, gamma, beta, *params
         k0 = ws[0].shape[1]
 
-        def buf(slot, shape):
-            return slot if slot is not None else torch.zeros(shape, device=dev)
-
-        # LayerNorm
-        ggamma = gbeta = None
+        # LayerNorm (buffers and returned gradients of gamma, beta)
+        gnorm, gnorm_out = (None, None), (None, None)
         dz = gy
         if gamma is not None:
-            ggamma, gbeta = buf(ctx.norm_slots[0], (out,)), buf(ctx.norm_slots[1], (out,))
-            n = lib.dlwp_graph_ln_bwd_ws_floats(rows, out)
-            if n < 0:
-                L.check(int(n))
+            gnorm, gnorm_out = zip(*(_grad_buffer(sl, (out,), dev, n) for sl, n in zip(ctx.norm_slots, need[7:9])))
+            scratch = L.workspace(lib.dlwp_graph_ln_bwd_ws_floats, rows, out, device=dev)
             dz = torch.empty(rows, out, device=dev)
             L.check(lib.dlwp_graph_ln_bwd(L.ptr(gy), L.ptr(xhat), L.ptr(rstd), L.ptr(gamma.detach().contiguous()), L.ptr(dz),
-                                          L.ptr(torch.empty(n, device=dev)), L.ptr(ggamma), L.ptr(gbeta), rows, out, s))
+                                          L.ptr(scratch), L.ptr(gnorm[0]), L.ptr(gnorm[1]), rows, out, s))
         # the Linears on stored rows, last to second: the 1 x 1 convolution's kernels (a Linear IS one on [rows] pixels)
-        pgrads = [buf(sl, sh) for sl, sh in zip(ctx.slots, ctx.shapes)]
+        pgrads, pgrads_out = zip(*(_grad_buffer(sl, sh, dev, n) for sl, sh, n in zip(ctx.slots, ctx.shapes, need[9:])))
         for i in range(nl, 0, -1):
             cout = out if i == nl else hidden
-            n = lib.dlwp_conv1x1_wgrad_ws_floats(rows, hidden, cout)
-            if n < 0:
-                L.check(int(n))
-            L.check(lib.dlwp_conv1x1_wgrad(L.ptr(hid[i - 1]), L.ptr(dz), L.ptr(torch.empty(n, device=dev)), L.ptr(pgrads[2 * i]),
-                                           L.ptr(pgrads[2 * i + 1]), rows, hidden, cout, s))
+            scratch = L.workspace(lib.dlwp_conv1x1_wgrad_ws_floats, rows, hidden, cout, device=dev)
+            L.check(lib.dlwp_conv1x1_wgrad(L.ptr(hid[i - 1]), L.ptr(dz), L.ptr(scratch), L.ptr(pgrads[2 * i]), L.ptr(pgrads[2 * i + 1]),
+                                           rows, hidden, cout, s))
             dh = torch.empty(rows, hidden, device=dev)
             L.check(lib.dlwp_conv1x1_dgrad(L.ptr(dz), L.ptr(ws[i]), L.ptr(dh), rows, hidden, cout, s))
             dz = torch.empty(rows, hidden, device=dev)
-            L.check(lib.dlwp_conv3x3_act_bwd(L.ptr(hid[i - 1]), L.ptr(dh), L.ptr(dz), dh.numel(), 2, s))
+            L.check(lib.dlwp_conv3x3_act_bwd(L.ptr(hid[i - 1]), L.ptr(dh), L.ptr(dz), dh.numel(), ACT["relu"], s))
         # the first Linear: its operand is gathered again, its input gradient leaves in parts
         src = L.ptr(graph.src) if mode == EDGE else None
         dst = L.ptr(graph.dst) if mode == EDGE else None
-        n = lib.dlwp_graph_wgrad0_ws_floats(rows, k0, hidden)
-        if n < 0:
-            L.check(int(n))
-        L.check(lib.dlwp_graph_wgrad0(mode, L.ptr(agg if mode == NODE else x), L.ptr(v), src, dst, L.ptr(dz),
-                                      L.ptr(torch.empty(n, device=dev)), L.ptr(pgrads[0]), L.ptr(pgrads[1]), B, N, E, rows, De, Dv,
-                                      hidden, s))
+        scratch = L.workspace(lib.dlwp_graph_wgrad0_ws_floats, rows, k0, hidden, device=dev)
+        L.check(lib.dlwp_graph_wgrad0(mode, L.ptr(agg if mode == NODE else x), L.ptr(v), src, dst, L.ptr(dz), L.ptr(scratch),
+                                      L.ptr(pgrads[0]), L.ptr(pgrads[1]), B, N, E, rows, De, Dv, hidden, s))
         gx = gv = None
         res = L.ptr(gy) if residual else None
         if mode == ROWS:
@@ -234,8 +220,7 @@ class _GraphMlpFn(torch.autograd.Function):
                 gx = torch.empty_like(x)
                 L.check(lib.dlwp_graph_edge_gather(L.ptr(dagg), L.ptr(graph.dst), L.ptr(graph.in_ptr) if mean else None, None,
                                                    L.ptr(gx), B, N, E, De, s))
-        gnorm = _param_grads(ctx.norm_slots, (ggamma, gbeta), need[7:9])
-        return (None, None, None, None, None, gx, gv) + gnorm + _param_grads(ctx.slots, pgrads, need[9:])
+        return (None, None, None, None, None, gx, gv) + tuple(gnorm_out) + tuple(pgrads_out)
 
 
 def _norm_pair(norm):

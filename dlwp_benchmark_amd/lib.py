@@ -281,6 +281,15 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def workspace(size_fn, *shape, device):
+    """The uninitialised fp32 scratch of an entry point whose size a `dlwp_*_floats(*shape)` entry gives (negative: its error)."""
+    import torch
+    n = size_fn(*shape)
+    if n < 0:
+        check(int(n))
+    return torch.empty(n, device=device)
+
+
 class gemm_precision:
     """Context manager / setter for the GEMM operand precision: "fp32" (default, exact fp32 MFMA) or "bf16"
     (bf16 operands, fp32 accumulation: the reference's bf16-autocast arithmetic)."""

@@ -130,6 +130,15 @@ def _grad_slot(p):
     return None
 
 
+def _grad_buffer(slot, shape, device, needed=True):
+    """(the buffer a backward kernel adds INTO, what backward returns for it): the slot and None where there is one, else fresh
+    zeros, which are also the returned gradient (None when none is needed)."""
+    if slot is not None:
+        return slot, None
+    g = torch.zeros(shape, device=device)
+    return g, (g if needed else None)
+
+
 def _dptr(t, offset=0):
     """Device pointer of `t` advanced by `offset` elements (views into bigger buffers are passed as base + offset)."""
     return None if t is None else L.ptr(t) + t.element_size() * offset

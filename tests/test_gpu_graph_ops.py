@@ -216,6 +216,9 @@ SHAPES = [
     (128, 128, 128, 3, 3, True, True, True, "hand"),
     (6, 4, 1, 1, 3, False, False, False, "grid"),
     (32, 32, 32, 2, 3, True, False, True, "grid"),
+    # edge mode: 707 rows = 12 row tiles (the last with 3 rows) for S = 11 splits of the first Linear's weight gradient
+    # (K0 = 384: 25 x 2 blocks), so a workgroup walks two tiles and prefetches tile t + S; in every other case S is the tile count
+    (128, 128, 128, 1, 7, True, False, True, "hand"),
 ]
 
 

@@ -23,9 +23,11 @@ from test_gpu_conv_ops import Out, bits, check, cl
 pytestmark = pytest.mark.gpu
 
 POOL_SHAPES = [(1, 2, 2, 1), (3, 4, 8, 5), (1, 6, 10, 8), (1, 34, 46, 13), (2, 16, 16, 64)]
-# (B, H, W, Cin, Cout): H, W the up-convolution's INPUT grid; the 1 x 1 convolution runs on npix = B H W
+# (B, H, W, Cin, Cout): H, W the up-convolution's INPUT grid; the 1 x 1 convolution runs on npix = B H W.  The last shape has
+# 12 pixel tiles for fewer weight-gradient splits (1 x 1: 17 x 3 blocks, S = 11; up-convolution: 17 x 9 blocks, S = 4), so a
+# workgroup walks more than one tile and prefetches tile t + S; in every other shape S is the tile count
 GEMM_SHAPES = [(1, 1, 1, 1, 1), (3, 2, 4, 5, 3), (1, 3, 5, 16, 8), (1, 4, 8, 13, 57), (2, 8, 16, 64, 32), (1, 5, 7, 57, 1),
-               (1, 8, 8, 264, 132), (1, 4, 4, 528, 264)]
+               (1, 8, 8, 264, 132), (1, 4, 4, 528, 264), (1, 16, 48, 264, 132)]
 
 
 def sentinels(outs):
