@@ -20,9 +20,13 @@
 // beyond K and N (nothing in memory is padded).  The chunk loop is row_gemm.hip.h's (row_gemm_chunks) in a copy of this kernel's
 // own: its barrier at the top of a chunk also hands Hs from one layer to the next, and from the second layer on the A fragment
 // comes from Hs.
-// When a backward pass follows the launch also stores the post-ReLU hidden rows, the normalised rows, 1/sigma and (NODE) agg.
+// When a backward pass follows the launch also stores the post-activation hidden rows, the normalised rows, 1/sigma and (NODE) agg.
+// The activation is a template parameter: ReLU, or SiLU (GraphCast: activation_fn of MeshGraphMLP, graph_cast_net_ns.py:208-246),
+// v s with s = 1 / (1 + exp(-v)).  SiLU is not monotone, so its derivative cannot be taken from the stored v s as ReLU's mask is:
+// the launch stores d = s (1 + v (1 - s)) as well, and the backward of a later Linear is ONE launch,
+// dz_{l-1} = (dz_l . W_l) * d_{l-1} (graph_dgrad0_kernel<ROWS, true>, dlwp_graph_dgrad_mul).
 //
-// Backward of the FIRST Linear (the others are Linears on stored rows: dlwp_conv1x1_dgrad / _wgrad):
+// Backward of the FIRST Linear (the others are Linears on stored rows: dlwp_conv1x1_dgrad / _wgrad, ReLU; dlwp_graph_dgrad_mul, SiLU):
 // * graph_wgrad0_kernel: gW0 = dz0^T . A with A gathered again exactly as in the forward (NODE reads the stored agg), on
 //   row_gemm.hip.h's split-K tile walk and fold (row_wgrad_tiles: INTO gw [hidden][K0] and gb; the bias rides along as operand
 //   column K0 = 1);
@@ -43,6 +47,7 @@ constexpr int MAXL = DLWP_GRAPH_MAX_HIDDEN_LAYERS;
 constexpr long long ROW_LIMIT = (1ll << 31) - 64;      // the kernels form row indices of a whole last 64-row tile in int
 
 enum { ROWS = DLWP_GRAPH_ROWS, EDGE = DLWP_GRAPH_EDGE, NODE = DLWP_GRAPH_NODE };
+enum { RELU = DLWP_GRAPH_ACT_RELU, SILU = DLWP_GRAPH_ACT_SILU };
 
 struct MlpArgs {
     const float *x, *v;
@@ -55,6 +60,7 @@ struct MlpArgs {
     float *xhat, *rstd, *agg;
     int R, N, E, De, Dv, K0, hidden, out, L, residual, mean;
     float eps;
+    float* der[MAXL];         // SiLU: the derivative rows (behind the fields the ReLU kernels read: their offsets stay)
 };
 
 // where the operand row of row m comes from (one per staged row and thread)
@@ -102,7 +108,15 @@ __device__ __forceinline__ float operand_fwd(const RowSrc& s, int k, const float
     }
 }
 
-template <int MODE, int NS>
+// SiLU v s and its derivative s (1 + v (1 - s)), s = 1 / (1 + exp(-v)).  Far out exp(-v) is inf or 0, so s is exactly 0 or 1 and the
+// pair is (-0, -0) or (v, 1): the division is IEEE's (1 / inf = 0), and no inf meets an inf or a zero
+__device__ __forceinline__ float silu(float v, float& d) {
+    const float s = 1.0f / (1.0f + __expf(-v));
+    d = s * (1.0f + v * (1.0f - s));
+    return v * s;
+}
+
+template <int MODE, int NS, int ACT>
 __global__ __launch_bounds__(256) void graph_mlp_kernel(const MlpArgs a) {
     constexpr int NC = NS * 16;
     constexpr int HP = NC + 4;
@@ -183,8 +197,17 @@ __global__ __launch_bounds__(256) void graph_mlp_kernel(const MlpArgs a) {
                 if (n < Nl) {
                     val = acc[ns][j] + (bl ? bl[n] : 0.f);
                     if (l < a.L) {
-                        val = fmaxf(val, 0.f);
-                        if (a.hid[l] && m < a.R) a.hid[l][(long long)m * a.hidden + n] = val;
+                        if constexpr (ACT == RELU) {
+                            val = fmaxf(val, 0.f);
+                            if (a.hid[l] && m < a.R) a.hid[l][(long long)m * a.hidden + n] = val;
+                        } else {
+                            float d;
+                            val = silu(val, d);
+                            if (m < a.R) {
+                                if (a.hid[l]) a.hid[l][(long long)m * a.hidden + n] = val;
+                                if (a.der[l]) a.der[l][(long long)m * a.hidden + n] = d;
+                            }
+                        }
                     }
                 }
                 Hs[row * HP + n] = val;
@@ -227,13 +250,13 @@ __global__ __launch_bounds__(256) void graph_mlp_kernel(const MlpArgs a) {
     if (a.gamma && a.rstd && lane < 16 && m0 + 16 * w + lane < a.R) a.rstd[m0 + 16 * w + lane] = Rs[16 * w + lane];
 }
 
-template <int MODE>
+template <int MODE, int ACT>
 int launch_mlp(const MlpArgs& a, hipStream_t s) {
     const dim3 grid(ceil_div(a.R, TM)), block(256);
     const int wmax = a.hidden > a.out ? a.hidden : a.out;
-    if (wmax <= 32) hipLaunchKernelGGL((graph_mlp_kernel<MODE, 2>), grid, block, 0, s, a);
-    else if (wmax <= 64) hipLaunchKernelGGL((graph_mlp_kernel<MODE, 4>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((graph_mlp_kernel<MODE, 8>), grid, block, 0, s, a);
+    if (wmax <= 32) hipLaunchKernelGGL((graph_mlp_kernel<MODE, 2, ACT>), grid, block, 0, s, a);
+    else if (wmax <= 64) hipLaunchKernelGGL((graph_mlp_kernel<MODE, 4, ACT>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((graph_mlp_kernel<MODE, 8, ACT>), grid, block, 0, s, a);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
@@ -248,6 +271,7 @@ struct Grad0Args {
     float *o0, *o1, *o2;      // dgrad outputs (each nullable): EDGE de, d_src, d_dst; NODE d_agg, dv; ROWS dx
     float* ws;                // wgrad: [S][k_pad][n_pad]
     int R, N, E, De, Dv, K0, hidden, ntiles, S, k_pad, n_pad;
+    const float* mul;         // dgrad, ROWS with MUL: [R][K0], multiplied into dx as it is stored (nullable)
 };
 
 // operand element c of row m as the weight gradient reads it: column K0 is the constant 1 (bias), beyond it zero
@@ -278,9 +302,11 @@ __global__ __launch_bounds__(256) void graph_wgrad0_kernel(const Grad0Args a) {
         [&](int m) -> float { return (m < a.R && col < a.hidden) ? a.dz[(long long)m * a.hidden + col] : 0.f; });
 }
 
-// dA[R][K0] = dz[R][hidden] . W0[hidden][K0], one workgroup per (64 rows, 64 columns), stored in parts
-template <int MODE>
+// dA[R][K0] = dz[R][hidden] . W0[hidden][K0], one workgroup per (64 rows, 64 columns), stored in parts.  MUL (ROWS only): dx times
+// a.mul element by element -- a later Linear's input gradient times the stored derivative of the activation in front of it
+template <int MODE, bool MUL = false>
 __global__ __launch_bounds__(256) void graph_dgrad0_kernel(const Grad0Args a) {
+    static_assert(!MUL || MODE == ROWS, "the multiplier has the layout of dx");
     constexpr int NS = 4, NC = 64;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
     const int m0 = blockIdx.x * TM, n0 = blockIdx.y * NC;
@@ -308,7 +334,9 @@ __global__ __launch_bounds__(256) void graph_dgrad0_kernel(const Grad0Args a) {
             const int n = n0 + ns * 16 + r;
             if (n >= a.K0) continue;
             const float val = acc[ns][j];
-            if constexpr (MODE == ROWS) {
+            if constexpr (MODE == ROWS && MUL) {
+                a.o0[m * a.K0 + n] = a.mul ? val * a.mul[m * a.K0 + n] : val;
+            } else if constexpr (MODE == ROWS) {
                 if (a.o0) a.o0[m * a.K0 + n] = val;
             } else if constexpr (MODE == EDGE) {
                 if (n < a.De) {
@@ -473,6 +501,10 @@ extern "C" int dlwp_graph_mlp_fwd(const dlwp_graph_mlp_args* p, void* stream_) {
     DLWP_REQUIRE(p->mode != NODE || (p->in_ptr && p->in_eid), DLWP_E_INVALID, "graph_mlp_fwd: NULL argument (in_ptr or in_eid)");
     for (int l = 0; l <= p->hidden_layers; ++l) DLWP_REQUIRE(p->w[l], DLWP_E_INVALID, "graph_mlp_fwd: NULL argument (weight %d)", l);
     DLWP_REQUIRE((p->gamma == nullptr) == (p->beta == nullptr), DLWP_E_INVALID, "graph_mlp_fwd: gamma and beta go together");
+    DLWP_REQUIRE(p->act == RELU || p->act == SILU, DLWP_E_INVALID, "graph_mlp_fwd: act %d is neither relu (0) nor silu (1)", p->act);
+    for (int l = 0; l < MAXL; ++l)
+        DLWP_REQUIRE(!p->der[l] || (p->act == SILU && l < p->hidden_layers), DLWP_E_INVALID,
+                     "graph_mlp_fwd: derivative rows %d given, but they are stored for the hidden layers of a silu chain only", l);
     if (p->residual) {
         DLWP_REQUIRE(p->mode != ROWS, DLWP_E_INVALID, "graph_mlp_fwd: a residual needs the edge or the node mode");
         DLWP_REQUIRE(p->out == (p->mode == EDGE ? p->De : p->Dv), DLWP_E_INVALID,
@@ -481,7 +513,7 @@ extern "C" int dlwp_graph_mlp_fwd(const dlwp_graph_mlp_args* p, void* stream_) {
     MlpArgs a{};
     a.x = p->x; a.v = p->v; a.src = p->src; a.dst = p->dst; a.in_ptr = p->in_ptr; a.in_eid = p->in_eid;
     for (int l = 0; l <= p->hidden_layers; ++l) { a.w[l] = p->w[l]; a.b[l] = p->b[l]; }
-    for (int l = 0; l < p->hidden_layers; ++l) a.hid[l] = p->hid[l];
+    for (int l = 0; l < p->hidden_layers; ++l) { a.hid[l] = p->hid[l]; a.der[l] = p->der[l]; }
     a.gamma = p->gamma; a.beta = p->beta; a.eps = p->eps; a.y = p->y;
     a.xhat = p->xhat; a.rstd = p->rstd; a.agg = p->mode == NODE ? p->agg : nullptr;
     a.R = (int)rows; a.N = p->N; a.E = p->E; a.De = p->De; a.Dv = p->Dv; a.K0 = K0; a.hidden = p->hidden; a.out = p->out;
@@ -490,11 +522,17 @@ extern "C" int dlwp_graph_mlp_fwd(const dlwp_graph_mlp_args* p, void* stream_) {
     const double macs = (double)K0 * a.hidden + (a.L - 1.0) * a.hidden * a.hidden + (double)a.hidden * a.out;
     double bytes = 4.0 * rows * ((double)K0 + a.out + (a.residual ? a.out : 0)) + 4.0 * macs;
     if (a.hid[0]) bytes += 4.0 * rows * a.L * a.hidden;
+    if (a.der[0]) bytes += 4.0 * rows * a.L * a.hidden;
     if (a.xhat) bytes += 4.0 * rows * a.out;
     dlwp_prof_scope ps(s, 2.0 * rows * macs, bytes, "graph_mlp_%s", mode_name(p->mode));
-    if (p->mode == ROWS) return launch_mlp<ROWS>(a, s);
-    if (p->mode == EDGE) return launch_mlp<EDGE>(a, s);
-    return launch_mlp<NODE>(a, s);
+    if (p->act == SILU) {
+        if (p->mode == ROWS) return launch_mlp<ROWS, SILU>(a, s);
+        if (p->mode == EDGE) return launch_mlp<EDGE, SILU>(a, s);
+        return launch_mlp<NODE, SILU>(a, s);
+    }
+    if (p->mode == ROWS) return launch_mlp<ROWS, RELU>(a, s);
+    if (p->mode == EDGE) return launch_mlp<EDGE, RELU>(a, s);
+    return launch_mlp<NODE, RELU>(a, s);
 }
 
 #define GRAD0_PROLOGUE(name)                                                                                                       \
@@ -543,6 +581,24 @@ extern "C" int dlwp_graph_dgrad0(int mode, const float* dz, const float* w, cons
     if (mode == ROWS) hipLaunchKernelGGL(graph_dgrad0_kernel<ROWS>, grid, block, 0, s, a);
     else if (mode == EDGE) hipLaunchKernelGGL(graph_dgrad0_kernel<EDGE>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(graph_dgrad0_kernel<NODE>, grid, block, 0, s, a);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+extern "C" int dlwp_graph_dgrad_mul(const float* dz, const float* w, const float* mul, float* out, long long rows, int in, int out_width,
+                                    void* stream_) {
+    DLWP_REQUIRE(dz && w && out, DLWP_E_INVALID, "graph_dgrad_mul: NULL argument");
+    DLWP_REQUIRE(rows > 0, DLWP_E_INVALID, "graph_dgrad_mul: bad shape (%lld rows)", rows);
+    DLWP_REQUIRE(rows < ROW_LIMIT, DLWP_E_UNSUPPORTED, "graph_dgrad_mul: more than 2^31 - 64 rows");
+    DLWP_REQUIRE(width_ok(in) && width_ok(out_width), DLWP_E_UNSUPPORTED, "graph_dgrad_mul: width (input %d, output %d) outside 1..%d", in,
+                 out_width, MAXW);
+    Grad0Args a{};
+    a.dz = dz; a.w = w; a.mul = mul; a.o0 = out;
+    a.R = (int)rows; a.K0 = in; a.hidden = out_width;
+    hipStream_t s = (hipStream_t)stream_;
+    dlwp_prof_scope ps(s, 2.0 * rows * in * out_width,
+                       4.0 * ((double)rows * ((mul ? 2.0 : 1.0) * in + out_width) + (double)in * out_width), "graph_dgrad_mul");
+    hipLaunchKernelGGL((graph_dgrad0_kernel<ROWS, true>), dim3(ceil_div((int)rows, TM), ceil_div(in, 64)), dim3(256), 0, s, a);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }

@@ -8,6 +8,10 @@ themselves, so the arrays do not grow with the batch and never change under grap
 (`params = [w0, b0, w1, b1, ..., wL, bL]`, `norm = (gamma, beta)` or None); their gradients are accumulated into the preallocated
 gradient buffers where those exist.  Under `torch.no_grad()` nothing is stored for a backward pass.  fp32 only; there is no CPU
 or torch fallback.
+
+The hidden layers' activation is ReLU (MeshGraphNet) or SiLU (GraphCast).  ReLU's backward takes its mask from the stored
+post-ReLU rows.  SiLU is not monotone, so its derivative cannot be read off `z sigmoid(z)`: the forward launch also stores the
+derivative rows, and the backward of a later Linear is ONE launch, `dz_{l-1} = (dz_l . W_l) * d_{l-1}` (dlwp_graph_dgrad_mul).
 """
 import ctypes as C
 
@@ -21,6 +25,7 @@ from .token_ops import _grad_buffer, _grad_slot
 
 ROWS, EDGE, NODE = L.GRAPH_ROWS, L.GRAPH_EDGE, L.GRAPH_NODE
 AGGREGATIONS = ("sum", "mean")
+ACTIVATIONS = tuple(L.GRAPH_ACT)      # "relu", "silu"
 EPS = 1e-5      # nn.LayerNorm's default, which the reference's MeshGraphMLP uses
 
 
@@ -97,7 +102,7 @@ class _GraphMlpFn(torch.autograd.Function):
     """One fused launch forward (all three modes); backward as described in csrc/graph_ops.hip."""
 
     @staticmethod
-    def forward(ctx, mode, graph, mean, residual, grad, x, v, gamma, beta, *params):
+    def forward(ctx, mode, graph, mean, residual, grad, act, x, v, gamma, beta, *params):
         lib = L.load()
         what = ("graph_mlp", "edge_block", "node_block")[mode]
         x = _rows(x, what)
@@ -126,6 +131,7 @@ class _GraphMlpFn(torch.autograd.Function):
         keep = grad and any(ctx.needs_input_grad)
         y = torch.empty(rows, out, device=dev)
         hid = [torch.empty(rows, hidden, device=dev) for _ in range(nl)] if keep else []
+        der = [torch.empty(rows, hidden, device=dev) for _ in range(nl)] if keep and act == L.GRAPH_ACT["silu"] else []
         xhat = torch.empty(rows, out, device=dev) if keep and norm is not None else None
         rstd = torch.empty(rows, device=dev) if keep and norm is not None else None
         agg = torch.empty(rows, De, device=dev) if keep and mode == NODE else None
@@ -142,13 +148,16 @@ class _GraphMlpFn(torch.autograd.Function):
             a.w[i], a.b[i] = L.ptr(ws[2 * i]), L.ptr(ws[2 * i + 1])
         for i, h in enumerate(hid):
             a.hid[i] = L.ptr(h)
+        a.act = act
+        for i, d in enumerate(der):
+            a.der[i] = L.ptr(d)
         if norm is not None:
             a.gamma, a.beta = L.ptr(gamma.detach().contiguous()), L.ptr(beta.detach().contiguous())
         a.y, a.xhat, a.rstd, a.agg = L.ptr(y), L.ptr(xhat), L.ptr(rstd), L.ptr(agg)
         L.check(lib.dlwp_graph_mlp_fwd(C.byref(a), L.stream()))
         if keep:
-            ctx.save_for_backward(x, v, gamma, xhat, rstd, agg, *hid, *ws[0::2])
-            ctx.cfg = (mode, graph, mean, residual, B, N, E, rows, De, Dv, hidden, out, nl)
+            ctx.save_for_backward(x, v, gamma, xhat, rstd, agg, *hid, *ws[0::2], *der)
+            ctx.cfg = (mode, graph, mean, residual, B, N, E, rows, De, Dv, hidden, out, nl, act)
             ctx.slots = [_grad_slot(p) for p in params]
             ctx.norm_slots = (_grad_slot(gamma), _grad_slot(beta)) if norm is not None else (None, None)
             ctx.shapes = [p.shape for p in params]
@@ -157,32 +166,37 @@ class _GraphMlpFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         lib = L.load()
-        mode, graph, mean, residual, B, N, E, rows, De, Dv, hidden, out, nl = ctx.cfg
+        mode, graph, mean, residual, B, N, E, rows, De, Dv, hidden, out, nl, act = ctx.cfg
         saved = ctx.saved_tensors
         x, v, gamma, xhat, rstd, agg = saved[:6]
-        hid, ws = saved[6:6 + nl], saved[6 + nl:]
+        hid, ws, der = saved[6:6 + nl], saved[6 + nl:7 + 2 * nl], saved[7 + 2 * nl:]
         what = ("graph_mlp", "edge_block", "node_block")[mode]
         gy = _rows(gy, what + " backward")
         dev, s = gy.device, L.stream()
-        need = ctx.needs_input_grad            # mode, graph, mean, residual, grad, x, v, gamma, beta, *params
+        need = ctx.needs_input_grad            # mode, graph, mean, residual, grad, act, x, v, gamma, beta, *params
         k0 = ws[0].shape[1]
 
         # LayerNorm (buffers and returned gradients of gamma, beta)
         gnorm, gnorm_out = (None, None), (None, None)
         dz = gy
         if gamma is not None:
-            gnorm, gnorm_out = zip(*(_grad_buffer(sl, (out,), dev, n) for sl, n in zip(ctx.norm_slots, need[7:9])))
+            gnorm, gnorm_out = zip(*(_grad_buffer(sl, (out,), dev, n) for sl, n in zip(ctx.norm_slots, need[8:10])))
             scratch = L.workspace(lib.dlwp_graph_ln_bwd_ws_floats, rows, out, device=dev)
             dz = torch.empty(rows, out, device=dev)
             L.check(lib.dlwp_graph_ln_bwd(L.ptr(gy), L.ptr(xhat), L.ptr(rstd), L.ptr(gamma.detach().contiguous()), L.ptr(dz),
                                           L.ptr(scratch), L.ptr(gnorm[0]), L.ptr(gnorm[1]), rows, out, s))
         # the Linears on stored rows, last to second: the 1 x 1 convolution's kernels (a Linear IS one on [rows] pixels)
-        pgrads, pgrads_out = zip(*(_grad_buffer(sl, sh, dev, n) for sl, sh, n in zip(ctx.slots, ctx.shapes, need[9:])))
+        pgrads, pgrads_out = zip(*(_grad_buffer(sl, sh, dev, n) for sl, sh, n in zip(ctx.slots, ctx.shapes, need[10:])))
         for i in range(nl, 0, -1):
             cout = out if i == nl else hidden
             scratch = L.workspace(lib.dlwp_conv1x1_wgrad_ws_floats, rows, hidden, cout, device=dev)
             L.check(lib.dlwp_conv1x1_wgrad(L.ptr(hid[i - 1]), L.ptr(dz), L.ptr(scratch), L.ptr(pgrads[2 * i]), L.ptr(pgrads[2 * i + 1]),
                                            rows, hidden, cout, s))
+            if der:            # SiLU: the input gradient times the stored derivative, one launch
+                dzp = torch.empty(rows, hidden, device=dev)
+                L.check(lib.dlwp_graph_dgrad_mul(L.ptr(dz), L.ptr(ws[i]), L.ptr(der[i - 1]), L.ptr(dzp), rows, hidden, cout, s))
+                dz = dzp
+                continue
             dh = torch.empty(rows, hidden, device=dev)
             L.check(lib.dlwp_conv1x1_dgrad(L.ptr(dz), L.ptr(ws[i]), L.ptr(dh), rows, hidden, cout, s))
             dz = torch.empty(rows, hidden, device=dev)
@@ -196,58 +210,66 @@ class _GraphMlpFn(torch.autograd.Function):
         gx = gv = None
         res = L.ptr(gy) if residual else None
         if mode == ROWS:
-            if need[5]:
+            if need[6]:
                 gx = torch.empty_like(x)
                 L.check(lib.dlwp_graph_dgrad0(mode, L.ptr(dz), L.ptr(ws[0]), None, L.ptr(gx), None, None, B, N, E, rows, De, Dv, hidden, s))
         elif mode == EDGE:
-            gx = torch.empty_like(x) if need[5] else None
-            dsrc = torch.empty(rows, Dv, device=dev) if need[6] else None
-            ddst = torch.empty(rows, Dv, device=dev) if need[6] else None
-            if need[5] or need[6]:
+            gx = torch.empty_like(x) if need[6] else None
+            dsrc = torch.empty(rows, Dv, device=dev) if need[7] else None
+            ddst = torch.empty(rows, Dv, device=dev) if need[7] else None
+            if need[6] or need[7]:
                 L.check(lib.dlwp_graph_dgrad0(mode, L.ptr(dz), L.ptr(ws[0]), res, L.ptr(gx), L.ptr(dsrc), L.ptr(ddst), B, N, E, rows,
                                               De, Dv, hidden, s))
-            if need[6]:
+            if need[7]:
                 gv = torch.empty_like(v)
                 L.check(lib.dlwp_graph_gather_sum(L.ptr(dsrc), L.ptr(graph.out_ptr), L.ptr(graph.out_eid), 0, L.ptr(ddst),
                                                   L.ptr(graph.in_ptr), L.ptr(graph.in_eid), None, L.ptr(gv), B, N, E, Dv, s))
         else:
-            dagg = torch.empty(rows, De, device=dev) if need[5] else None
-            gv = torch.empty_like(v) if need[6] else None
-            if need[5] or need[6]:
+            dagg = torch.empty(rows, De, device=dev) if need[6] else None
+            gv = torch.empty_like(v) if need[7] else None
+            if need[6] or need[7]:
                 L.check(lib.dlwp_graph_dgrad0(mode, L.ptr(dz), L.ptr(ws[0]), res, L.ptr(dagg), L.ptr(gv), None, B, N, E, rows, De, Dv,
                                               hidden, s))
-            if need[5]:
+            if need[6]:
                 gx = torch.empty_like(x)
                 L.check(lib.dlwp_graph_edge_gather(L.ptr(dagg), L.ptr(graph.dst), L.ptr(graph.in_ptr) if mean else None, None,
                                                    L.ptr(gx), B, N, E, De, s))
-        return (None, None, None, None, None, gx, gv) + tuple(gnorm_out) + tuple(pgrads_out)
+        return (None, None, None, None, None, None, gx, gv) + tuple(gnorm_out) + tuple(pgrads_out)
 
 
 def _norm_pair(norm):
     return (None, None) if norm is None else tuple(norm)
 
 
-def graph_mlp(x, params, norm=None):
-    """`LayerNorm(Linear(relu(... relu(Linear(x)))))` on rows `x [rows, in]`: params = [w0, b0, ..., wL, bL] (1 to 3 hidden
-    layers of one width, every width 1..128), norm = (gamma, beta) or None.  One launch."""
-    return _GraphMlpFn.apply(ROWS, None, False, False, torch.is_grad_enabled(), x, None, *_norm_pair(norm), *params)
+def _act_code(act):
+    if act not in L.GRAPH_ACT:
+        raise ValueError(f"act must be 'relu' or 'silu', not {act!r}")
+    return L.GRAPH_ACT[act]
 
 
-def edge_block(e, v, graph, params, norm=None, residual=True):
+def graph_mlp(x, params, norm=None, act="relu"):
+    """`LayerNorm(Linear(act(... act(Linear(x)))))` on rows `x [rows, in]`: params = [w0, b0, ..., wL, bL] (1 to 3 hidden
+    layers of one width, every width 1..128), norm = (gamma, beta) or None, act "relu" or "silu".  One launch."""
+    return _GraphMlpFn.apply(ROWS, None, False, False, torch.is_grad_enabled(), _act_code(act), x, None, *_norm_pair(norm), *params)
+
+
+def edge_block(e, v, graph, params, norm=None, residual=True, act="relu"):
     """`e + MLP(cat(e, v[src], v[dst]))` on edge rows `e [B * E, De]` and node rows `v [B * N, Dv]` (MeshEdgeBlock)."""
     if not isinstance(graph, Graph):
         raise TypeError("edge_block: graph must be a graph_ops.Graph")
-    return _GraphMlpFn.apply(EDGE, graph, False, bool(residual), torch.is_grad_enabled(), e, v, *_norm_pair(norm), *params)
+    return _GraphMlpFn.apply(EDGE, graph, False, bool(residual), torch.is_grad_enabled(), _act_code(act), e, v, *_norm_pair(norm),
+                             *params)
 
 
-def node_block(e, v, graph, params, norm=None, aggregation="sum", residual=True):
+def node_block(e, v, graph, params, norm=None, aggregation="sum", residual=True, act="relu"):
     """`v + MLP(cat(agg, v))`, agg[i] = sum or mean of the rows of `e` over the in-edges of node i, zeros where there is none
     (MeshNodeBlock).  Returns the new node rows."""
     if not isinstance(graph, Graph):
         raise TypeError("node_block: graph must be a graph_ops.Graph")
     if aggregation not in AGGREGATIONS:
         raise ValueError(f"aggregation must be 'sum' or 'mean', not {aggregation!r}")
-    return _GraphMlpFn.apply(NODE, graph, aggregation == "mean", bool(residual), torch.is_grad_enabled(), e, v, *_norm_pair(norm), *params)
+    return _GraphMlpFn.apply(NODE, graph, aggregation == "mean", bool(residual), torch.is_grad_enabled(), _act_code(act), e, v,
+                             *_norm_pair(norm), *params)
 
 
 def aggregate(e, graph, aggregation="sum"):

@@ -30,11 +30,13 @@ class GraphMlpArgs(C.Structure):
                 + [(n, C.c_void_p) for n in ("x", "v", "src", "dst", "in_ptr", "in_eid")]
                 + [(n, C.c_int) for n in ("De", "Dv", "hidden", "out", "hidden_layers", "residual", "mean")] + [("eps", C.c_float)]
                 + [("w", C.c_void_p * 4), ("b", C.c_void_p * 4), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p),
-                   ("hid", C.c_void_p * 3), ("xhat", C.c_void_p), ("rstd", C.c_void_p), ("agg", C.c_void_p)])
+                   ("hid", C.c_void_p * 3), ("xhat", C.c_void_p), ("rstd", C.c_void_p), ("agg", C.c_void_p),
+                   ("act", C.c_int), ("der", C.c_void_p * 3)])
 
 
 GRAPH_MAX_WIDTH, GRAPH_MAX_HIDDEN_LAYERS = 128, 3      # DLWP_GRAPH_MAX_WIDTH, DLWP_GRAPH_MAX_HIDDEN_LAYERS
 GRAPH_ROWS, GRAPH_EDGE, GRAPH_NODE = 0, 1, 2
+GRAPH_ACT = {"relu": 0, "silu": 1}      # DLWP_GRAPH_ACT_RELU, DLWP_GRAPH_ACT_SILU
 
 # parameter kinds of the flat FNO parameter buffer (dlwpmi.h enum)
 P_LIFT_W1, P_LIFT_B1, P_LIFT_W2, P_LIFT_B2, P_PROJ_W1, P_PROJ_B1, P_PROJ_W2, P_PROJ_B2, \
@@ -226,6 +228,7 @@ SIGNATURES = {
     "dlwp_graph_wgrad0_ws_floats": (_L, [_L, _I, _I]),
     "dlwp_graph_wgrad0": (_I, [_I] + [_V] * 8 + [_I, _I, _I, _L, _I, _I, _I, _V]),
     "dlwp_graph_dgrad0": (_I, [_I] + [_V] * 6 + [_I, _I, _I, _L, _I, _I, _I, _V]),
+    "dlwp_graph_dgrad_mul": (_I, [_V] * 4 + [_L, _I, _I, _V]),
     "dlwp_graph_gather_sum": (_I, [_V, _V, _V, _I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _V]),
     "dlwp_graph_edge_gather": (_I, [_V] * 5 + [_I] * 4 + [_V]),
     "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),

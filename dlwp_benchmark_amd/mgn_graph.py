@@ -1,5 +1,5 @@
-"""The fixed meshes of the MeshGraphNet baselines as index arrays: numpy only (scipy for the Delaunay triangulation), no networkx,
-no DGL, and no import of the library -- the CPU tests use it as it is.
+"""The fixed meshes of the MeshGraphNet and GraphCastNS baselines as index arrays: numpy only (scipy for the Delaunay
+triangulation), no networkx, no DGL, and no import of the library -- the CPU tests use it as it is.
 
 Reference: MeshGraphNet.create_grid_2d_graph / create_grid_2d_graph_8stencil / create_delaunay_graph / create_edge_features in
 src/nsbench/models/mgn/meshgraphnet.py:231-341 and src/dlwpbench/models/mgn/meshgraphnet.py:233-345, which build a networkx graph
@@ -9,6 +9,9 @@ RESTATED from its documentation, not executed:
 * `to_bidirected` adds the reverse of every edge and drops duplicates;
 * `batch` offsets the node ids of sample b by b * num_nodes.
 tests/golden/make_mgn_golden.py runs the reference classes on a stub `dgl` with exactly this behaviour.
+GraphCastNS's mesh (build_nhop_grid: the periodic grid plus n-hop shortcuts, GraphCastNetNS.create_grid_2d_graph /
+create_edge_features in src/nsbench/models/graphcast/graph_cast_net_ns.py:252-312, which walk a networkx graph node by node and
+edge by edge) is restated the same way and pinned by tests/golden/make_graphcast_ns_golden.py.
 
 Node u is grid point (u // width, u % width): the order of the models' "(b h w) d" rows.  The edge ORDER is ours (the model only
 sums over edges): sorted by destination, then source, so the in-edges of a node are consecutive.
@@ -128,6 +131,58 @@ def build_graph(graph_type, height, width, periodic=True, cylinder=False):
     key = np.unique(np.concatenate([b * n + a, a * n + b]).astype(np.int64))
     dst, src = key // n, key % n
     feats = edge_features(src, dst, height, width, graph_type == "grid_2d_8stencil")
+    return Graph(src.astype(np.int32), dst.astype(np.int32), feats, n, *build_csr(src, dst, n))
+
+
+def nhop_edge_features(src, dst, height, width, nhop_neighbors):
+    """GraphCastNetNS.create_edge_features of the reference: [dir_y, dir_x, dist] per directed edge.  The coordinates are
+    (u // HEIGHT, u % width) as there; the four wrap-around assignments run one after the other on BOTH components (on a small grid
+    a later one rewrites what an earlier one set); dist is the distance on the 1-hop torus (true grid coordinates) over max(nhop),
+    formed in float64 and rounded to fp32 as there."""
+    u, v = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    m = int(max(nhop_neighbors))
+    normal = np.stack([v // height - u // height, v % width - u % width], axis=1)
+    normal[normal >= height - 1 - m] = -1
+    normal[normal >= width - 1 - m] = -1
+    normal[normal <= -(height - 1 - m)] = 1
+    normal[normal <= -(width - 1 - m)] = 1
+    normal = normal.clip(-1, 1)
+    di, dj = np.abs(v // width - u // width), np.abs(v % width - u % width)
+    dist = (np.minimum(di, height - di) + np.minimum(dj, width - dj)) / float(m)
+    return np.ascontiguousarray(np.concatenate([normal.astype(np.float64), dist[:, None]], axis=1), dtype=np.float32)
+
+
+def build_nhop_grid(height, width, nhop_neighbors=(2,)):
+    """The mesh of the reference's GraphCastNetNS (src/nsbench/models/graphcast/graph_cast_net_ns.py:252-312) -> Graph with
+    edge_features [E, 3]: the periodic height x width 4-neighbour grid (always periodic) plus "n-hop" shortcuts.  Every node
+    (i, j) with a multiple of some nhop value on each axis gets an undirected edge to every node of its row or column whose torus
+    distance d is one of the nhop values and d <= max(nhop) - max(max(i, j) % nhop); then both directions, duplicates dropped."""
+    height, width = int(height), int(width)
+    nhop = np.unique(np.asarray(list(nhop_neighbors), np.int64))
+    if height < 3 or width < 3:
+        raise ValueError(f"the periodic n-hop grid needs at least 3 x 3 nodes, not {height} x {width}")
+    if len(nhop) == 0 or nhop[0] < 1:
+        raise ValueError(f"nhop_neighbors must be positive hop counts, not {list(nhop_neighbors)}")
+    n = height * width
+    pairs = _grid_pairs(height, width, True)
+    a = [p[0] * width + p[1] for p in pairs]
+    b = [p[2] * width + p[3] for p in pairs]
+    i, j = (x.reshape(-1) for x in np.meshgrid(np.arange(height), np.arange(width), indexing="ij"))
+    listed = ((i[:, None] % nhop) == 0).any(axis=1) & ((j[:, None] % nhop) == 0).any(axis=1)
+    cutoff = nhop[-1] - (np.maximum(i, j)[:, None] % nhop).max(axis=1)
+    for d in nhop:
+        sel = listed & (d <= cutoff)
+        si, sj = i[sel], j[sel]
+        # a node of the same row (column) at torus distance d exists only while 2 d <= the row's (column's) length
+        for ok, ti, tj in ((2 * d <= width, si, (sj + d) % width), (2 * d <= width, si, (sj - d) % width),
+                           (2 * d <= height, (si + d) % height, sj), (2 * d <= height, (si - d) % height, sj)):
+            if ok:
+                a.append(si * width + sj)
+                b.append(ti * width + tj)
+    a, b = np.concatenate(a), np.concatenate(b)
+    key = np.unique(np.concatenate([b * n + a, a * n + b]).astype(np.int64))
+    dst, src = key // n, key % n
+    feats = nhop_edge_features(src, dst, height, width, nhop)
     return Graph(src.astype(np.int32), dst.astype(np.int32), feats, n, *build_csr(src, dst, n))
 
 

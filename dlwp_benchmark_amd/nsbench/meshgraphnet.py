@@ -19,9 +19,9 @@ from .convlstm import _Slot
 
 class MeshGraphMLP(nn.Module):
     """`model` = Sequential(Linear, slot, [Linear, slot, ...] Linear [, LayerNorm]) with the reference's indices (a parameter-free
-    slot stands where it has the ReLU); `forward` on rows is graph_ops.graph_mlp."""
+    slot stands where it has the activation: ReLU, or SiLU in GraphCast); `forward` on rows is graph_ops.graph_mlp."""
 
-    def __init__(self, input_dim, output_dim, hidden_dim, hidden_layers, norm=True):
+    def __init__(self, input_dim, output_dim, hidden_dim, hidden_layers, norm=True, act="relu"):
         super().__init__()
         layers = [nn.Linear(input_dim, hidden_dim), _Slot()]
         for _ in range(hidden_layers - 1):
@@ -30,7 +30,7 @@ class MeshGraphMLP(nn.Module):
         if norm:
             layers.append(nn.LayerNorm(output_dim))
         self.model = nn.Sequential(*layers)
-        self.hidden_layers, self.has_norm = hidden_layers, norm
+        self.hidden_layers, self.has_norm, self.act = hidden_layers, norm, act
 
     def params(self):
         return [p for m in self.model if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
@@ -39,36 +39,36 @@ class MeshGraphMLP(nn.Module):
         return (self.model[-1].weight, self.model[-1].bias) if self.has_norm else None
 
     def forward(self, x):
-        return graph_mlp(x, self.params(), self.norm())
+        return graph_mlp(x, self.params(), self.norm(), act=self.act)
 
 
 class MeshEdgeBlock(nn.Module):
-    def __init__(self, dim, hidden_layers):
+    def __init__(self, dim, hidden_layers, act="relu"):
         super().__init__()
-        self.edge_mlp = MeshGraphMLP(3 * dim, dim, dim, hidden_layers)
+        self.edge_mlp = MeshGraphMLP(3 * dim, dim, dim, hidden_layers, act=act)
 
     def forward(self, e, v, graph):
-        return edge_block(e, v, graph, self.edge_mlp.params(), self.edge_mlp.norm()), v
+        return edge_block(e, v, graph, self.edge_mlp.params(), self.edge_mlp.norm(), act=self.edge_mlp.act), v
 
 
 class MeshNodeBlock(nn.Module):
-    def __init__(self, aggregation, dim, hidden_layers):
+    def __init__(self, aggregation, dim, hidden_layers, act="relu"):
         super().__init__()
         self.aggregation = aggregation
-        self.node_mlp = MeshGraphMLP(2 * dim, dim, dim, hidden_layers)
+        self.node_mlp = MeshGraphMLP(2 * dim, dim, dim, hidden_layers, act=act)
 
     def forward(self, e, v, graph):
-        return e, node_block(e, v, graph, self.node_mlp.params(), self.node_mlp.norm(), self.aggregation)
+        return e, node_block(e, v, graph, self.node_mlp.params(), self.node_mlp.norm(), self.aggregation, act=self.node_mlp.act)
 
 
 class MeshGraphNetProcessor(nn.Module):
     """`processor_layers` = edge block, node block, edge block, ... (the reference's interleaved ModuleList)"""
 
-    def __init__(self, processor_size, dim, num_layers_node, num_layers_edge, aggregation):
+    def __init__(self, processor_size, dim, num_layers_node, num_layers_edge, aggregation, act="relu"):
         super().__init__()
         layers = []
         for _ in range(processor_size):
-            layers += [MeshEdgeBlock(dim, num_layers_edge), MeshNodeBlock(aggregation, dim, num_layers_node)]
+            layers += [MeshEdgeBlock(dim, num_layers_edge, act), MeshNodeBlock(aggregation, dim, num_layers_node, act)]
         self.processor_layers = nn.ModuleList(layers)
 
     def forward(self, v, e, graph):
@@ -89,6 +89,27 @@ def _graph_spec(graph):
     return int(h), int(w), (bool(p) if isinstance(p, (bool, int)) else tuple(bool(q) for q in p))
 
 
+def check_limits(widths, depths, aggregation, do_concat_trick, num_processor_checkpoint_segments):
+    """The refusals every model on the graph kernels shares (widths, depths: keyword -> value)"""
+    if do_concat_trick:
+        raise NotImplementedError("do_concat_trick=True splits the first edge Linear into three parameters (lin_efeat, lin_src, "
+                                  "lin_dst): other state_dict keys, not built")
+    if num_processor_checkpoint_segments and int(num_processor_checkpoint_segments) > 0:
+        raise NotImplementedError("num_processor_checkpoint_segments > 0 (gradient checkpointing of the processor) is not built")
+    if aggregation not in AGGREGATIONS:
+        raise ValueError(f"aggregation must be 'sum' or 'mean', not {aggregation!r}")
+    for k, d in widths.items():
+        if int(d) < 1:
+            raise ValueError(f"{k} = {d} must be positive")
+        if int(d) > L.GRAPH_MAX_WIDTH:
+            raise NotImplementedError(f"{k} = {d}: the graph kernels take widths up to {L.GRAPH_MAX_WIDTH}")
+    for k, d in depths.items():
+        if int(d) < 1:
+            raise ValueError(f"{k} = {d} must be at least 1")
+        if int(d) > L.GRAPH_MAX_HIDDEN_LAYERS:
+            raise NotImplementedError(f"{k} = {d}: the graph kernels take up to {L.GRAPH_MAX_HIDDEN_LAYERS} hidden layers")
+
+
 class MeshGraphNetBase(nn.Module):
     """What the two benchmarks' classes share: the refusals, the mesh, the four sub-networks (registered in the reference's
     order: edge_encoder, node_encoder, node_decoder, processor) and one network call."""
@@ -97,11 +118,7 @@ class MeshGraphNetBase(nn.Module):
                num_layers_edge_processor, hidden_dim_processor, hidden_dim_node_encoder, num_layers_node_encoder,
                hidden_dim_edge_encoder, num_layers_edge_encoder, hidden_dim_node_decoder, num_layers_node_decoder, aggregation,
                do_concat_trick, num_processor_checkpoint_segments, graph_type, graph, cylinder, device):
-        if do_concat_trick:
-            raise NotImplementedError("do_concat_trick=True splits the first edge Linear into three parameters (lin_efeat, lin_src, "
-                                      "lin_dst): other state_dict keys, not built")
-        if num_processor_checkpoint_segments and int(num_processor_checkpoint_segments) > 0:
-            raise NotImplementedError("num_processor_checkpoint_segments > 0 (gradient checkpointing of the processor) is not built")
+        check_limits({}, {}, "sum", do_concat_trick, num_processor_checkpoint_segments)
         if graph_type not in mgn_graph.GRAPH_TYPES:
             raise ValueError(f"graph_type is '{graph_type}' but should be any of {list(mgn_graph.GRAPH_TYPES)}.")
         if aggregation not in AGGREGATIONS:
@@ -115,16 +132,7 @@ class MeshGraphNetBase(nn.Module):
         depths = dict(num_layers_node_processor=num_layers_node_processor, num_layers_edge_processor=num_layers_edge_processor,
                       num_layers_node_encoder=num_layers_node_encoder, num_layers_edge_encoder=num_layers_edge_encoder,
                       num_layers_node_decoder=num_layers_node_decoder)
-        for k, d in widths.items():
-            if int(d) < 1:
-                raise ValueError(f"{k} = {d} must be positive")
-            if int(d) > L.GRAPH_MAX_WIDTH:
-                raise NotImplementedError(f"{k} = {d}: the graph kernels take widths up to {L.GRAPH_MAX_WIDTH}")
-        for k, d in depths.items():
-            if int(d) < 1:
-                raise ValueError(f"{k} = {d} must be at least 1")
-            if int(d) > L.GRAPH_MAX_HIDDEN_LAYERS:
-                raise NotImplementedError(f"{k} = {d}: the graph kernels take up to {L.GRAPH_MAX_HIDDEN_LAYERS} hidden layers")
+        check_limits(widths, depths, aggregation, False, 0)
         if int(processor_size) < 1 or int(message_passing_steps) < 1:
             raise ValueError("processor_size and message_passing_steps must be at least 1")
         self.message_passing_steps, self.graph_type = int(message_passing_steps), graph_type

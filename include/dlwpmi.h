@@ -1041,16 +1041,21 @@ int dlwp_upconv2x2_wgrad(const float* x, const float* dy, float* ws, float* gw, 
 #define DLWP_GRAPH_MAX_WIDTH 128
 #define DLWP_GRAPH_MAX_HIDDEN_LAYERS 3
 enum { DLWP_GRAPH_ROWS = 0, DLWP_GRAPH_EDGE = 1, DLWP_GRAPH_NODE = 2 };
-/* One launch: hidden_layers x (Linear + bias + ReLU), Linear + bias [, LayerNorm (biased variance, affine) when     */
-/* gamma != NULL] [, + residual] on the operand rows                                                                */
+enum { DLWP_GRAPH_ACT_RELU = 0, DLWP_GRAPH_ACT_SILU = 1 };
+/* One launch: hidden_layers x (Linear + bias + activation), Linear + bias [, LayerNorm (biased variance, affine)    */
+/* when gamma != NULL] [, + residual] on the operand rows                                                           */
 /*   rows  A[r] = x[r]                                   (x [rows][De])                                              */
 /*   edge  A[r] = x[r] | v[b N + src[k]] | v[b N + dst[k]]   (x = e [B E][De], v [B N][Dv]; residual: + e[r])          */
 /*   node  A[r] = agg[r] | v[r],  agg[r] = sum (mean != 0: mean) of x[b E + in_eid[j]], in_ptr[i] <= j < in_ptr[i+1]   */
 /*         (x = e [B E][De]; a node without in-edges gets zeros; residual: + v[r])                                   */
 /* which are assembled while they are staged: the concatenation is never written.  w[l] [out_l][in_l] and b[l] are   */
 /* nn.Linear's own arrays (b[l] nullable); every hidden layer has `hidden` columns.  Stored for a backward pass,     */
-/* each unless NULL: hid[l] [rows][hidden] post-ReLU rows, xhat [rows][out] normalised rows, rstd [rows] 1 / sigma,   */
-/* agg [B N][De] (node mode).                                                                                        */
+/* each unless NULL: hid[l] [rows][hidden] post-activation rows, xhat [rows][out] normalised rows, rstd [rows]       */
+/* 1 / sigma, agg [B N][De] (node mode).                                                                             */
+/* act (the LAST fields, so that a zero-initialised struct of the earlier layout means what it meant): ReLU (0), or  */
+/* SiLU v s with s = 1 / (1 + exp(-v)) (MeshGraphMLP's activation_fn in GraphCastNetNS, graph_cast_net_ns.py:208-246). */
+/* SiLU's derivative cannot be taken from the stored v s, so der[l] [rows][hidden] (each unless NULL, SiLU only)     */
+/* receives d = s (1 + v (1 - s)); both stay finite for any finite v (-0 / 0 and v / 1 far out).                     */
 typedef struct dlwp_graph_mlp_args {
     int mode, B, N, E;
     long long rows;                     /* rows mode only; edge: B E, node: B N */
@@ -1064,6 +1069,8 @@ typedef struct dlwp_graph_mlp_args {
     float* y;
     float* hid[DLWP_GRAPH_MAX_HIDDEN_LAYERS];
     float *xhat, *rstd, *agg;
+    int act;
+    float* der[DLWP_GRAPH_MAX_HIDDEN_LAYERS];
 } dlwp_graph_mlp_args;
 int dlwp_graph_mlp_fwd(const dlwp_graph_mlp_args* args, void* stream);
 /* LayerNorm backward from the stored rows: WRITES dz [rows][C]; ggamma / gbeta (each nullable) are ACCUMULATED      */
@@ -1084,6 +1091,11 @@ int dlwp_graph_wgrad0(int mode, const float* x, const float* v, const int* src, 
 /* res (nullable): the gradient arriving along the block's residual, in the layout of the part it is added to.       */
 int dlwp_graph_dgrad0(int mode, const float* dz, const float* w, const float* res, float* out0, float* out1, float* out2,
                       int B, int N, int E, long long rows, int De, int Dv, int hidden, void* stream);
+/* Input gradient of a LATER Linear with the activation's derivative applied as it is stored:                        */
+/* out [rows][in] = (dz [rows][out_width] . w [out_width][in]) * mul [rows][in]   (mul NULL: dz . w alone).           */
+/* One launch for dlwp_conv1x1_dgrad followed by an element-wise pass; SiLU's backward takes it with mul = der[l-1]. */
+int dlwp_graph_dgrad_mul(const float* dz, const float* w, const float* mul, float* out, long long rows, int in, int out_width,
+                         void* stream);
 /* out[b N + i] = [add[b N + i]] + sum_j in1[b E + eid1[j]] (ptr1[i] <= j < ptr1[i+1]; mean1 != 0: divided by the     */
 /* count) [+ sum_j in2[b E + eid2[j]] over the second list], rows of width C, summed in list order.  The forward     */
 /* aggregation on its own (in-edges), and dv of an edge block (out-edges of d_src, in-edges of d_dst).               */
