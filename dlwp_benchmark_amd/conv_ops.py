@@ -2,17 +2,21 @@
 and the other U-Net layers (csrc/unet_ops.hip): 2 x 2 average pool, 2 x 2 stride-2 up-convolution, 1 x 1 convolution.
 
 Activations are channels-last fp32 `[B, H, W, C]`.  The padding is a pair of per-axis modes (height, width), each "zeros" or
-"circular"; it is resolved inside the kernels, so neither a padded tensor nor `cat(x, h_prev)` is ever written.  The weight
+"circular", or "healpix" on both axes at once (`[12 * spheres, n, n, C]`, face index fastest: every face is padded with the
+border pixels of its neighbour faces, `hpx_halo_map`); it is resolved inside the kernels, so neither a padded tensor nor
+`cat(x, h_prev)` is ever written.  The weight
 stays `nn.Conv2d`'s `[Cout, Cin, 3, 3]` parameter; the kernels read packed images of it (`pack_weight`), which a model refreshes
 once per forward pass and shares between its time steps.  There is no CPU or torch fallback.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import lib as L
 from .token_ops import _grad_buffer, _grad_slot
 
-PAD = {"zeros": 0, "circular": 1}
+PAD = {"zeros": 0, "circular": 1, "healpix": 2}
+PAD_HEALPIX = PAD["healpix"]
 ACT = {None: 0, "none": 0, "tanh": 1, "relu": 2}
 IMG_FWD, IMG_GATES, IMG_DGRAD = 0, 1, 2
 
@@ -21,9 +25,126 @@ def _pad_codes(padding):
     if isinstance(padding, str):
         padding = (padding, padding)
     try:
-        return PAD[padding[0]], PAD[padding[1]]
+        ph, pw = PAD[padding[0]], PAD[padding[1]]
     except (KeyError, IndexError, TypeError):
-        raise ValueError(f"padding must be 'zeros' / 'circular' or a (height, width) pair of them, not {padding!r}") from None
+        raise ValueError("padding must be 'zeros' / 'circular' or a (height, width) pair of them, or 'healpix' (both axes), "
+                         f"not {padding!r}") from None
+    if (ph == PAD_HEALPIX) != (pw == PAD_HEALPIX):
+        raise ValueError(f"'healpix' pads both axes at once: it cannot be mixed with another mode ({padding!r})")
+    return ph, pw
+
+
+# ---- HEALPix geometry (padding width 1)
+def _hpx_ring(n):
+    """(pr, pc) of the 4 n + 4 ring cells of a padded (n + 2) x (n + 2) face in table order: top row, bottom row, left column,
+    right column (the columns without their corners)"""
+    return ([(0, c) for c in range(n + 2)] + [(n + 1, c) for c in range(n + 2)] + [(r, 0) for r in range(1, n + 1)]
+            + [(r, n + 1) for r in range(1, n + 1)])
+
+
+def hpx_halo_map(n):
+    """The HEALPix padding of width 1 as a linear map, pure numpy: for each of the 12 faces (0 - 3 north, 4 - 7 equator, 8 - 11
+    south) and each of the `4 * (n + 1)` cells of the one-pixel ring around it, the at most two source pixels.
+
+    Returns `(cells, sources)`: `cells [12, 4 n + 4, 2]` int, the (row, column) of each ring cell in the padded
+    `(n + 2) x (n + 2)` face (top row, bottom row, left column, right column); `sources [12, 4 n + 4, 2, 4]` float64 with
+    `(face, y, x, weight)` per source, weight 0 (and face -1) for an unused second slot.  Weights are 1, or 0.5 + 0.5 for the
+    top-left and bottom-right corner cell of the four equatorial faces, where three faces meet and no corner neighbour exists.
+    """
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"the face size must be positive, not {n}")
+    m = n - 1
+    ring = _hpx_ring(n)
+    cells = np.tile(np.asarray(ring, dtype=np.int64), (12, 1, 1))
+    src = np.zeros((12, len(ring), 2, 4))
+    src[:, :, 1, 0] = -1
+    for f in range(12):
+        band, k = divmod(f, 4)
+        N = lambda q: (k + q) % 4              # noqa: E731  (north, equator, south face q steps around the axis)
+        E = lambda q: 4 + (k + q) % 4          # noqa: E731
+        S = lambda q: 8 + (k + q) % 4          # noqa: E731
+        for ci, (pr, pc) in enumerate(ring):
+            i, j = pr - 1, pc - 1
+            top, bot, left, right = pr == 0, pr == n + 1, pc == 0, pc == n + 1
+            two = None
+            if band == 0:      # the pole neighbours N(1), N(2), N(3) are seen rotated by 90, 180, 270 degrees
+                if top:
+                    one = (N(2), 0, 0) if left else (N(1), m, 0) if right else (N(1), j, 0)
+                elif bot:
+                    one = (N(3), 0, m) if left else (S(0), 0, 0) if right else (E(0), 0, j)
+                else:
+                    one = (N(3), 0, i) if left else (E(1), i, 0)
+            elif band == 1:
+                if top:
+                    one = (N(0), m, 0) if left else (E(1), m, 0) if right else (N(0), m, j)
+                    two = (N(3), 0, m) if left else None
+                elif bot:
+                    one = (E(3), 0, m) if left else (S(3), 0, m) if right else (S(3), 0, j)
+                    two = (S(0), m, 0) if right else None
+                else:
+                    one = (N(3), i, m) if left else (S(0), i, 0)
+            else:
+                if top:
+                    one = (N(0), m, m) if left else (S(1), m, 0) if right else (E(1), m, j)
+                elif bot:
+                    one = (S(3), 0, m) if left else (S(2), m, m) if right else (S(3), j, m)
+                else:
+                    one = (E(0), i, m) if left else (S(1), m, i)
+            src[f, ci, 0] = (*one, 0.5 if two else 1.0)
+            if two:
+                src[f, ci, 1] = (*two, 0.5)
+    return cells, src
+
+
+def hpx_fold_table(n):
+    """The inverse of `hpx_halo_map` in the form `dlwp_conv3x3_hpx_dgrad` reads, numpy int32 `[12, 4 n - 4, 4]`: per border pixel
+    of a face (top row, bottom row, left column, right column without corners) the ring cells that read it, in ascending cell
+    order, as `(cell << 1) | half` with `cell = (face * (n + 2) + row) * (n + 2) + column` and half = 1 for weight 0.5; -1 = none."""
+    if n < 2:
+        raise ValueError(f"HEALPix padding needs faces of at least 2 x 2 pixels, not {n}")
+    cells, src = hpx_halo_map(n)
+    readers = {}
+    for f in range(12):
+        for ci in range(cells.shape[1]):
+            pr, pc = cells[f, ci]
+            for sf, y, x, wgt in src[f, ci]:
+                if wgt > 0:
+                    readers.setdefault((int(sf), int(y), int(x)), []).append(((((f * (n + 2)) + int(pr)) * (n + 2) + int(pc)) << 1)
+                                                                             | int(wgt == 0.5))
+    pix = ([(0, x) for x in range(n)] + [(n - 1, x) for x in range(n)] + [(y, 0) for y in range(1, n - 1)]
+           + [(y, n - 1) for y in range(1, n - 1)])
+    table = np.full((12, 4 * n - 4, 4), -1, dtype=np.int32)
+    for (f, y, x), ents in readers.items():
+        if len(ents) > 4 or (y, x) not in pix:
+            raise AssertionError(f"pixel {(f, y, x)} of face size {n} is read by {len(ents)} ring cells")
+        table[f, pix.index((y, x)), :len(ents)] = sorted(ents)
+    return table
+
+
+_HPX_TABLES = {}
+
+
+def _hpx_table(n, device):
+    """the fold table of face size n on `device`, built and uploaded once (so that a captured step only reads it)"""
+    key = (int(n), str(device))
+    if key not in _HPX_TABLES:
+        _HPX_TABLES[key] = torch.from_numpy(hpx_fold_table(int(n))).to(device)
+    return _HPX_TABLES[key]
+
+
+def _input_grad(dz, dgrad_img, g1, g2, B, H, W, cout, C1, C2, pads):
+    """the input gradient(s) of a convolution from dz: the flipped-weight product with the same padding for zeros / circular; for
+    HEALPix that product over the padded domain of every face followed by the fold onto the pixels the ring cells read"""
+    lib = L.load()
+    if pads[0] != PAD_HEALPIX:
+        L.check(lib.dlwp_conv3x3_fwd(L.ptr(dz), None, L.ptr(dgrad_img), None, L.ptr(g1), L.ptr(g2), B, H, W, cout, 0, C1, C2,
+                                     pads[0], pads[1], 0, L.stream()))
+        return
+    ws = L.workspace(lib.dlwp_conv3x3_hpx_dgrad_ws_floats, B, H, C1 + C2, device=dz.device)
+    table = _hpx_table(H, dz.device)
+    L.check(lib.dlwp_conv3x3_hpx_dgrad(L.ptr(dz), L.ptr(dgrad_img), table.data_ptr(), L.ptr(ws), L.ptr(g1), L.ptr(g2), B, H, cout,
+                                       C1, C2, L.stream()))
 
 
 def _check_weight(weight):
@@ -110,8 +231,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         if need1 or need2:
             if ctx.packed.dgrad is None:
                 raise L.DlwpError("conv3x3: this weight was packed without its input-gradient image")
-            L.check(lib.dlwp_conv3x3_fwd(L.ptr(dz), None, L.ptr(ctx.packed.dgrad), None, L.ptr(g1), L.ptr(g2), B, H, W, cout, 0, C1, C2,
-                                         ctx.pads[0], ctx.pads[1], 0, L.stream()))
+            _input_grad(dz, ctx.packed.dgrad, g1, g2, B, H, W, cout, C1, C2, ctx.pads)
         gw = gb = None
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
             gw, gb = _weight_grad(x1, x2, dz, ctx.wshape, ctx.wslot, ctx.bslot, ctx.has_bias, ctx.pads)
@@ -120,7 +240,8 @@ class _Conv3x3Fn(torch.autograd.Function):
 
 def conv3x3(x, weight, bias=None, padding="zeros", act=None, x2=None, packed=None):
     """`act(conv2d(cat(x, x2), weight, bias))`, 3 x 3, stride 1, same size, on channels-last `[B, H, W, C]` tensors.
-    padding: "zeros" / "circular" or a (height, width) pair; act: None / "tanh" / "relu"; packed: the weight's PackedWeight
+    padding: "zeros" / "circular" or a (height, width) pair, or "healpix" (`B = 12 * spheres` square faces); act: None / "tanh" /
+    "relu"; packed: the weight's PackedWeight
     (built here when absent: two more launches)."""
     _check_weight(weight)
     ph, pw = _pad_codes(padding)
@@ -176,8 +297,7 @@ class _ConvLSTMCellFn(torch.autograd.Function):
         if needx or needh:
             if ctx.packed.dgrad is None:
                 raise L.DlwpError("convlstm_cell: this weight was packed without its input-gradient image")
-            L.check(lib.dlwp_conv3x3_fwd(L.ptr(dz), None, L.ptr(ctx.packed.dgrad), None, L.ptr(gx), L.ptr(ghp), B, H, W, 4 * hid, 0, Cx,
-                                         hid, ctx.pads[0], ctx.pads[1], 0, L.stream()))
+            _input_grad(dz, ctx.packed.dgrad, gx, ghp, B, H, W, 4 * hid, Cx, hid, ctx.pads)
         gw = gb = None
         if ctx.needs_input_grad[3] or (ctx.has_bias and ctx.needs_input_grad[4]):
             if h_prev is None:
@@ -202,12 +322,12 @@ class Conv3x3(nn.Conv2d):
     """`nn.Conv2d(cin, cout, 3, padding=1)` on the hand-written kernel: parameter names and shapes are nn.Conv2d's, so a
     checkpoint of the torch layer loads as it is.  `forward` takes and returns channels-FIRST `[B, C, H, W]` like nn.Conv2d
     (two permute copies); `forward_cl` is the channels-last form the models chain.  `pad_modes`: per-axis (height, width)
-    padding, default from `padding_mode` ("zeros" / "circular" on both axes)."""
+    padding, default from `padding_mode` ("zeros" / "circular" on both axes); `("healpix", "healpix")` for a HEALPix layer."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, padding_mode="zeros", bias=True, pad_modes=None,
                  act=None, **kw):
         ks = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
-        if ks != 3 or padding not in (1, (1, 1)) or padding_mode not in PAD:
+        if ks != 3 or padding not in (1, (1, 1)) or padding_mode not in ("zeros", "circular"):
             raise ValueError("Conv3x3: kernel_size 3, padding 1 and padding_mode 'zeros' / 'circular' only")
         super().__init__(in_channels, out_channels, 3, padding=1, padding_mode=padding_mode, bias=bias, **kw)
         if tuple(self.stride) != (1, 1) or tuple(self.dilation) != (1, 1) or self.groups != 1:

@@ -18,6 +18,14 @@
 // one 16-byte LDS read and a chunk's image is one contiguous copy.  kind 1 reorders the columns of a cell weight so that the
 // four gate pre-activations of a hidden channel are the four column tiles of ONE lane; kind 2 is the flipped, transposed image
 // that turns the same kernel into the input-gradient product.
+//
+// HEALPix padding (PAD_HEALPIX, both axes at once; src/dlwpbench/utils/healpix.py HEALPixPadding(1) in front of every
+// nn.Conv2d(3) of a HEALPixLayer): B = 12 * spheres square faces, face index fastest.  A ring cell of a face is one pixel of a
+// neighbour face or the mean of two (hpx_halo.hip.h), resolved while staging like the other modes (MODE_HPX of the kernels).
+// Its input gradient is NOT the same convolution with the flipped weight: MODE_HPX_DGRAD runs the flipped-weight product over
+// the PADDED domain (n + 2) x (n + 2) of every face (dz read as zero outside the face) into a scratch, and conv3x3_hpx_fold_kernel
+// gives every pixel its interior value plus, in a fixed order, the weighted ring cells that read it (gather form, no atomics).
+#include "hpx_halo.hip.h"
 #include "row_gemm.hip.h"
 
 namespace {
@@ -30,7 +38,8 @@ using rowgemm::ZP;                        // LDS floats per pixel of the dz tile
 constexpr int NPIX_H = HR * HC;           // 180
 constexpr int STAGE_IT = (NPIX_H + 15) / 16;
 
-enum { PAD_ZEROS = 0, PAD_CIRCULAR = 1 };
+enum { PAD_ZEROS = 0, PAD_CIRCULAR = 1, PAD_HEALPIX = 2 };
+enum { MODE_STD = 0, MODE_HPX = 1, MODE_HPX_DGRAD = 2 };   // how a kernel resolves its halo (template parameter)
 enum { ACT_NONE = 0, ACT_TANH = 1, ACT_RELU = 2 };
 enum { IMG_FWD = 0, IMG_GATES = 1, IMG_DGRAD = 2 };
 
@@ -55,10 +64,33 @@ __device__ __forceinline__ int halo_pixel(int b, int y0, int x0, int pr, int pc,
     return (b * H + yy) * W + xx;
 }
 
+// MODE_HPX: faces are n x n (H = W = n), b = 12 * sphere + face.  *second: the other pixel of a mean-of-two cell, or -1.
+__device__ __forceinline__ int halo_pixel_hpx(int b, int y0, int x0, int pr, int pc, int n, int* second) {
+    const int yy = y0 - 1 + pr, xx = x0 - 1 + pc;
+    *second = -1;
+    if (yy > n || xx > n) return -1;
+    if (yy >= 0 && yy < n && xx >= 0 && xx < n) return (b * n + yy) * n + xx;
+    const int sphere = b / hpx::FACES;
+    int s0, s1;
+    hpx::halo_sources(n, b - sphere * hpx::FACES, yy + 1, xx + 1, &s0, &s1);
+    const int base = sphere * hpx::FACES * n * n;
+    if (s1 >= 0) *second = base + s1;
+    return base + s0;
+}
+
+// MODE_HPX_DGRAD: the tile lies in the PADDED domain np x np (np = n + 2) of face b; position p of it reads dz at p - 1
+// of the n x n face, zero outside.
+__device__ __forceinline__ int halo_pixel_hpx_dgrad(int b, int y0, int x0, int pr, int pc, int np) {
+    const int n = np - 2, yy = y0 - 2 + pr, xx = x0 - 2 + pc;
+    if (yy < 0 || yy >= n || xx < 0 || xx >= n) return -1;
+    return (b * n + yy) * n + xx;
+}
+
 __device__ __forceinline__ float sigmoid_f(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 // CELL = false: y = act(conv + bias) to one or two destinations.  CELL = true (NS = 4, image kind 1): the LSTM update.
-template <int NS, bool CELL>
+// MODE: MODE_STD (zeros / circular per axis), MODE_HPX, or MODE_HPX_DGRAD (H = W = n + 2: the padded domain is the output).
+template <int NS, bool CELL, int MODE>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
     extern __shared__ float lds[];
     float* As = lds;                          // [180][AP]
@@ -74,11 +106,18 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
 
     // this thread stages channel (tid & 15) of the haloed pixels (tid >> 4) + 16 i
     int src[STAGE_IT];
+    int src2[MODE == MODE_HPX ? STAGE_IT : 1];          // MODE_HPX: the second pixel of a mean-of-two cell, or -1
 #pragma unroll
     for (int i = 0; i < STAGE_IT; ++i) {
         const int p = (tid >> 4) + 16 * i;
         const int pr = p / HC, pc = p - pr * HC;
-        src[i] = p < NPIX_H ? halo_pixel(b, y0, x0, pr, pc, a.H, a.W, a.pad_h, a.pad_w) : -2;
+        if constexpr (MODE == MODE_HPX) {
+            src[i] = p < NPIX_H ? halo_pixel_hpx(b, y0, x0, pr, pc, a.H, &src2[i]) : (src2[i] = -1, -2);
+        } else if constexpr (MODE == MODE_HPX_DGRAD) {
+            src[i] = p < NPIX_H ? halo_pixel_hpx_dgrad(b, y0, x0, pr, pc, a.H) : -2;
+        } else {
+            src[i] = p < NPIX_H ? halo_pixel(b, y0, x0, pr, pc, a.H, a.W, a.pad_h, a.pad_w) : -2;
+        }
     }
     f32x4 acc[2][NS];
 #pragma unroll
@@ -96,7 +135,11 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const ConvArgs a) {
         const float* xs = c < a.C1 ? a.x1 + c : (c < Cin ? a.x2 + (c - a.C1) : nullptr);
         const int cs = c < a.C1 ? a.C1 : a.C2;
 #pragma unroll
-        for (int i = 0; i < STAGE_IT; ++i) v[i] = (xs && src[i] >= 0) ? xs[(long long)src[i] * cs] : 0.f;
+        for (int i = 0; i < STAGE_IT; ++i) {
+            v[i] = (xs && src[i] >= 0) ? xs[(long long)src[i] * cs] : 0.f;
+            if constexpr (MODE == MODE_HPX)
+                if (xs && src2[i] >= 0) v[i] = 0.5f * (v[i] + xs[(long long)src2[i] * cs]);
+        }
         const float4* w4 = reinterpret_cast<const float4*>(wsrc + (long long)kc * WIMG);
 #pragma unroll
         for (int i = 0; i < WIT; ++i) {
@@ -267,6 +310,7 @@ struct WgradArgs {
     int C1, C2, Cout, B, H, W, pad_h, pad_w, tiles_h, tiles_w, ntiles, S, cin_pad, cout_pad;
 };
 
+template <bool HPX>
 __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(const WgradArgs a) {
     __shared__ float As[NPIX_H * KC];
     __shared__ float Zs[TH * TW * ZP];
@@ -295,8 +339,15 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(const WgradArgs a) {
         for (int i = 0; i < STAGE_IT; ++i) {
             const int p = (tid >> 4) + 16 * i;
             const int pr = p / HC, pc = p - pr * HC;
-            const int sp = p < NPIX_H ? halo_pixel(b, y0, x0, pr, pc, a.H, a.W, a.pad_h, a.pad_w) : -1;
-            v[i] = xs ? (sp >= 0 ? xs[(long long)sp * cs] : 0.f) : fill;
+            if constexpr (HPX) {
+                int sp2 = -1;
+                const int sp = p < NPIX_H ? halo_pixel_hpx(b, y0, x0, pr, pc, a.H, &sp2) : -1;
+                v[i] = xs ? (sp >= 0 ? xs[(long long)sp * cs] : 0.f) : fill;
+                if (xs && sp2 >= 0) v[i] = 0.5f * (v[i] + xs[(long long)sp2 * cs]);
+            } else {
+                const int sp = p < NPIX_H ? halo_pixel(b, y0, x0, pr, pc, a.H, a.W, a.pad_h, a.pad_w) : -1;
+                v[i] = xs ? (sp >= 0 ? xs[(long long)sp * cs] : 0.f) : fill;
+            }
         }
         // dz tile: thread -> column (tid & 63), pixels (tid >> 6) + 4 i
 #pragma unroll
@@ -358,14 +409,63 @@ inline void wgrad_geometry(int B, int H, int W, int Cin, int Cout, int* cin_pad,
     rowgemm::split_k_geometry(*ntiles, Cin + 1, Cout, cin_pad, cout_pad, S);
 }
 
+// ---- HEALPix input gradient, second half: dx = P^T G with G [B][n + 2][n + 2][C] the flipped-weight product over the padded
+// domain.  Gather form: pixel (b, y, x) takes its interior value G[b][y + 1][x + 1] and then, in the order of the table, the
+// at most four ring cells that read it.  table [12][4 n - 4][4]: per border pixel (hpx::ring_pixel) entries
+// (cell << 1) | half, cell = (face * (n + 2) + pr) * (n + 2) + pc within the sphere, half = 1 for weight 0.5; -1 = none.
+// Channel c < C1 goes to g1 [..][C1], the others to g2 [..][C - C1]; a NULL destination is skipped.
+__global__ __launch_bounds__(256) void conv3x3_hpx_fold_kernel(const float* __restrict__ G, const int* __restrict__ table,
+                                                               float* __restrict__ g1, float* __restrict__ g2, int B, int n, int C1,
+                                                               int C) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)B * n * n * C) return;
+    const int c = (int)(e % C);
+    const int pix = (int)(e / C);
+    const int x = pix % n, y = (pix / n) % n, b = pix / (n * n);
+    const int np = n + 2, ncell = hpx::FACES * np * np;
+    float v = G[(((long long)b * np + y + 1) * np + x + 1) * C + c];
+    if (y == 0 || y == n - 1 || x == 0 || x == n - 1) {
+        const int sphere = b / hpx::FACES, f = b - sphere * hpx::FACES;
+        const int* t = table + ((long long)f * (4 * n - 4) + hpx::ring_pixel(n, y, x)) * 4;
+        const float* Gs = G + (long long)sphere * ncell * C + c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int ent = t[q];
+            if (ent < 0 || (ent >> 1) >= ncell) continue;       // no reader (or a table that is not this face size's)
+            const float gv = Gs[(long long)(ent >> 1) * C];
+            v += (ent & 1) ? 0.5f * gv : gv;
+        }
+    }
+    if (c < C1) { if (g1) g1[(long long)pix * C1 + c] = v; }
+    else if (g2) g2[(long long)pix * (C - C1) + (c - C1)] = v;
+}
+
 bool pad_ok(int p) { return p == PAD_ZEROS || p == PAD_CIRCULAR; }
 
-template <int NS, bool CELL>
+// the padding pair of an entry point: 0 = per-axis zeros / circular, 1 = HEALPix (valid), negative = refused (error set)
+int pad_mode(const char* who, int pad_h, int pad_w, int B, int H, int W) {
+    if (pad_h != PAD_HEALPIX && pad_w != PAD_HEALPIX) {
+        if (pad_ok(pad_h) && pad_ok(pad_w)) return MODE_STD;
+        dlwp_set_error("%s: unknown padding code (%d, %d)", who, pad_h, pad_w);
+        return DLWP_E_INVALID;
+    }
+    if (pad_h != pad_w) {
+        dlwp_set_error("%s: HEALPix padding applies to both axes at once (padding codes %d, %d)", who, pad_h, pad_w);
+        return DLWP_E_INVALID;
+    }
+    if (B % hpx::FACES != 0 || H != W || H < 2) {
+        dlwp_set_error("%s: HEALPix padding needs 12 square faces of at least 2 x 2 pixels per sphere (B %d, H %d, W %d)", who, B, H, W);
+        return DLWP_E_INVALID;
+    }
+    return MODE_HPX;
+}
+
+template <int NS, bool CELL, int MODE>
 int launch_conv(const ConvArgs& a, int nblk, hipStream_t s) {
     const size_t lds = (size_t)(NPIX_H * AP + 9 * 4 * NS * 16 * 4) * sizeof(float);
-    int rc = dlwp_ensure_lds((const void*)conv3x3_kernel<NS, CELL>, lds, "conv3x3");
+    int rc = dlwp_ensure_lds((const void*)conv3x3_kernel<NS, CELL, MODE>, lds, "conv3x3");
     if (rc) return rc;
-    hipLaunchKernelGGL((conv3x3_kernel<NS, CELL>), dim3(a.B * a.tiles_h * a.tiles_w, nblk), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((conv3x3_kernel<NS, CELL, MODE>), dim3(a.B * a.tiles_h * a.tiles_w, nblk), dim3(256), lds, s, a);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
@@ -403,7 +503,8 @@ extern "C" int dlwp_conv3x3_fwd(const float* x1, const float* x2, const float* w
                  "conv3x3_fwd: bad shape (B %d, H %d, W %d, C %d + %d, N %d + %d)", B, H, W, C1, C2, N1, N2);
     DLWP_REQUIRE((C2 == 0) == (x2 == nullptr), DLWP_E_INVALID, "conv3x3_fwd: the second input and its channel count go together");
     DLWP_REQUIRE((!y1 || N1 > 0) && (!y2 || N2 > 0), DLWP_E_INVALID, "conv3x3_fwd: a destination without columns");
-    DLWP_REQUIRE(pad_ok(pad_h) && pad_ok(pad_w), DLWP_E_INVALID, "conv3x3_fwd: unknown padding code (%d, %d)", pad_h, pad_w);
+    const int mode = pad_mode("conv3x3_fwd", pad_h, pad_w, B, H, W);
+    if (mode < 0) return mode;
     DLWP_REQUIRE(act >= ACT_NONE && act <= ACT_RELU, DLWP_E_INVALID, "conv3x3_fwd: unknown activation code %d", act);
     DLWP_REQUIRE((long long)B * H * W < (1ll << 31), DLWP_E_UNSUPPORTED, "conv3x3_fwd: more than 2^31 pixels");
     ConvArgs a{};
@@ -417,8 +518,9 @@ extern "C" int dlwp_conv3x3_fwd(const float* x1, const float* x2, const float* w
     hipStream_t s = (hipStream_t)stream_;
     const double px = (double)B * H * W;
     dlwp_prof_scope ps(s, 2.0 * px * 9 * (C1 + C2) * (N1 + N2), 4.0 * (px * (C1 + C2 + N1 + N2) + 9.0 * (C1 + C2) * (N1 + N2)),
-                       NS == 1 ? "conv3x3_n16" : "conv3x3_n64");
-    return NS == 1 ? launch_conv<1, false>(a, nblk, s) : launch_conv<4, false>(a, nblk, s);
+                       mode == MODE_HPX ? (NS == 1 ? "conv3x3_hpx_n16" : "conv3x3_hpx_n64") : (NS == 1 ? "conv3x3_n16" : "conv3x3_n64"));
+    if (mode == MODE_HPX) return NS == 1 ? launch_conv<1, false, MODE_HPX>(a, nblk, s) : launch_conv<4, false, MODE_HPX>(a, nblk, s);
+    return NS == 1 ? launch_conv<1, false, MODE_STD>(a, nblk, s) : launch_conv<4, false, MODE_STD>(a, nblk, s);
 }
 
 extern "C" int dlwp_convlstm_cell_fwd(const float* x, const float* h_prev, const float* wimg, const float* bias, const float* c_prev,
@@ -427,7 +529,8 @@ extern "C" int dlwp_convlstm_cell_fwd(const float* x, const float* h_prev, const
     DLWP_REQUIRE(x && wimg && h && c, DLWP_E_INVALID, "convlstm_cell_fwd: NULL argument");
     DLWP_REQUIRE(B > 0 && H > 0 && W > 0 && Cx > 0 && hid > 0, DLWP_E_INVALID, "convlstm_cell_fwd: bad shape (B %d, H %d, W %d, Cx %d, hidden %d)",
                  B, H, W, Cx, hid);
-    DLWP_REQUIRE(pad_ok(pad_h) && pad_ok(pad_w), DLWP_E_INVALID, "convlstm_cell_fwd: unknown padding code (%d, %d)", pad_h, pad_w);
+    const int mode = pad_mode("convlstm_cell_fwd", pad_h, pad_w, B, H, W);
+    if (mode < 0) return mode;
     DLWP_REQUIRE((long long)B * H * W < (1ll << 31), DLWP_E_UNSUPPORTED, "convlstm_cell_fwd: more than 2^31 pixels");
     ConvArgs a{};
     a.x1 = x; a.x2 = h_prev; a.wimg = wimg; a.bias = bias; a.y1 = h; a.c_prev = c_prev; a.c_out = c; a.gates = gates;
@@ -441,8 +544,8 @@ extern "C" int dlwp_convlstm_cell_fwd(const float* x, const float* h_prev, const
     hipStream_t s = (hipStream_t)stream_;
     const double px = (double)B * H * W;
     dlwp_prof_scope ps(s, 2.0 * px * 9 * (Cx + a.C2) * 4 * hid, 4.0 * (px * (Cx + a.C2 + 3 * hid + (gates ? 4 * hid : 0)) + 36.0 * (Cx + hid) * hid),
-                       "convlstm_cell_fwd");
-    return launch_conv<4, true>(a, nblk, s);
+                       mode == MODE_HPX ? "convlstm_cell_hpx_fwd" : "convlstm_cell_fwd");
+    return mode == MODE_HPX ? launch_conv<4, true, MODE_HPX>(a, nblk, s) : launch_conv<4, true, MODE_STD>(a, nblk, s);
 }
 
 extern "C" int dlwp_convlstm_gate_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev, const float* c,
@@ -485,7 +588,8 @@ extern "C" int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float*
     DLWP_REQUIRE(B > 0 && H > 0 && W > 0 && C1 > 0 && C2 >= 0 && Cout > 0, DLWP_E_INVALID,
                  "conv3x3_wgrad: bad shape (B %d, H %d, W %d, C %d + %d, Cout %d)", B, H, W, C1, C2, Cout);
     DLWP_REQUIRE((C2 == 0) == (x2 == nullptr), DLWP_E_INVALID, "conv3x3_wgrad: the second input and its channel count go together");
-    DLWP_REQUIRE(pad_ok(pad_h) && pad_ok(pad_w), DLWP_E_INVALID, "conv3x3_wgrad: unknown padding code (%d, %d)", pad_h, pad_w);
+    const int mode = pad_mode("conv3x3_wgrad", pad_h, pad_w, B, H, W);
+    if (mode < 0) return mode;
     DLWP_REQUIRE((long long)B * H * W < (1ll << 31), DLWP_E_UNSUPPORTED, "conv3x3_wgrad: more than 2^31 pixels");
     WgradArgs a{};
     a.x1 = x1; a.x2 = x2; a.dz = dz; a.ws = ws;
@@ -496,8 +600,11 @@ extern "C" int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float*
     const double px = (double)B * H * W;
     const int Cin = C1 + C2;
     {
-        dlwp_prof_scope ps(s, 2.0 * px * 9 * Cin * Cout, 4.0 * (px * (Cin + Cout) + (double)a.S * 9 * a.cin_pad * a.cout_pad), "conv3x3_wgrad");
-        hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3(a.cin_pad / KC, a.cout_pad / 64, a.S), dim3(256), 0, s, a);
+        dlwp_prof_scope ps(s, 2.0 * px * 9 * Cin * Cout, 4.0 * (px * (Cin + Cout) + (double)a.S * 9 * a.cin_pad * a.cout_pad),
+                           mode == MODE_HPX ? "conv3x3_hpx_wgrad" : "conv3x3_wgrad");
+        const dim3 grid(a.cin_pad / KC, a.cout_pad / 64, a.S);
+        if (mode == MODE_HPX) hipLaunchKernelGGL(conv3x3_wgrad_kernel<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(conv3x3_wgrad_kernel<false>, grid, dim3(256), 0, s, a);
         DLWP_LAUNCH_CHECK();
     }
     {
@@ -505,6 +612,63 @@ extern "C" int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float*
         dlwp_prof_scope ps(s, (double)a.S * n, 4.0 * (a.S + 2.0) * n, "conv3x3_wgrad_fold");
         hipLaunchKernelGGL(conv3x3_wgrad_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, gw, gb, Cin, Cout, a.S,
                            a.cin_pad, a.cout_pad);
+        DLWP_LAUNCH_CHECK();
+    }
+    return DLWP_OK;
+}
+
+// ---- HEALPix
+extern "C" int dlwp_hpx_halo_sources(int n, int* out) {
+    DLWP_REQUIRE(out, DLWP_E_INVALID, "hpx_halo_sources: NULL argument");
+    DLWP_REQUIRE(n >= 1 && n <= 4096, DLWP_E_INVALID, "hpx_halo_sources: bad face size %d", n);
+    for (int f = 0; f < hpx::FACES; ++f)
+        for (int pr = 0; pr < n + 2; ++pr)
+            for (int pc = 0; pc < n + 2; ++pc) {
+                if (pr != 0 && pr != n + 1 && pc != 0 && pc != n + 1) continue;
+                int* o = out + ((long long)f * (4 * n + 4) + hpx::ring_cell(n, pr, pc)) * 2;
+                hpx::halo_sources(n, f, pr, pc, o, o + 1);
+            }
+    return DLWP_OK;
+}
+
+extern "C" long long dlwp_conv3x3_hpx_dgrad_ws_floats(int B, int n, int Cin) {
+    if (B <= 0 || B % hpx::FACES != 0 || n < 2 || Cin <= 0) {
+        dlwp_set_error("conv3x3_hpx_dgrad_ws_floats: bad shape (B %d, face size %d, Cin %d)", B, n, Cin);
+        return DLWP_E_INVALID;
+    }
+    return (long long)B * (n + 2) * (n + 2) * Cin;
+}
+
+extern "C" int dlwp_conv3x3_hpx_dgrad(const float* dz, const float* wimg, const int* table, float* ws, float* g1, float* g2, int B,
+                                      int n, int Cout, int C1, int C2, void* stream_) {
+    DLWP_REQUIRE(dz && wimg && table && ws && (g1 || g2), DLWP_E_INVALID, "conv3x3_hpx_dgrad: NULL argument");
+    DLWP_REQUIRE(B > 0 && Cout > 0 && C1 > 0 && C2 >= 0, DLWP_E_INVALID, "conv3x3_hpx_dgrad: bad shape (B %d, face size %d, Cout %d, C %d + %d)",
+                 B, n, Cout, C1, C2);
+    DLWP_REQUIRE(B % hpx::FACES == 0 && n >= 2, DLWP_E_INVALID,
+                 "conv3x3_hpx_dgrad: HEALPix padding needs 12 square faces of at least 2 x 2 pixels per sphere (B %d, face size %d)", B, n);
+    DLWP_REQUIRE(!g2 || C2 > 0, DLWP_E_INVALID, "conv3x3_hpx_dgrad: a destination without columns");
+    const int np = n + 2, C = C1 + C2;
+    DLWP_REQUIRE((long long)B * np * np < (1ll << 31), DLWP_E_UNSUPPORTED, "conv3x3_hpx_dgrad: more than 2^31 pixels");
+    ConvArgs a{};
+    a.x1 = dz; a.wimg = wimg; a.y1 = ws;
+    a.C1 = Cout; a.N1 = C; a.act = ACT_NONE;
+    a.B = B; a.H = np; a.W = np; a.pad_h = a.pad_w = PAD_HEALPIX;
+    a.tiles_h = ceil_div(np, TH); a.tiles_w = ceil_div(np, TW);
+    int NS, nblk;
+    image_geometry(C, Cout, IMG_DGRAD, &NS, &nblk, &a.nchunks);
+    a.img_chunks = a.nchunks;
+    hipStream_t s = (hipStream_t)stream_;
+    const double px = (double)B * np * np;
+    {
+        dlwp_prof_scope ps(s, 2.0 * px * 9 * Cout * C, 4.0 * ((double)B * n * n * Cout + px * C + 9.0 * Cout * C),
+                           NS == 1 ? "conv3x3_hpx_dgrad_n16" : "conv3x3_hpx_dgrad_n64");
+        const int rc = NS == 1 ? launch_conv<1, false, MODE_HPX_DGRAD>(a, nblk, s) : launch_conv<4, false, MODE_HPX_DGRAD>(a, nblk, s);
+        if (rc) return rc;
+    }
+    {
+        const long long nel = (long long)B * n * n * C;
+        dlwp_prof_scope ps(s, 4.0 * nel, 4.0 * (px * C + nel), "conv3x3_hpx_fold");
+        hipLaunchKernelGGL(conv3x3_hpx_fold_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s, ws, table, g1, g2, B, n, C1, C);
         DLWP_LAUNCH_CHECK();
     }
     return DLWP_OK;

@@ -25,7 +25,7 @@ class UNet(nn.Module):
                  n_convolutions=2, activation="th.nn.ReLU()", context_size=1, mesh="equirectangular", device=None, **kwargs):
         super().__init__()
         if mesh != "equirectangular":
-            raise NotImplementedError("only the equirectangular mesh is on the MI355X hot path (healpix needs dgl)")
+            raise NotImplementedError("UNet is built on the equirectangular mesh only (the HEALPix U-Net is not built yet)")
         hs, n = check_unet_config(hidden_channels, n_convolutions)
         if context_size < 1:
             raise ValueError("context_size must be >= 1: the first frame needs an initial condition")
@@ -50,7 +50,7 @@ class UNet(nn.Module):
 
 
 class UNetHPX(UNet):
-    """The reference's HEALPix variant: not built (its layers need dgl)."""
+    """The reference's HEALPix variant: not built yet (the 3 x 3 kernels have the padding, conv_ops "healpix"; the class is a follow-up)."""
 
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("UNetHPX runs on the HEALPix mesh, which is not on the MI355X hot path (it needs dgl)")
+        raise NotImplementedError("UNetHPX, the U-Net on the HEALPix mesh, is not built yet")

@@ -20,20 +20,36 @@ class _Slot(nn.Module):
         return x
 
 
+class Layers(nn.Module):
+    """The shape of the reference's HEALPixLayer: the convolution at index 1 of a Sequential NAMED `layers`, behind its padding
+    module (key `layers.1.weight`)."""
+
+    def __init__(self, conv):
+        super().__init__()
+        self.layers = nn.Sequential(_Slot(), conv)
+
+    @property
+    def conv(self):
+        return self.layers[1]
+
+
 class ConvLSTMCell(nn.Module):
     """One cell: `conv` is the 3 x 3 convolution `2 hidden -> 4 hidden` over `cat(x, h_prev)`; the states are plain
     attributes (not buffers), zeroed by `reset_states`.  wrap_conv: the reference's dlwpbench cell keeps the convolution at
-    index 1 of a Sequential behind its padding module (key `conv.1.weight`)."""
+    index 1 of a Sequential behind its padding module (key `conv.1.weight`); wrap_conv="layers": its HEALPix cell keeps it in a
+    HEALPixLayer (key `conv.layers.1.weight`)."""
 
     def __init__(self, input_size, hidden_size, bias=True, pad_modes=("circular", "circular"), wrap_conv=False):
         super().__init__()
         self.input_size, self.hidden_size, self.pad_modes = input_size, hidden_size, tuple(pad_modes)
         conv = Conv3x3(input_size + hidden_size, 4 * hidden_size, bias=bias, pad_modes=pad_modes)
-        self.conv = nn.Sequential(_Slot(), conv) if wrap_conv else conv
+        self.conv = Layers(conv) if wrap_conv == "layers" else (nn.Sequential(_Slot(), conv) if wrap_conv else conv)
         self.h = self.c = None
 
     @property
     def layer(self):
+        if isinstance(self.conv, Layers):
+            return self.conv.conv
         return self.conv[1] if isinstance(self.conv, nn.Sequential) else self.conv
 
     def reset_states(self, batch_size=None):

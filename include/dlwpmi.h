@@ -960,7 +960,8 @@ int dlwp_comm_broadcast(dlwp_comm* comm, float* buf, long long n, int root, void
 /* nn.Conv2d(kernel_size=3, padding=1, padding_mode="circular") of src/nsbench/models/convlstm/convlstm.py */
 /* (:31-39, :105-128) and the CylinderPad + nn.Conv2d pairs of src/dlwpbench/models/convlstm/convlstm.py.   */
 /* Activations are channels-last fp32 [B][H][W][C]; fp32 operands on the exact-fp32 MFMA, fp32 sums.        */
-/* Codes: padding per axis 0 = zeros, 1 = circular; activation 0 = none, 1 = tanh, 2 = relu;                */
+/* Codes: padding per axis 0 = zeros, 1 = circular, 2 = HEALPix (both axes at once, see below);            */
+/* activation 0 = none, 1 = tanh, 2 = relu;                                                                */
 /* image kind 0 = forward, 1 = forward of a cell weight (gate columns interleaved), 2 = input gradient.    */
 /* No padded tensor and no cat(x, h_prev) is ever written: the halo is resolved while a tile is staged.    */
 /*                                                                                                         */
@@ -998,6 +999,29 @@ int dlwp_conv3x3_act_bwd(const float* y, const float* gy, float* dz, long long n
 long long dlwp_conv3x3_wgrad_ws_floats(int B, int H, int W, int Cin, int Cout);
 int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float* dz, float* ws, float* gw, float* gb, int B,
                        int H, int W, int C1, int C2, int Cout, int pad_h, int pad_w, void* stream);
+/* HEALPix padding (code 2 on BOTH axes; HEALPixPadding(1) of src/dlwpbench/utils/healpix.py in front of    */
+/* every nn.Conv2d(3) of a HEALPixLayer): B = 12 * spheres square faces [B][n][n][C], face index fastest.  */
+/* Every cell of the one-pixel ring around a face is one pixel of a neighbour face (some faces are seen     */
+/* rotated) or, for the top-left / bottom-right corner cell of the four equatorial faces, the mean of two;  */
+/* dlwp_conv3x3_fwd, dlwp_convlstm_cell_fwd and dlwp_conv3x3_wgrad resolve it while they stage a tile.       */
+/* They refuse (DLWP_E_INVALID) the code on one axis only, B % 12 != 0, H != W and H < 2.                   */
+/*                                                                                                         */
+/* HOST function, no GPU: out [12][4 n + 4][2] <- the source pixels ((face * n + y) * n + x within the       */
+/* sphere; second entry -1 unless the cell is a mean of two) of every ring cell, from the closed form the    */
+/* kernels run.  Ring cell order of the padded (n + 2) x (n + 2) face: top row, bottom row, then the left    */
+/* and the right column without their corners.                                                             */
+int dlwp_hpx_halo_sources(int n, int* out);
+/* Input gradient under HEALPix padding: dx = P^T (full transposed convolution of dz), which is NOT the      */
+/* convolution with the flipped weight and the same padding.  Two launches: the kind 2 image product over    */
+/* the padded domain of every face into ws [B][n + 2][n + 2][C1 + C2] (dlwp_conv3x3_hpx_dgrad_ws_floats),     */
+/* then a gather that WRITES g1 [B][n][n][C1] and g2 [..][C2] (either may be NULL): every pixel takes its     */
+/* interior value plus, in the table's order, the ring cells that read it -- no atomics, repeated launches   */
+/* are bit-identical.  table: device int [12][4 n - 4][4], per border pixel of a face (top row, bottom row,  */
+/* left, right column without corners) up to four entries (cell << 1) | half with                           */
+/* cell = (face * (n + 2) + pr) * (n + 2) + pc within the sphere and half = 1 for weight 0.5; -1 = none.      */
+long long dlwp_conv3x3_hpx_dgrad_ws_floats(int B, int n, int Cin);
+int dlwp_conv3x3_hpx_dgrad(const float* dz, const float* wimg, const int* table, float* ws, float* g1, float* g2,
+                           int B, int n, int Cout, int C1, int C2, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* The U-Net layers that are not 3 x 3 convolutions (csrc/unet_ops.hip): AvgPool2d(2, 2), ConvTranspose2d(2, 2)  */

@@ -9,6 +9,14 @@ threads, and -- where torch's own convolution runs on the card -- the helper on 
 library"; a failure there is reported in the line, nothing is retried).
 
     python tools/bench_convlstm.py [--widths 2x16,4x57,4x162] [--steps 10] [--out profiles/convlstm_step.json] [--append]
+
+`--mesh healpix` times `dlwpbench.ConvLSTMHPX` instead, and `--mesh equirectangular` `dlwpbench.ConvLSTM` beside it, at the
+reference's training protocol (src/dlwpbench/configs/training/default.yaml: batch 16, sequence 5; model/convlstm.yaml: 4
+constant, 1 prescribed, 8 prognostic channels, context 1): widths 2 x 16 (the shipped config) and 4 x 228 (the published
+"16M"), face sizes 8 and 32 with 16 spheres per batch, the equirectangular grid 32 x 64 with 16 samples.  One JSON line per
+width and grid with the graphed step and the per-kernel accounting of one eager step; the helper models are not timed here.
+
+    python tools/bench_convlstm.py --mesh healpix [--widths 2x16,4x228] [--faces 8,32] --out profiles/convlstm_hpx_step.json
 """
 import argparse
 import json
@@ -49,9 +57,78 @@ def helper_step_seconds(params, x, y, device, reps):
     return statistics.median(times)
 
 
+DLWP_B, DLWP_SEQ, DLWP_CH = 16, 5, dict(constant_channels=4, prescribed_channels=1, prognostic_channels=8, context_size=1)
+
+
+def accounting_rows(acc):
+    total_ms = sum(r["ms"] for r in acc.rows)
+    rows = [{"name": r["name"], "calls": r["calls"], "ms": round(r["ms"], 3), "tflops": round(r["flops"] / (r["ms"] * 1e9), 2) if r["ms"] else 0.0,
+             "fraction_of_fp32_matrix_roof": round(r["flops"] / (r["ms"] * 1e9) / ROOF_TFLOPS, 4) if r["ms"] else 0.0,
+             "fraction_of_8TBs": round(r["bytes"] / (r["ms"] * 1e9) / ROOF_TBS, 4) if r["ms"] else 0.0,
+             "share_of_kernel_time": round(r["ms"] / total_ms, 4)} for r in acc.rows]
+    return rows, total_ms
+
+
+def timed_steps(step, warmup, steps):
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(steps, 10)):
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    return statistics.median(times) * 1e3, len(times)
+
+
+def dlwp_lines(a, dev, lines):
+    """the dlwpbench ConvLSTM on either mesh: one line per width and grid"""
+    from dlwp_benchmark_amd import dlwpbench, lib as L
+    from dlwp_benchmark_amd.train_engine import GraphedTrainStep
+    hpx = a.mesh == "healpix"
+    grids = [(12, int(f), int(f)) for f in a.faces.split(",")] if hpx else [(32, 64)]
+    for spec in (a.widths or "2x16,4x228").split(","):
+        n, h = (int(v) for v in spec.split("x"))
+        for grid in grids:
+            torch.manual_seed(0)
+            g = torch.Generator().manual_seed(1)
+            r = lambda t, c: torch.randn(DLWP_B, t, c, *grid, generator=g).to(dev)      # noqa: E731
+            kw = {"constants": r(1, DLWP_CH["constant_channels"]), "prescribed": r(DLWP_SEQ, DLWP_CH["prescribed_channels"]),
+                  "prognostic": r(DLWP_SEQ, DLWP_CH["prognostic_channels"])}
+            yd = r(DLWP_SEQ - DLWP_CH["context_size"], DLWP_CH["prognostic_channels"])
+            cls = dlwpbench.ConvLSTMHPX if hpx else dlwpbench.ConvLSTM
+            model = cls(batch_size=DLWP_B, hidden_sizes=[h] * n, height=grid[-2], width=grid[-1], device=dev, **DLWP_CH).train()
+            line = {"model": f"dlwpbench.{cls.__name__} {n} x {h}", "mesh": a.mesh, "parameters": sum(p.numel() for p in model.parameters()),
+                    "batch": DLWP_B, "grid": list(grid), "pixels_per_sample": int(torch.tensor(grid).prod()), "sequence": DLWP_SEQ,
+                    "context_size": DLWP_CH["context_size"], "precision": "fp32"}
+            for _ in range(2):
+                model.zero_grad(set_to_none=True)
+                with L.kernel_accounting() as acc:
+                    torch.nn.functional.mse_loss(model(**kw), yd).backward()
+                    torch.cuda.synchronize()
+            line["eager_step_kernels"], total_ms = accounting_rows(acc)
+            line["eager_step_kernel_ms"] = round(total_ms, 3)
+            model.zero_grad(set_to_none=True)
+            step = GraphedTrainStep(model, kw, yd, lr=1e-3)
+            ms, ntimed = timed_steps(step, a.warmup, a.steps)
+            line.update({"step_ms": round(ms, 3), "samples_per_s": round(DLWP_B / ms * 1e3, 2), "steps_timed": ntimed,
+                         "us_per_pixel_frame": round(ms * 1e3 / (DLWP_B * line["pixels_per_sample"] * DLWP_SEQ), 5),
+                         "loss": float(step.loss.item())})
+            del step, model
+            lines.append(line)
+            print(json.dumps(line), flush=True)
+            os.makedirs(os.path.dirname(a.out), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(lines, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--widths", default="2x16,4x57,4x162")
+    ap.add_argument("--mesh", default="ns", choices=["ns", "healpix", "equirectangular"],
+                    help="ns: the nsbench model (default); healpix / equirectangular: dlwpbench.ConvLSTMHPX / dlwpbench.ConvLSTM")
+    ap.add_argument("--faces", default="8,32", help="--mesh healpix: face sizes")
+    ap.add_argument("--widths", default=None, help="LAYERSxWIDTH,...; default 2x16,4x57,4x162 (ns) or 2x16,4x228 (dlwpbench)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cpu-reps", type=int, default=1)
@@ -66,7 +143,9 @@ def main():
     if a.append and os.path.exists(a.out):
         with open(a.out) as f:
             lines = json.load(f)
-    for spec in a.widths.split(","):
+    if a.mesh != "ns":
+        return dlwp_lines(a, dev, lines)
+    for spec in (a.widths or "2x16,4x57,4x162").split(","):
         n, h = (int(v) for v in spec.split("x"))
         torch.manual_seed(0)
         g = torch.Generator().manual_seed(1)
@@ -83,27 +162,13 @@ def main():
             with L.kernel_accounting() as acc:
                 torch.nn.functional.mse_loss(model(xd, TF), yd).backward()
                 torch.cuda.synchronize()
-        total_ms = sum(r["ms"] for r in acc.rows)
-        line["eager_step_kernels"] = [
-            {"name": r["name"], "calls": r["calls"], "ms": round(r["ms"], 3), "tflops": round(r["flops"] / (r["ms"] * 1e9), 2) if r["ms"] else 0.0,
-             "fraction_of_fp32_matrix_roof": round(r["flops"] / (r["ms"] * 1e9) / ROOF_TFLOPS, 4) if r["ms"] else 0.0,
-             "fraction_of_8TBs": round(r["bytes"] / (r["ms"] * 1e9) / ROOF_TBS, 4) if r["ms"] else 0.0,
-             "share_of_kernel_time": round(r["ms"] / total_ms, 4)} for r in acc.rows]
+        line["eager_step_kernels"], total_ms = accounting_rows(acc)
         line["eager_step_kernel_ms"] = round(total_ms, 3)
         model.zero_grad(set_to_none=True)
         # ---- the graphed step
         step = GraphedTrainStep(model, {"x": xd}, yd, lr=1e-3, call=lambda m, kw: m(kw["x"], TF))
-        for _ in range(a.warmup):
-            step()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(max(a.steps, 10)):
-            t0 = time.perf_counter()
-            step()
-            torch.cuda.synchronize()
-            times.append(time.perf_counter() - t0)
-        ms = statistics.median(times) * 1e3
-        line.update({"step_ms": round(ms, 3), "samples_per_s": round(B / ms * 1e3, 2), "steps_timed": len(times),
+        ms, ntimed = timed_steps(step, a.warmup, a.steps)
+        line.update({"step_ms": round(ms, 3), "samples_per_s": round(B / ms * 1e3, 2), "steps_timed": ntimed,
                      "loss": float(step.loss.item())})
         del step
         # ---- the helper on the host CPU (16 threads) and, if torch's convolution runs there, on the card
