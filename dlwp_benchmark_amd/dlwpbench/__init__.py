@@ -1,6 +1,7 @@
 """Mirror of src/dlwpbench/models/__init__.py for the hot-path models."""
 from .convlstm import ConvLSTM, ConvLSTMHPX  # noqa: F401
 from .fno import FNO2DModule, TFNO2DModule  # noqa: F401
+from .graphcast import GraphCastNet  # noqa: F401
 from .fourcastnet import AFNONet, FourCastNet, FourCastNetv2, SFNONet  # noqa: F401
 from .meshgraphnet import MeshGraphNet  # noqa: F401
 from .panguweather import PanguWeather  # noqa: F401
@@ -9,4 +10,4 @@ from .swin_transformer import SwinTransformer  # noqa: F401
 from .unet import UNet, UNetHPX  # noqa: F401
 
 __all__ = ["FNO2DModule", "TFNO2DModule", "SFNO2DModule", "AFNONet", "FourCastNet", "FourCastNetv2", "SFNONet", "PanguWeather",
-           "SwinTransformer", "ConvLSTM", "ConvLSTMHPX", "UNet", "UNetHPX", "MeshGraphNet"]
+           "SwinTransformer", "ConvLSTM", "ConvLSTMHPX", "UNet", "UNetHPX", "MeshGraphNet", "GraphCastNet"]

@@ -34,9 +34,16 @@ class GraphMlpArgs(C.Structure):
                    ("act", C.c_int), ("der", C.c_void_p * 3)])
 
 
+class GraphWideOperand(C.Structure):
+    """dlwp_graph_wide_operand (include/dlwpmi.h)"""
+    _fields_ = ([(n, C.c_int) for n in ("mode", "B", "Ns", "Nd", "E")] + [("rows", C.c_longlong)]
+                + [(n, C.c_void_p) for n in ("x", "vs", "vd", "src", "dst")] + [(n, C.c_int) for n in ("D0", "D1", "D2")])
+
+
 GRAPH_MAX_WIDTH, GRAPH_MAX_HIDDEN_LAYERS = 128, 3      # DLWP_GRAPH_MAX_WIDTH, DLWP_GRAPH_MAX_HIDDEN_LAYERS
 GRAPH_ROWS, GRAPH_EDGE, GRAPH_NODE = 0, 1, 2
 GRAPH_ACT = {"relu": 0, "silu": 1}      # DLWP_GRAPH_ACT_RELU, DLWP_GRAPH_ACT_SILU
+GRAPH_WIDE_MAX_WIDTH, GRAPH_WIDE_ACT_NONE = 512, -1      # DLWP_GRAPH_WIDE_MAX_WIDTH, DLWP_GRAPH_WIDE_ACT_NONE
 
 # parameter kinds of the flat FNO parameter buffer (dlwpmi.h enum)
 P_LIFT_W1, P_LIFT_B1, P_LIFT_W2, P_LIFT_B2, P_PROJ_W1, P_PROJ_B1, P_PROJ_W2, P_PROJ_B2, \
@@ -234,6 +241,15 @@ SIGNATURES = {
     "dlwp_graph_dgrad_mul": (_I, [_V] * 4 + [_L, _I, _I, _V]),
     "dlwp_graph_gather_sum": (_I, [_V, _V, _V, _I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _V]),
     "dlwp_graph_edge_gather": (_I, [_V] * 5 + [_I] * 4 + [_V]),
+    "dlwp_graph_wide_linear_fwd": (_I, [C.POINTER(GraphWideOperand)] + [_V] * 5 + [_I, _I, _V]),
+    "dlwp_graph_wide_ln_fwd": (_I, [_V] * 7 + [_L, _I, _F, _V]),
+    "dlwp_graph_wide_ln_bwd_ws_floats": (_L, [_L, _I]),
+    "dlwp_graph_wide_ln_bwd": (_I, [_V] * 8 + [_L, _I, _V]),
+    "dlwp_graph_wide_wgrad0_ws_floats": (_L, [C.POINTER(GraphWideOperand), _I]),
+    "dlwp_graph_wide_wgrad0": (_I, [C.POINTER(GraphWideOperand)] + [_V] * 4 + [_I, _V]),
+    "dlwp_graph_wide_dgrad": (_I, [C.POINTER(GraphWideOperand)] + [_V] * 4 + [_I] + [_V] * 3 + [_I, _V]),
+    "dlwp_graph_wide_gather_sum": (_I, [_V, _V, _V, _I, _V, _V, _I, _I, _I, _I, _V]),
+    "dlwp_graph_wide_edge_gather": (_I, [_V] * 5 + [_I] * 4 + [_V]),
     "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),
     "dlwp_debug_null_kernels": (_I, [_I, _I, _V]),
     "dlwp_debug_spin_kernels": (_I, [_I, _I, _I, _I, _I, _V]),

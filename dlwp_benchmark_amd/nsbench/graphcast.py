@@ -7,7 +7,8 @@ plus n-hop shortcut edges with [dir_y, dir_x, dist] features (mgn_graph.build_nh
 in the reference's order here -- node_encoder, edge_encoder, processor, node_decoder --, which is not MeshGraphNet's.  The edge
 encoder's input is the same for every time step: it runs once per `forward`.
 
-The dlwpbench GraphCastNet (icosphere mesh file, bipartite grid-to-mesh and mesh-to-grid graphs, hidden_dim 512) is not built.
+The dlwpbench GraphCastNet (icosphere mesh file, bipartite grid-to-mesh and mesh-to-grid graphs, hidden_dim 512) is another model on
+another kernel family: dlwpbench/graphcast.py.
 """
 import torch
 import torch.nn as nn

@@ -1130,6 +1130,65 @@ int dlwp_graph_gather_sum(const float* in1, const int* ptr1, const int* eid1, in
 int dlwp_graph_edge_gather(const float* in, const int* dst, const int* in_ptr, const float* add, float* out, int B, int N,
                            int E, int C, void* stream);
 
+/* ---- wide, bipartite graph kernels of the dlwpbench GraphCastNet (csrc/graph_wide.hip) ---------------------------- */
+/* The row MLPs above at widths 1..DLWP_GRAPH_WIDE_MAX_WIDTH, one Linear per launch on a (64 rows x 64 | 128 columns) */
+/* grid, on graphs whose source and destination nodes are different sets (Ns, Nd nodes; the mesh graph: Ns == Nd and   */
+/* vs == vd).  Reference: MeshGraphMLP / MeshGraphEdgeMLPConcat (mesh_graph_mlp.py), concat_efeat and                 */
+/* aggregate_and_concat (utils.py) of src/dlwpbench/models/graphcast/gnn_layers/.  Layout, index arrays and            */
+/* reproducibility as above: fp32 rows, int32 arrays of ONE sample's graph, no atomics.  Nothing above changes:        */
+/* DLWP_GRAPH_MAX_WIDTH stays 128.                                                                                    */
+#define DLWP_GRAPH_WIDE_MAX_WIDTH 512
+#define DLWP_GRAPH_WIDE_ACT_NONE (-1)
+/* The operand rows of a first Linear, assembled while they are staged (the concatenation is never written):         */
+/*   rows  A[r] = x[r]                                         (x [rows][D0])                                         */
+/*   edge  A[r] = x[r] | vs[b Ns + src[k]] | vd[b Nd + dst[k]]   (x = e [B E][D0], vs [B Ns][D1], vd [B Nd][D2])        */
+/*   node  A[r] = x[r] | vs[r]                                 (x = agg [B Nd][D0] from dlwp_graph_wide_gather_sum,   */
+/*                                                              vs = v [B Nd][D1])                                    */
+/* Every part is 1..512 wide, so the fan-in K = D0 [+ D1 [+ D2]] is at most 1536.  Entry points that read shapes only */
+/* (dlwp_graph_wide_dgrad, *_ws_floats) ignore the pointers.                                                          */
+typedef struct dlwp_graph_wide_operand {
+    int mode, B, Ns, Nd, E;
+    long long rows;                     /* rows mode only; edge: B E, node: B Nd */
+    const float *x, *vs, *vd;
+    const int *src, *dst;
+    int D0, D1, D2;
+} dlwp_graph_wide_operand;
+/* y [rows][N] = act(A . w^T + b) [+ res]: w [N][K] and b [N] (nullable) are nn.Linear's own arrays; act             */
+/* DLWP_GRAPH_WIDE_ACT_NONE, DLWP_GRAPH_ACT_RELU or DLWP_GRAPH_ACT_SILU; res [rows][N] nullable.  der (nullable, SiLU */
+/* only) receives the derivative rows d = s (1 + v (1 - s)).                                                          */
+int dlwp_graph_wide_linear_fwd(const dlwp_graph_wide_operand* op, const float* w, const float* b, const float* res, float* y,
+                               float* der, int N, int act, void* stream);
+/* y = LayerNorm(z) gamma + beta [+ res] over rows of width C (biased variance, one wave per row); xhat [rows][C] and  */
+/* rstd [rows] (both or neither) receive the normalised rows and 1 / sigma for dlwp_graph_wide_ln_bwd.                */
+int dlwp_graph_wide_ln_fwd(const float* z, const float* gamma, const float* beta, const float* res, float* y, float* xhat,
+                           float* rstd, long long rows, int C, float eps, void* stream);
+/* WRITES dz [rows][C]; ggamma / gbeta (each nullable) are ACCUMULATED into from per-workgroup column sums folded in   */
+/* workgroup order.  ws: dlwp_graph_wide_ln_bwd_ws_floats floats.                                                     */
+long long dlwp_graph_wide_ln_bwd_ws_floats(long long rows, int C);
+int dlwp_graph_wide_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* dz, float* ws,
+                           float* ggamma, float* gbeta, long long rows, int C, void* stream);
+/* gw [N][K] += dz^T . A, gb [N] += column sums of dz (NULL: none), A gathered as in the forward.  ws: scratch of      */
+/* dlwp_graph_wide_wgrad0_ws_floats(op, N) floats (per-workgroup partial sums, folded in a fixed order).  A later      */
+/* Linear's operand is stored rows: dlwp_conv1x1_wgrad takes them at any width.                                       */
+long long dlwp_graph_wide_wgrad0_ws_floats(const dlwp_graph_wide_operand* op, int N);
+int dlwp_graph_wide_wgrad0(const dlwp_graph_wide_operand* op, const float* dz, float* ws, float* gw, float* gb, int N,
+                           void* stream);
+/* dA = dz [rows][N] . w [N][K], WRITTEN in parts (each nullable except rows' out0):                                  */
+/*   rows  out0 = dx [rows][D0], times mul [rows][D0] (nullable; mask != 0: kept where mul > 0, else zero -- ReLU's    */
+/*         mask from the stored post-activation rows), + res                                                          */
+/*   edge  out0 = de [B E][D0] (+ res), out1 = per-edge d_src [B E][D1], out2 = per-edge d_dst [B E][D2]               */
+/*   node  out0 = d_agg [B Nd][D0], out1 = dv [B Nd][D1] (+ res)                                                       */
+int dlwp_graph_wide_dgrad(const dlwp_graph_wide_operand* op, const float* dz, const float* w, const float* res, const float* mul,
+                          int mask, float* out0, float* out1, float* out2, int N, void* stream);
+/* out[b N + i] = [add[b N + i]] + sum_j in[b E + eid[j]] (ptr[i] <= j < ptr[i+1], in list order; mean != 0: divided   */
+/* by the count), rows of width C, onto ONE node set of N nodes: the forward aggregation (in-CSR, Nd), and dv of an    */
+/* edge block as two launches (out-CSR of d_src onto the Ns sources, in-CSR of d_dst onto the Nd destinations).        */
+int dlwp_graph_wide_gather_sum(const float* in, const int* ptr, const int* eid, int mean, const float* add, float* out, int B,
+                               int N, int E, int C, void* stream);
+/* out[b E + k] = [add[b E + k]] + in[b N + dst[k]] (in_ptr != NULL: divided by the in-degree of dst[k]).              */
+int dlwp_graph_wide_edge_gather(const float* in, const int* dst, const int* in_ptr, const float* add, float* out, int B, int N,
+                                int E, int C, void* stream);
+
 /* bench probe: ONE forward `spatial` launch of an inner FNO block as the rollout issues it     */
 /* (x = previous pre-activation, GELU on load; spec = [B][m1][m2c][C][2] mixed modes; fused      */
 /* W-axis DFT of gelu(pre) into x1_out [B][H][m2c][C][2]).                                       */

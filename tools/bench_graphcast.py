@@ -13,6 +13,12 @@ after 20 warm-up launches, median microseconds per launch; the operands (<= 10 M
 they do inside a step.
 
     python tools/bench_graphcast.py [--steps 10] [--out profiles/graphcast_step.json]
+
+`--model dlwp`: the dlwpbench GraphCastNet instead, at its shipped config (tests/golden/shipped_graphcast_dlwp_model_config.json:
+hidden_dim 512, 16 processor layers, 32 x 64 grid) on a level-3 icosphere file this tool writes itself (the reference ships none),
+B 1, 3 frames (context 1: two lead times).  Same line -- graphed step, accounting of one eager step, the plain-torch helper
+(tests/graphcast_dlwp_ref.py, fp32) on the same card -- without the dgrad_mul comparison; default output
+profiles/graphcast_dlwp_step.json.
 """
 import argparse
 import json
@@ -94,12 +100,106 @@ def dgrad_mul_against_the_pair(dev, rows, width):
             "conv1x1_dgrad_alone_us": round(d, 2), "pair_over_fused": round(p / f, 3)}
 
 
+def accounting_rows(acc):
+    total_ms = sum(r["ms"] for r in acc.rows)
+    return total_ms, [
+        {"name": r["name"], "calls": r["calls"], "ms": round(r["ms"], 3), "tflops": round(r["flops"] / (r["ms"] * 1e9), 3) if r["ms"] else 0.0,
+         "fraction_of_fp32_matrix_roof": round(r["flops"] / (r["ms"] * 1e9) / ROOF_TFLOPS, 4) if r["ms"] else 0.0,
+         "fraction_of_8TBs": round(r["bytes"] / (r["ms"] * 1e9) / ROOF_TBS, 4) if r["ms"] else 0.0,
+         "share_of_kernel_time": round(r["ms"] / total_ms, 4)} for r in acc.rows]
+
+
+def main_dlwp(a):
+    """the dlwpbench GraphCastNet at its shipped config"""
+    import tempfile
+
+    import graphcast_dlwp_ref as R
+    from dlwp_benchmark_amd import dlwpbench, gc_mesh, lib as L
+    from dlwp_benchmark_amd.train_engine import GraphedTrainStep
+    torch.set_num_threads(16)
+    dev = torch.device("cuda:0")
+    with open(os.path.join(ROOT, "tests", "golden", "shipped_graphcast_dlwp_model_config.json")) as f:
+        entry = json.load(f)["dlwpbench/graphcast"]
+    cfg, frames = dict(entry["kwargs"]), 3
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, f"icospheres_l{entry['icosphere_level']}.json")
+        gc_mesh.write_icospheres(path, entry["icosphere_level"])
+        torch.manual_seed(0)
+        model = dlwpbench.GraphCastNet(device=dev, **dict(cfg, meshgraph_path=path)).train()
+        graphs = gc_mesh.build_graphs(*gc_mesh.load_icospheres(path), cfg["input_height"], cfg["input_width"])
+    inputs, target = R.make_inputs(cfg, frames, torch.Generator().manual_seed(1))
+    params = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    line = {"model": "dlwpbench.GraphCastNet", "config": cfg, "parameters": sum(v.numel() for v in params.values()), "batch": 1,
+            "frames": frames, "grid": [model.height, model.width], "precision": "fp32",
+            "graphs": {k: {"sources": g.num_src, "destinations": g.num_dst, "edges": g.num_edges} for k, g in model.graphs.items()}}
+    ind, yd = {k: v.to(dev) for k, v in inputs.items()}, target.to(dev)
+    call = lambda m, kw: m(kw["constants"], kw["prescribed"], kw["prognostic"])      # noqa: E731
+
+    def save():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump([line], f, indent=1)
+
+    for _ in range(2):
+        model.zero_grad(set_to_none=True)
+        with L.kernel_accounting() as acc:
+            torch.nn.functional.mse_loss(call(model, ind), yd).backward()
+            torch.cuda.synchronize()
+    total_ms, line["eager_step_kernels"] = accounting_rows(acc)
+    line["eager_step_kernel_ms"] = round(total_ms, 3)
+    line["eager_step_launches"] = sum(r["calls"] for r in acc.rows)
+    model.zero_grad(set_to_none=True)
+    step = GraphedTrainStep(model, ind, yd, lr=1e-3, call=call)
+    for _ in range(a.warmup):
+        step()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(a.steps, 10)):
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    ms = statistics.median(times) * 1e3
+    line.update({"step_ms": round(ms, 3), "step_ms_min": round(min(times) * 1e3, 3), "step_ms_max": round(max(times) * 1e3, 3),
+                 "samples_per_s": round(1 / ms * 1e3, 2), "steps_timed": len(times), "loss": float(step.loss.item())})
+    del step
+    line["torch_gpu_helper"] = "not reached"
+    save()
+    try:      # the helper's step: forward + backward + Adam in plain torch on the same card, fp32
+        p = {k: v.detach().clone().to(dev).requires_grad_(True) for k, v in params.items()}
+        opt = torch.optim.Adam(list(p.values()), lr=1e-3)
+        net = R.RefGraphCast(graphs, p, cfg)
+        htimes = []
+        for i in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            opt.zero_grad(set_to_none=True)
+            torch.nn.functional.mse_loss(net(ind["constants"], ind["prescribed"], ind["prognostic"]), yd).backward()
+            opt.step()
+            torch.cuda.synchronize()
+            if i:
+                htimes.append(time.perf_counter() - t0)
+        gpu_s = statistics.median(htimes)
+        del line["torch_gpu_helper"]
+        line.update({"torch_gpu_helper_step_ms": round(gpu_s * 1e3, 2), "torch_gpu_helper_samples_per_s": round(1 / gpu_s, 2),
+                     "speedup_over_torch_gpu_helper": round(gpu_s * 1e3 / ms, 2)})
+    except Exception as e:      # noqa: BLE001 -- reported, not retried
+        line["torch_gpu_helper"] = f"did not run: {type(e).__name__}: {str(e)[:200]}"
+    print(json.dumps(line), flush=True)
+    save()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("ns", "dlwp"), default="ns")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "graphcast_step.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "graphcast_dlwp_step.json" if a.model == "dlwp" else "graphcast_step.json")
+    if a.model == "dlwp":
+        return main_dlwp(a)
     import graphcast_ref as R
     from dlwp_benchmark_amd import lib as L, nsbench
     from dlwp_benchmark_amd.train_engine import GraphedTrainStep
@@ -128,12 +228,7 @@ def main():
         with L.kernel_accounting() as acc:
             torch.nn.functional.mse_loss(call(model, ind), yd).backward()
             torch.cuda.synchronize()
-    total_ms = sum(r["ms"] for r in acc.rows)
-    line["eager_step_kernels"] = [
-        {"name": r["name"], "calls": r["calls"], "ms": round(r["ms"], 3), "tflops": round(r["flops"] / (r["ms"] * 1e9), 3) if r["ms"] else 0.0,
-         "fraction_of_fp32_matrix_roof": round(r["flops"] / (r["ms"] * 1e9) / ROOF_TFLOPS, 4) if r["ms"] else 0.0,
-         "fraction_of_8TBs": round(r["bytes"] / (r["ms"] * 1e9) / ROOF_TBS, 4) if r["ms"] else 0.0,
-         "share_of_kernel_time": round(r["ms"] / total_ms, 4)} for r in acc.rows]
+    total_ms, line["eager_step_kernels"] = accounting_rows(acc)
     line["eager_step_kernel_ms"] = round(total_ms, 3)
     line["eager_step_launches"] = sum(r["calls"] for r in acc.rows)
     model.zero_grad(set_to_none=True)
