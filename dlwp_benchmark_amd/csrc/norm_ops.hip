@@ -50,17 +50,21 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     const float* xr = x + (long long)row * C;
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += xr[c];
-    const float mu = wave_sum64(s) / C;
-    float v = 0.f;
-    for (int c = lane; c < C; c += 64) { const float d = xr[c] - mu; v += d * d; }
-    const float rs = rsqrtf(wave_sum64(v) / C + eps);
+    // The fp32 sum of a row that sits at 1e3 loses ~1e-4 of its mean, and that shift times rstd gamma reaches y (1e-5 of its max
+    // norm).  The deviations d = x - mu0 are small and exact to their own rounding: their mean r is what the sum lost, taken in the
+    // variance pass -- mean = mu0 + r, deviations d - r, variance mean(d^2) - r^2 (r^2 << variance: no cancellation).
+    const float mu0 = wave_sum64(s) / C;
+    float v = 0.f, e = 0.f;
+    for (int c = lane; c < C; c += 64) { const float d = xr[c] - mu0; v += d * d; e += d; }
+    const float r = wave_sum64(e) / C;
+    const float rs = rsqrtf(fmaxf(wave_sum64(v) / C - r * r, 0.f) + eps);
     if (y_bf16) {         // the output feeds a GEMM under bf16 storage: rounded once here instead of in every tile load
         __bf16* yh = reinterpret_cast<__bf16*>(y);
-        for (int c = lane; c < C; c += 64) yh[(long long)row * C + c] = (__bf16)((xr[c] - mu) * rs * gamma[c] + beta[c]);
+        for (int c = lane; c < C; c += 64) yh[(long long)row * C + c] = (__bf16)((xr[c] - mu0 - r) * rs * gamma[c] + beta[c]);
     } else {
-        for (int c = lane; c < C; c += 64) y[(long long)row * C + c] = (xr[c] - mu) * rs * gamma[c] + beta[c];
+        for (int c = lane; c < C; c += 64) y[(long long)row * C + c] = (xr[c] - mu0 - r) * rs * gamma[c] + beta[c];
     }
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+    if (lane == 0) { mean[row] = mu0 + r; rstd[row] = rs; }
 }
 
 // Wide rows (256 < C <= 1024, C % 4 == 0): the row is read ONCE into NV float4 groups per lane (the scalar kernel above walks it
@@ -83,15 +87,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const float* __
         v[q] = *reinterpret_cast<const f32x4*>(xr + (ok[q] ? c : 0));
         if (ok[q]) s += (v[q][0] + v[q][1]) + (v[q][2] + v[q][3]);
     }
-    const float mu = wave_sum64(s) / C;
-    float var = 0.f;
+    const float mu0 = wave_sum64(s) / C;
+    float var = 0.f, e = 0.f;
 #pragma unroll
     for (int q = 0; q < NV; ++q)
         if (ok[q]) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { const float d = v[q][k] - mu; var += d * d; }
+            for (int k = 0; k < 4; ++k) { v[q][k] -= mu0; var += v[q][k] * v[q][k]; e += v[q][k]; }
         }
-    const float rs = rsqrtf(wave_sum64(var) / C + eps);
+    const float r = wave_sum64(e) / C;           // what the fp32 row sum lost (layernorm_fwd_kernel): mean = mu0 + r
+    const float rs = rsqrtf(fmaxf(wave_sum64(var) / C - r * r, 0.f) + eps);
 #pragma unroll
     for (int q = 0; q < NV; ++q)
         if (ok[q]) {
@@ -99,14 +104,22 @@ __global__ __launch_bounds__(256) void layernorm_fwd_wide_kernel(const float* __
             const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
             f32x4 o;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = (v[q][k] - mu) * rs * gm[k] + bt[k];
+            for (int k = 0; k < 4; ++k) o[k] = (v[q][k] - r) * rs * gm[k] + bt[k];
             if (y_bf16)
                 *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(y) + (long long)row * C + c) =
                     bf16x4{(__bf16)o[0], (__bf16)o[1], (__bf16)o[2], (__bf16)o[3]};
             else
                 *reinterpret_cast<f32x4*>(y + (long long)row * C + c) = o;
         }
-    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+    if (lane == 0) { mean[row] = mu0 + r; rstd[row] = rs; }
+}
+
+// a * b rounded to fp32 whatever consumes it: the empty statement keeps -ffp-contract=fast from fusing the product into a later
+// addition (an fma would use the unrounded product there and the rounded one elsewhere)
+__device__ __forceinline__ float rounded_product(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return p;
 }
 
 // gx = rstd * (g*gamma - mean(g*gamma) - xhat * mean(g*gamma*xhat)) (+ gadd: the gradient that reached x along the residual
@@ -163,7 +176,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         for (int q = 0; q < NQ; ++q) {
             const float g0 = okc[q] ? gv[q] : 0.f;
             xh[q] = okc[q] ? (xv[q] - mu) * rs : 0.f;
-            const float gg = g0 * gam[q];
+            const float gg = rounded_product(g0, gam[q]);
             s1 += gg;
             s2 += gg * xh[q];
             pg[q] += g0 * xh[q];
@@ -174,7 +187,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 #pragma unroll
         for (int q = 0; q < NQ; ++q)
             if (okc[q]) {
-                const float o1 = rs * (gv[q] * gam[q] - s1 - xh[q] * s2) + av[q];
+                // the rounded product that went into s1, not one fused into the subtraction: a row of one column has s1 == g gamma and
+                // gx == gadd exactly, where the fused form left rstd (1e3) times the product's rounding error
+                const float o1 = rs * (rounded_product(gv[q], gam[q]) - s1 - xh[q] * s2) + av[q];
                 gx[(long long)row * C + lane + 64 * q] = o1;
                 if (lp.out) lp.out[(long long)row * C + lane + 64 * q] = (__bf16)(o1 * ln_lowp_scale(lp, row));
             }
@@ -241,11 +256,15 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const float* __r
     f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f}, gm = v, bt = v;
     if (ok) v = *reinterpret_cast<const f32x4*>(x + row * C + 4 * l);
     if (okc) { gm = *reinterpret_cast<const f32x4*>(gamma + 4 * l); bt = *reinterpret_cast<const f32x4*>(beta + 4 * l); }
-    const float mu = row_sum<LPR>((v[0] + v[1]) + (v[2] + v[3])) / C;
+    const float mu0 = row_sum<LPR>((v[0] + v[1]) + (v[2] + v[3])) / C;
     f32x4 d;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d[k] = okc ? v[k] - mu : 0.f;
-    const float rs = rsqrtf(row_sum<LPR>((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) / C + eps);
+    for (int k = 0; k < 4; ++k) d[k] = okc ? v[k] - mu0 : 0.f;
+    const float r = row_sum<LPR>((d[0] + d[1]) + (d[2] + d[3])) / C;       // what the fp32 row sum lost (layernorm_fwd_kernel)
+    const float m2 = row_sum<LPR>((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) / C;
+    const float mu = mu0 + r, rs = rsqrtf(fmaxf(m2 - r * r, 0.f) + eps);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = okc ? d[k] - r : 0.f;
     if (ok) {
         f32x4 o;
 #pragma unroll
@@ -276,20 +295,21 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vecn_kernel(const float* __
         s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
     }
     const float invC = 1.f / C;
-    const float mu = row_sum<LPR>(s) * invC;
-    float var = 0.f;
+    const float mu0 = row_sum<LPR>(s) * invC;
+    float var = 0.f, e = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { v[c][k] -= mu; var += v[c][k] * v[c][k]; }
-    const float rs = rsqrtf(row_sum<LPR>(var) * invC + eps);
+        for (int k = 0; k < 4; ++k) { v[c][k] -= mu0; var += v[c][k] * v[c][k]; e += v[c][k]; }
+    const float r = row_sum<LPR>(e) * invC;      // what the fp32 row sum lost (layernorm_fwd_kernel): mean = mu0 + r
+    const float mu = mu0 + r, rs = rsqrtf(fmaxf(row_sum<LPR>(var) * invC - r * r, 0.f) + eps);
     if (ok) {
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * l + CS * c), bt = *reinterpret_cast<const f32x4*>(beta + 4 * l + CS * c);
             f32x4 q;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) q[k] = v[c][k] * rs * gm[k] + bt[k];
+            for (int k = 0; k < 4; ++k) q[k] = (v[c][k] - r) * rs * gm[k] + bt[k];
             if (y_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(y) + o + CS * c) = bf16x4{(__bf16)q[0], (__bf16)q[1], (__bf16)q[2], (__bf16)q[3]};
             else *reinterpret_cast<f32x4*>(y + o + CS * c) = q;
         }
