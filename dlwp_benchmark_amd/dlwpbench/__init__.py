@@ -6,8 +6,8 @@ from .fourcastnet import AFNONet, FourCastNet, FourCastNetv2, SFNONet  # noqa: F
 from .meshgraphnet import MeshGraphNet  # noqa: F401
 from .panguweather import PanguWeather  # noqa: F401
 from .sfno import SFNO2DModule  # noqa: F401
-from .swin_transformer import SwinTransformer  # noqa: F401
+from .swin_transformer import SwinTransformer, SwinTransformerHPX  # noqa: F401
 from .unet import UNet, UNetHPX  # noqa: F401
 
 __all__ = ["FNO2DModule", "TFNO2DModule", "SFNO2DModule", "AFNONet", "FourCastNet", "FourCastNetv2", "SFNONet", "PanguWeather",
-           "SwinTransformer", "ConvLSTM", "ConvLSTMHPX", "UNet", "UNetHPX", "MeshGraphNet", "GraphCastNet"]
+           "SwinTransformer", "SwinTransformerHPX", "ConvLSTM", "ConvLSTMHPX", "UNet", "UNetHPX", "MeshGraphNet", "GraphCastNet"]

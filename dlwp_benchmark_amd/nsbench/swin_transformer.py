@@ -469,6 +469,11 @@ class PatchEmbed(nn.Module):
             x = self.norm(x.flatten(2).transpose(1, 2)).transpose(1, 2).reshape(-1, self.embed_dim, Wh, Ww)
         return x
 
+    def forward_rows(self, rows):
+        """the same on rows [M, C*ph*pw] that are already unfolded (hpx_ops.faces_to_tokens): GEMM + norm -> tokens [M, E]"""
+        x = self.proj.forward_rows(rows)
+        return self.norm(x) if self.norm is not None else x
+
 
 def absolute_position_tokens(embed, Wh, Ww):
     """`ape=True` (reference nsbench :640-643, dlwpbench :650-653): the [1, E, Wh0, Ww0] embedding as [1, Wh*Ww, E] tokens,

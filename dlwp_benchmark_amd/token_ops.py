@@ -1133,6 +1133,11 @@ class PatchConv2d(nn.Conv2d):
         y = _LinearFn.apply(cols, self.weight, self.bias, act, None, False)
         return y.reshape(B, h, w, self.out_channels).permute(0, 3, 1, 2)
 
+    def forward_rows(self, rows, act=0):
+        """rows [M, C*ph*pw] already unfolded in the weight's K order (hpx_ops.faces_to_tokens) -> [M, O]: the GEMM alone."""
+        assert rows.dim() == 2 and rows.shape[1] == self.weight[0].numel(), (tuple(rows.shape), tuple(self.weight.shape))
+        return _LinearFn.apply(rows, self.weight, self.bias, act, None, False)
+
     def forward_tokens(self, x, act=0):
         """1 x 1 form on channels-last tokens [B, H, W, Cin] -> [B, H, W, O]: the GEMM alone (no unfold copy)."""
         assert tuple(self.kernel_size) == (1, 1) and tuple(self.stride) == (1, 1)

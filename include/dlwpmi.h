@@ -545,6 +545,18 @@ int dlwp_window_advance_bwd(const float* g_next, const float* g_net, long long n
                             const float* g_out, long long out_batch_stride, float* g_win, float* g_delta,
                             int B, int ctx, long long frame, int delta_layout, int D, int H, int W, int ph,
                             int pw, void* stream);
+/* HEALPix faces <-> the patch tokens of the 3n x 4n canvas (csrc/hpx_canvas.hip; SwinTransformerHPX._faces2rect,  */
+/* _prepare_inputs and _reshape_output, src/dlwpbench/models/swintransformer/swin_transformer.py:826-879): face f, */
+/* pixel (y, x) sits at canvas row (f / 4) n + y, column (f % 4) n + x.  gather: up to three face tensors, each    */
+/* (pointer, batch stride in floats, channels C_k) with a dense [C_k][12][n][n] block per sample (a skipped source */
+/* is NULL with 0 channels), -> tok [B][3n/ph][4n/pw][Ctot][ph][pw], Ctot = C0 + C1 + C2 in source order: the rows  */
+/* of the patch-embedding GEMM (for patch 1 x 1 the channels-last canvas).  scatter, its adjoint: channels           */
+/* [c0, c0 + C) of a tok tensor in that layout -> dense faces [B][C][12][n][n].  Pure data movement, bit-exact.     */
+int dlwp_hpx_canvas_gather(const float* src0, long long bs0, int C0, const float* src1, long long bs1, int C1,
+                           const float* src2, long long bs2, int C2, float* tok, int B, int n, int ph, int pw,
+                           void* stream);
+int dlwp_hpx_canvas_scatter(const float* tok, float* faces, int B, int n, int ph, int pw, int Ctot, int c0, int C,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Token-level building blocks of the AFNO / Swin / Pangu blocks (nn.Linear, nn.LayerNorm, */

@@ -4,7 +4,7 @@ rollout models built on libdlwpmi's kernels, at the reference's nsbench / dlwpbe
 forward rollout + MSE + backward (autograd over the HIP ops) + one fused Adam launch on the flat parameter
 buffer, captured into a hipGraph by train_engine.GraphedTrainStep (--no-graph: eager dispatch).
 
-    python tools/bench_models.py [fno_dlwp|tfno_dlwp|fno_ctx|afno|afno_tiled|afno_fcn|afno_c5p1|swin|swin_c4|swin_dlwp|sfno|pangu|pangu_c4|all] [--steps N]
+    python tools/bench_models.py [fno_dlwp|tfno_dlwp|fno_ctx|afno|afno_tiled|afno_fcn|afno_c5p1|swin|swin_c4|swin_dlwp|swin_hpx|sfno|pangu|pangu_c4|all] [--steps N]
 """
 import argparse
 import json
@@ -54,6 +54,74 @@ def run_fno(name, module, step_fn, B, steps, warmup=3):
     print(json.dumps({"model": name, "graph": True, "gemm_precision": "fp32", "storage": "fp32", "samples_per_s": round(B * steps / dt, 2),
                       "ms_per_step": round(dt / steps * 1e3, 3), "batch": B, "loss": float(loss),
                       "n_params": sum(p.numel() for p in module.parameters())}), flush=True)
+
+
+def run_swin_hpx(a, g):
+    """The reference's published HEALPix Swin (swint16m_hpx8_d120_l3x4_h3x4): HPX8 faces, one window per face, B 16, 4 | 1 | 8
+    channels, four lead times.  Besides the graphed step line: the per-kernel accounting shares of the two canvas launches in one
+    eager step, and the time of the torch chain they replace (three face-to-canvas cats + cat + channels-last copy in front of
+    the patch embedding, permute + face split behind the head) per lead time.  Everything lands in profiles/swin_hpx_step.json."""
+    import os
+    from dlwp_benchmark_amd import lib as L
+    from dlwp_benchmark_amd.train_engine import mse_loss
+    dev, B, T, n = torch.device("cuda:0"), 16, 5, 8
+    cfg = dict(constant_channels=4, prescribed_channels=1, prognostic_channels=8, context_size=1, img_height=8, img_width=8, patch_size=1,
+               embed_dim=120, depths=[4, 4, 4], num_heads=[4, 4, 4], drop_path_rate=0.0)
+    r = lambda *s: torch.randn(*s, generator=g).to(dev)      # noqa: E731
+    kw = dict(constants=r(B, 1, 4, 12, n, n), prescribed=r(B, T, 1, 12, n, n), prognostic=r(B, T, 8, 12, n, n))
+    target = r(B, T - 1, 8, 12, n, n)
+    name = f"dlwpbench SwinTransformerHPX HPX8 p1 E120 depths[4,4,4] one face per window B{B} T{T}"
+    model = dlwpbench.SwinTransformerHPX(**cfg).to(dev).train()
+    step = GraphedTrainStep(model, kw, target, lr=1e-3, use_graph=not a.no_graph)
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        loss = step()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    rec = {"model": name, "graph": not a.no_graph, "gemm_precision": PRECISION, "storage": STORAGE, "samples_per_s": round(B * a.steps / dt, 2),
+           "ms_per_step": round(dt / a.steps * 1e3, 3), "batch": B, "lead_times": T - 1, "loss": loss.item(),
+           "n_params": sum(p.numel() for p in model.parameters())}
+    # one eager forward + backward under the library's own accounting (launches inside a capture are not recorded)
+    eager = dlwpbench.SwinTransformerHPX(**cfg).to(dev).train()
+    mse_loss(eager(**kw), target).backward()
+    torch.cuda.synchronize()
+    with L.kernel_accounting() as acc:
+        mse_loss(eager(**kw), target).backward()
+        torch.cuda.synchronize()
+    total = sum(row["ms"] for row in acc.rows)
+    rec["eager_accounted_ms"] = round(total, 4)
+    for row in acc.rows:
+        if row["name"] in ("hpx_canvas_gather", "hpx_canvas_scatter"):
+            rec[row["name"]] = {"calls": row["calls"], "ms": round(row["ms"], 4), "share_pct": round(100.0 * row["ms"] / total, 3),
+                                "GBs": round(row["bytes"] / (row["ms"] * 1e6), 1) if row["ms"] > 0 else None}
+
+    def faces2rect(x):
+        f = x.unbind(-3)
+        return torch.cat([torch.cat(f[4 * k:4 * k + 4], dim=-1) for k in range(3)], dim=-2)
+
+    def torch_chain():
+        x = torch.cat([faces2rect(kw["constants"][:, 0]), faces2rect(kw["prescribed"][:, 0:1].flatten(1, 2)),
+                       faces2rect(kw["prognostic"][:, 0:1].flatten(1, 2))], dim=1)
+        rows = x.permute(0, 2, 3, 1).contiguous()                           # the 1 x 1 patch embedding's unfold
+        y = rows[..., :8].permute(0, 3, 1, 2)                               # stands for the head's output canvas
+        return rows, torch.stack([blk for band in y.split(n, dim=-2) for blk in band.split(n, dim=-1)], dim=2)
+    for _ in range(3):
+        torch_chain()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(50):
+        torch_chain()
+    e1.record()
+    torch.cuda.synchronize()
+    rec["torch_chain_forward_ms_per_lead_time"] = round(e0.elapsed_time(e1) / 50, 4)
+    print(json.dumps(rec), flush=True)
+    out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "swin_hpx_step.json")
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
 
 
 def main():
@@ -183,6 +251,8 @@ def main():
             return kw, torch.randn(4, 4, 8, 32, 64, generator=g).to(dev), 4
         run("dlwpbench SwinTransformer 32x64 p1 E96 depths[4,4] whole-map windows B4 T5", m, batch, a.steps,
             use_graph=not a.no_graph)
+    if a.which in ("swin_hpx",):
+        run_swin_hpx(a, g)
     if a.which in ("pangu_c4",):
         m = dlwpbench.PanguWeather(constant_channels=4, prescribed_channels=1, prognostic_channels=8, embed_dim=192,
                                    num_heads=(6, 12, 12, 6), window_size=(2, 7, 7), patch_size=(1, 1), n_lat=128, n_lon=256,
