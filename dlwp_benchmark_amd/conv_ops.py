@@ -7,6 +7,10 @@ border pixels of its neighbour faces, `hpx_halo_map`); it is resolved inside the
 `cat(x, h_prev)` is ever written.  The weight
 stays `nn.Conv2d`'s `[Cout, Cin, 3, 3]` parameter; the kernels read packed images of it (`pack_weight`), which a model refreshes
 once per forward pass and shares between its time steps.  There is no CPU or torch fallback.
+
+`pack_faces=True` (HEALPix padding, faces of 1, 2, 4 or 8 pixels) routes a convolution and both its gradients to the face-packed
+kernels (csrc/conv3x3_hpx_packed.hip; dlwp_conv3x3_hpxp_*), whose tiles hold several whole faces: the levels of the HEALPix U-Net
+below its top.  The default is False: one tile per face, the only form for larger faces and for the ConvLSTM cell.
 """
 import numpy as np
 import torch
@@ -122,6 +126,30 @@ def hpx_fold_table(n):
     return table
 
 
+def hpx_fold_rows(n):
+    """The inverse of `hpx_halo_map` for every face size n >= 1, in the form `dlwp_conv3x3_hpxp_dgrad` reads, numpy int32
+    `[12, n * n, R]`: per pixel of a face (row-major, interior pixels included) the ring cells that read it, in ascending cell
+    order, entries as in `hpx_fold_table` (`(cell << 1) | half`), padded with -1.  R is the largest number of readers of one
+    pixel, at least 1: 4 for n >= 2 and 10 at n = 1, where one pixel is all four edges and corners of its face."""
+    n = int(n)
+    cells, src = hpx_halo_map(n)
+    readers = [[[] for _ in range(n * n)] for _ in range(12)]
+    for f in range(12):
+        for ci in range(cells.shape[1]):
+            pr, pc = cells[f, ci]
+            for sf, y, x, wgt in src[f, ci]:
+                if wgt > 0:
+                    readers[int(sf)][int(y) * n + int(x)].append(((((f * (n + 2)) + int(pr)) * (n + 2) + int(pc)) << 1)
+                                                                  | int(wgt == 0.5))
+    R = max(1, max(len(ents) for face in readers for ents in face))
+    table = np.full((12, n * n, R), -1, dtype=np.int32)
+    for f in range(12):
+        for p, ents in enumerate(readers[f]):
+            table[f, p, :len(ents)] = sorted(ents)
+    return table
+
+
+PACKED_FACE_SIZES = (1, 2, 4, 8)      # csrc/conv3x3_hpx_packed.hip
 _HPX_TABLES = {}
 
 
@@ -133,10 +161,35 @@ def _hpx_table(n, device):
     return _HPX_TABLES[key]
 
 
-def _input_grad(dz, dgrad_img, g1, g2, B, H, W, cout, C1, C2, pads):
+def _hpx_rows(n, device):
+    """`hpx_fold_rows(n)` on `device`, built and uploaded once"""
+    key = ("rows", int(n), str(device))
+    if key not in _HPX_TABLES:
+        _HPX_TABLES[key] = torch.from_numpy(hpx_fold_rows(int(n))).to(device)
+    return _HPX_TABLES[key]
+
+
+def _check_pack_faces(ph, pw, n):
+    """`pack_faces=True` is the HEALPix padding on faces of a packed size (ValueError otherwise)"""
+    if ph != PAD_HEALPIX or pw != PAD_HEALPIX:
+        raise ValueError("pack_faces=True needs padding='healpix': the packed kernels tile whole HEALPix faces")
+    if n > 8:
+        raise ValueError(f"pack_faces=True is for faces of at most 8 x 8 pixels, not {n} x {n}: larger faces fill the tiles of "
+                         "the default kernels")
+    if n not in PACKED_FACE_SIZES:
+        raise ValueError(f"pack_faces=True: the packed kernels are built for faces of {PACKED_FACE_SIZES} pixels, not {n}")
+
+
+def _input_grad(dz, dgrad_img, g1, g2, B, H, W, cout, C1, C2, pads, pack_faces=False):
     """the input gradient(s) of a convolution from dz: the flipped-weight product with the same padding for zeros / circular; for
     HEALPix that product over the padded domain of every face followed by the fold onto the pixels the ring cells read"""
     lib = L.load()
+    if pack_faces:
+        ws = L.workspace(lib.dlwp_conv3x3_hpxp_dgrad_ws_floats, B, H, C1 + C2, device=dz.device)
+        table = _hpx_rows(H, dz.device)
+        L.check(lib.dlwp_conv3x3_hpxp_dgrad(L.ptr(dz), L.ptr(dgrad_img), table.data_ptr(), table.shape[-1], L.ptr(ws), L.ptr(g1),
+                                            L.ptr(g2), B, H, cout, C1, C2, L.stream()))
+        return
     if pads[0] != PAD_HEALPIX:
         L.check(lib.dlwp_conv3x3_fwd(L.ptr(dz), None, L.ptr(dgrad_img), None, L.ptr(g1), L.ptr(g2), B, H, W, cout, 0, C1, C2,
                                      pads[0], pads[1], 0, L.stream()))
@@ -178,7 +231,7 @@ def _cl(t, what):
     return t.contiguous()
 
 
-def _weight_grad(x1, x2, dz, weight_shape, wslot, bslot, has_bias, pads):
+def _weight_grad(x1, x2, dz, weight_shape, wslot, bslot, has_bias, pads, pack_faces=False):
     """gW, gb of a convolution: straight into the gradient slots where they exist (returns None for those)."""
     lib = L.load()
     B, H, W, C1 = x1.shape
@@ -186,6 +239,11 @@ def _weight_grad(x1, x2, dz, weight_shape, wslot, bslot, has_bias, pads):
     cout = weight_shape[0]
     gw, gw_out = _grad_buffer(wslot, weight_shape, dz.device)
     gb, gb_out = _grad_buffer(bslot, cout, dz.device) if has_bias else (None, None)
+    if pack_faces:
+        ws = L.workspace(lib.dlwp_conv3x3_hpxp_wgrad_ws_floats, B, H, C1 + C2, cout, device=dz.device)
+        L.check(lib.dlwp_conv3x3_hpxp_wgrad(L.ptr(x1), L.ptr(x2), L.ptr(dz), L.ptr(ws), L.ptr(gw), L.ptr(gb), B, H, C1, C2, cout,
+                                            L.stream()))
+        return gw_out, gb_out
     ws = L.workspace(lib.dlwp_conv3x3_wgrad_ws_floats, B, H, W, C1 + C2, cout, device=dz.device)
     L.check(lib.dlwp_conv3x3_wgrad(L.ptr(x1), L.ptr(x2), L.ptr(dz), L.ptr(ws), L.ptr(gw), L.ptr(gb), B, H, W, C1, C2, cout,
                                    pads[0], pads[1], L.stream()))
@@ -194,7 +252,7 @@ def _weight_grad(x1, x2, dz, weight_shape, wslot, bslot, has_bias, pads):
 
 class _Conv3x3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x1, x2, weight, bias, packed, pad_h, pad_w, act):
+    def forward(ctx, x1, x2, weight, bias, packed, pad_h, pad_w, act, pack_faces=False):
         lib = L.load()
         x1 = _cl(x1, "conv3x3")
         x2 = _cl(x2, "conv3x3") if x2 is not None else None
@@ -204,10 +262,17 @@ class _Conv3x3Fn(torch.autograd.Function):
         if weight.shape[1] != C1 + C2 or (x2 is not None and x2.shape[:3] != x1.shape[:3]):
             raise L.DlwpError(f"conv3x3: weight {tuple(weight.shape)} does not fit inputs with {C1} + {C2} channels")
         y = torch.empty(B, H, W, cout, device=x1.device)
-        L.check(lib.dlwp_conv3x3_fwd(L.ptr(x1), L.ptr(x2), L.ptr(packed.fwd), L.ptr(bias), L.ptr(y), None, B, H, W, C1, C2, cout, 0,
-                                     pad_h, pad_w, act, L.stream()))
+        if pack_faces:
+            if H != W:
+                raise ValueError(f"HEALPix faces are square, not {H} x {W}")
+            _check_pack_faces(pad_h, pad_w, H)
+            L.check(lib.dlwp_conv3x3_hpxp_fwd(L.ptr(x1), L.ptr(x2), L.ptr(packed.fwd), L.ptr(bias), L.ptr(y), None, B, H, W, C1, C2,
+                                              cout, 0, act, L.stream()))
+        else:
+            L.check(lib.dlwp_conv3x3_fwd(L.ptr(x1), L.ptr(x2), L.ptr(packed.fwd), L.ptr(bias), L.ptr(y), None, B, H, W, C1, C2, cout, 0,
+                                         pad_h, pad_w, act, L.stream()))
         ctx.save_for_backward(x1, x2, y if act else None)
-        ctx.packed, ctx.pads, ctx.act = packed, (pad_h, pad_w), act
+        ctx.packed, ctx.pads, ctx.act, ctx.pack_faces = packed, (pad_h, pad_w), act, pack_faces
         ctx.wshape, ctx.has_bias = weight.shape, bias is not None
         ctx.wslot = _grad_slot(weight)
         ctx.bslot = _grad_slot(bias) if bias is not None else None
@@ -231,25 +296,31 @@ class _Conv3x3Fn(torch.autograd.Function):
         if need1 or need2:
             if ctx.packed.dgrad is None:
                 raise L.DlwpError("conv3x3: this weight was packed without its input-gradient image")
-            _input_grad(dz, ctx.packed.dgrad, g1, g2, B, H, W, cout, C1, C2, ctx.pads)
+            _input_grad(dz, ctx.packed.dgrad, g1, g2, B, H, W, cout, C1, C2, ctx.pads, ctx.pack_faces)
         gw = gb = None
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            gw, gb = _weight_grad(x1, x2, dz, ctx.wshape, ctx.wslot, ctx.bslot, ctx.has_bias, ctx.pads)
-        return g1, g2, gw, gb, None, None, None, None
+            gw, gb = _weight_grad(x1, x2, dz, ctx.wshape, ctx.wslot, ctx.bslot, ctx.has_bias, ctx.pads, ctx.pack_faces)
+        return g1, g2, gw, gb, None, None, None, None, None
 
 
-def conv3x3(x, weight, bias=None, padding="zeros", act=None, x2=None, packed=None):
+def conv3x3(x, weight, bias=None, padding="zeros", act=None, x2=None, packed=None, pack_faces=False):
     """`act(conv2d(cat(x, x2), weight, bias))`, 3 x 3, stride 1, same size, on channels-last `[B, H, W, C]` tensors.
     padding: "zeros" / "circular" or a (height, width) pair, or "healpix" (`B = 12 * spheres` square faces); act: None / "tanh" /
     "relu"; packed: the weight's PackedWeight
-    (built here when absent: two more launches)."""
+    (built here when absent: two more launches).  pack_faces=True (HEALPix padding, faces of 1, 2, 4 or 8 pixels; ValueError
+    otherwise): forward, input gradient and weight gradient run the face-packed kernels (csrc/conv3x3_hpx_packed.hip), whose
+    tiles hold several whole faces -- the same weight images, the same results up to the order of the fold's additions."""
     _check_weight(weight)
     ph, pw = _pad_codes(padding)
     if act not in ACT:
         raise ValueError(f"act must be None, 'tanh' or 'relu', not {act!r}")
+    if pack_faces:
+        if x.dim() != 4 or x.shape[1] != x.shape[2]:
+            raise ValueError(f"pack_faces=True needs square faces [12 * spheres, n, n, C], not {tuple(x.shape)}")
+        _check_pack_faces(ph, pw, x.shape[1])
     if packed is None:
         packed = PackedWeight(weight, need_grad=torch.is_grad_enabled())
-    return _Conv3x3Fn.apply(x, x2, weight, bias, packed, ph, pw, ACT[act])
+    return _Conv3x3Fn.apply(x, x2, weight, bias, packed, ph, pw, ACT[act], bool(pack_faces))
 
 
 class _ConvLSTMCellFn(torch.autograd.Function):
@@ -325,7 +396,7 @@ class Conv3x3(nn.Conv2d):
     padding, default from `padding_mode` ("zeros" / "circular" on both axes); `("healpix", "healpix")` for a HEALPix layer."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, padding_mode="zeros", bias=True, pad_modes=None,
-                 act=None, **kw):
+                 act=None, pack_faces=False, **kw):
         ks = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
         if ks != 3 or padding not in (1, (1, 1)) or padding_mode not in ("zeros", "circular"):
             raise ValueError("Conv3x3: kernel_size 3, padding 1 and padding_mode 'zeros' / 'circular' only")
@@ -337,12 +408,15 @@ class Conv3x3(nn.Conv2d):
         if act not in ACT:
             raise ValueError(f"act must be None, 'tanh' or 'relu', not {act!r}")
         self.act = act
+        if pack_faces and _pad_codes(self.pad_modes) != (PAD_HEALPIX, PAD_HEALPIX):
+            raise ValueError("Conv3x3: pack_faces=True needs pad_modes=('healpix', 'healpix')")
+        self.pack_faces = bool(pack_faces)
 
     def pack(self, cell=False):
         return PackedWeight(self.weight, cell=cell, need_grad=torch.is_grad_enabled())
 
     def forward_cl(self, x, x2=None, packed=None):
-        return conv3x3(x, self.weight, self.bias, self.pad_modes, self.act, x2=x2, packed=packed)
+        return conv3x3(x, self.weight, self.bias, self.pad_modes, self.act, x2=x2, packed=packed, pack_faces=self.pack_faces)
 
     def forward(self, x):
         return self.forward_cl(x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)

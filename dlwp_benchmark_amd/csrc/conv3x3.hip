@@ -607,13 +607,15 @@ extern "C" int dlwp_conv3x3_wgrad(const float* x1, const float* x2, const float*
         else hipLaunchKernelGGL(conv3x3_wgrad_kernel<false>, grid, dim3(256), 0, s, a);
         DLWP_LAUNCH_CHECK();
     }
-    {
-        const long long n = (long long)9 * (Cin + 1) * Cout;
-        dlwp_prof_scope ps(s, (double)a.S * n, 4.0 * (a.S + 2.0) * n, "conv3x3_wgrad_fold");
-        hipLaunchKernelGGL(conv3x3_wgrad_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, gw, gb, Cin, Cout, a.S,
-                           a.cin_pad, a.cout_pad);
-        DLWP_LAUNCH_CHECK();
-    }
+    return dlwp_conv3x3_wgrad_fold(ws, gw, gb, Cin, Cout, a.S, a.cin_pad, a.cout_pad, s);
+}
+
+int dlwp_conv3x3_wgrad_fold(const float* ws, float* gw, float* gb, int Cin, int Cout, int S, int cin_pad, int cout_pad, hipStream_t s) {
+    const long long n = (long long)9 * (Cin + 1) * Cout;
+    dlwp_prof_scope ps(s, (double)S * n, 4.0 * (S + 2.0) * n, "conv3x3_wgrad_fold");
+    hipLaunchKernelGGL(conv3x3_wgrad_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ws, gw, gb, Cin, Cout, S, cin_pad,
+                       cout_pad);
+    DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
 

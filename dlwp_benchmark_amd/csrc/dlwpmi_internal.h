@@ -24,6 +24,11 @@ struct dlwp_prof_scope {
     dlwp_prof_scope& operator=(const dlwp_prof_scope&) = delete;
 };
 
+// conv3x3.hip -- conv3x3_wgrad_fold_kernel's launch (with its accounting row), shared with conv3x3_hpx_packed.hip:
+// gw[co][ci][tap] += sum_s ws[s][tap][ci][co], gb[co] += sum_s ws[s][centre][Cin][co] in the fixed order s = 0..S-1
+int dlwp_conv3x3_wgrad_fold(const float* ws, float* gw, float* gb, int Cin, int Cout, int S, int cin_pad, int cout_pad,
+                            hipStream_t stream);
+
 // pwmlp.hip — strided/gathered channel views, optional residual and fused MSE gradient
 int dlwp_pwmlp_fwd_ex(const dlwp_chan_src* x, const float* w1, const float* b1, const float* w2,
                       const float* b2, const dlwp_chan_dst* y, const dlwp_chan_src* res, int B,

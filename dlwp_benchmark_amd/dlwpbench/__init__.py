@@ -7,7 +7,8 @@ from .meshgraphnet import MeshGraphNet  # noqa: F401
 from .panguweather import PanguWeather  # noqa: F401
 from .sfno import SFNO2DModule  # noqa: F401
 from .swin_transformer import SwinTransformer, SwinTransformerHPX  # noqa: F401
-from .unet import UNet, UNetHPX  # noqa: F401
+from .unet import UNet, UNetHEALPix, UNetHPX, model_class  # noqa: F401
 
 __all__ = ["FNO2DModule", "TFNO2DModule", "SFNO2DModule", "AFNONet", "FourCastNet", "FourCastNetv2", "SFNONet", "PanguWeather",
-           "SwinTransformer", "SwinTransformerHPX", "ConvLSTM", "ConvLSTMHPX", "UNet", "UNetHPX", "MeshGraphNet", "GraphCastNet"]
+           "SwinTransformer", "SwinTransformerHPX", "ConvLSTM", "ConvLSTMHPX", "UNet", "UNetHPX", "UNetHEALPix", "MeshGraphNet", "GraphCastNet",
+           "model_class"]

@@ -224,6 +224,11 @@ SIGNATURES = {
     "dlwp_hpx_halo_sources": (_I, [_I, _V]),
     "dlwp_conv3x3_hpx_dgrad_ws_floats": (_L, [_I] * 3),
     "dlwp_conv3x3_hpx_dgrad": (_I, [_V] * 6 + [_I] * 5 + [_V]),
+    "dlwp_conv3x3_hpxp_fwd": (_I, [_V] * 6 + [_I] * 8 + [_V]),
+    "dlwp_conv3x3_hpxp_dgrad_ws_floats": (_L, [_I] * 3),
+    "dlwp_conv3x3_hpxp_dgrad": (_I, [_V] * 3 + [_I] + [_V] * 3 + [_I] * 5 + [_V]),
+    "dlwp_conv3x3_hpxp_wgrad_ws_floats": (_L, [_I] * 4),
+    "dlwp_conv3x3_hpxp_wgrad": (_I, [_V] * 6 + [_I] * 5 + [_V]),
     "dlwp_avgpool2x2_fwd": (_I, [_V, _V] + [_I] * 4 + [_V]),
     "dlwp_avgpool2x2_bwd": (_I, [_V, _V] + [_I] * 4 + [_V]),
     "dlwp_conv1x1_fwd": (_I, [_V] * 4 + [_L, _I, _I, _V]),

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from ..conv_ops import PAD, Conv1x1, Conv3x3, UpConv2x2, avg_pool2x2
 from ..rollout_ops import ns_rollout
-from .convlstm import _Slot
+from .convlstm import Layers, _Slot
 
 ACTIVATIONS = {"th.nn.ReLU()": "relu", "torch.nn.ReLU()": "relu", "nn.ReLU()": "relu",
                "th.nn.Tanh()": "tanh", "torch.nn.Tanh()": "tanh", "nn.Tanh()": "tanh"}
@@ -54,6 +54,8 @@ def run_level(layer, x, packs, skip=None):
     """The modules of one level's Sequential on a channels-last tensor; with `skip` the first convolution reads
     `skip | x` as two tensors (the decoder's concatenation)."""
     for m in layer:
+        if isinstance(m, Layers):
+            m = m.conv
         if isinstance(m, _Pool):
             x = avg_pool2x2(x)
         elif isinstance(m, Conv3x3):
@@ -66,9 +68,10 @@ def run_level(layer, x, packs, skip=None):
 
 class UNetEncoder(nn.Module):
     """levels of [pool (not at the top),] n x (3 x 3 convolution + activation); the bottom level runs n // 2 of them.
-    slots_before: parameter-free modules in front of every convolution (1 in dlwpbench: the reference's CylinderPad)."""
+    slots_before: parameter-free modules in front of every convolution (1 in dlwpbench: the reference's CylinderPad).
+    wrap: a module class that takes the convolution's slot and holds it (Layers: the reference's HEALPixLayer)."""
 
-    def __init__(self, in_channels, hidden_channels, n_convolutions, act, conv_kw, slots_before=0):
+    def __init__(self, in_channels, hidden_channels, n_convolutions, act, conv_kw, slots_before=0, wrap=None):
         super().__init__()
         channels = [in_channels] + list(hidden_channels)
         layers = []
@@ -77,7 +80,8 @@ class UNetEncoder(nn.Module):
             n = n_convolutions // 2 if i == len(hidden_channels) - 1 else n_convolutions
             for k in range(n):
                 layer += [_Slot() for _ in range(slots_before)]
-                layer += [Conv3x3(channels[i] if k == 0 else channels[i + 1], channels[i + 1], act=act, **conv_kw), _Slot()]
+                conv = Conv3x3(channels[i] if k == 0 else channels[i + 1], channels[i + 1], act=act, **conv_kw)
+                layer += [wrap(conv) if wrap else conv, _Slot()]
             layers.append(nn.Sequential(*layer))
         self.layers = nn.ModuleList(layers)
 
@@ -94,7 +98,7 @@ class UNetDecoder(nn.Module):
     """bottom to top: n x (3 x 3 convolution + activation) [+ 2 x 2 up-convolution (not at the top)], then the 1 x 1 output
     layer.  Above the bottom the first convolution of a level reads `skip | upsampled` as two tensors."""
 
-    def __init__(self, hidden_channels, out_channels, n_convolutions, act, conv_kw, slots_before=0):
+    def __init__(self, hidden_channels, out_channels, n_convolutions, act, conv_kw, slots_before=0, wrap=None):
         super().__init__()
         hs = list(hidden_channels)[::-1]
         layers = []
@@ -103,7 +107,8 @@ class UNetDecoder(nn.Module):
             n = n_convolutions // 2 if i == 0 else n_convolutions
             for k in range(n):
                 layer += [_Slot() for _ in range(slots_before)]
-                layer += [Conv3x3((h if i == 0 else 2 * h) if k == 0 else h, h, act=act, **conv_kw), _Slot()]
+                conv = Conv3x3((h if i == 0 else 2 * h) if k == 0 else h, h, act=act, **conv_kw)
+                layer += [wrap(conv) if wrap else conv, _Slot()]
             if i < len(hs) - 1:
                 layer.append(UpConv2x2(h, hs[i + 1]))
             layers.append(nn.Sequential(*layer))

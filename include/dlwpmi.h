@@ -1034,6 +1034,23 @@ int dlwp_hpx_halo_sources(int n, int* out);
 long long dlwp_conv3x3_hpx_dgrad_ws_floats(int B, int n, int Cin);
 int dlwp_conv3x3_hpx_dgrad(const float* dz, const float* wimg, const int* table, float* ws, float* g1, float* g2,
                            int B, int n, int Cout, int C1, int C2, void* stream);
+/* Face-packed HEALPix 3 x 3 kernels for small faces (csrc/conv3x3_hpx_packed.hip), n in {1, 2, 4, 8}: the M  */
+/* axis of a workgroup is the pixels of several whole consecutive faces of [B][n][n][C] (64 faces at n = 1,  */
+/* 32 at 2, 8 at 4, 2 at 8) instead of one 8 x 16 tile of one face.  Same packed weight images (kinds 0 and  */
+/* 2), same arithmetic.  Other n <= 8 and n > 8: DLWP_E_UNSUPPORTED; B % 12 != 0 or H != W: DLWP_E_INVALID.   */
+/* fwd: dlwp_conv3x3_fwd's arguments without the padding codes.                                              */
+int dlwp_conv3x3_hpxp_fwd(const float* x1, const float* x2, const float* wimg, const float* bias, float* y1, float* y2,
+                          int B, int H, int W, int C1, int C2, int N1, int N2, int act, void* stream);
+/* dgrad: as dlwp_conv3x3_hpx_dgrad (product over the padded domain into ws, then the gather fold), but the  */
+/* table is conv_ops.hpx_fold_rows(n): device int [12][n * n][R], per pixel of a face (row-major) the ring    */
+/* cells that read it in ascending order, (cell << 1) | half as above, -1 = none; R = 10 at n = 1, else 4.    */
+long long dlwp_conv3x3_hpxp_dgrad_ws_floats(int B, int n, int Cin);
+int dlwp_conv3x3_hpxp_dgrad(const float* dz, const float* wimg, const int* table, int R, float* ws, float* g1, float* g2,
+                            int B, int n, int Cout, int C1, int C2, void* stream);
+/* wgrad: as dlwp_conv3x3_wgrad with the packed tile walk as the K axis; ws [S][9][Cin_pad][Cout_pad].        */
+long long dlwp_conv3x3_hpxp_wgrad_ws_floats(int B, int n, int Cin, int Cout);
+int dlwp_conv3x3_hpxp_wgrad(const float* x1, const float* x2, const float* dz, float* ws, float* gw, float* gb, int B,
+                            int n, int C1, int C2, int Cout, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* The U-Net layers that are not 3 x 3 convolutions (csrc/unet_ops.hip): AvgPool2d(2, 2), ConvTranspose2d(2, 2)  */

@@ -12,6 +12,14 @@ backward on tensors of that level's shapes and accounted on their own), the same
 without this library"; a failure there is reported in the line, nothing is retried).
 
     python tools/bench_unet.py [--widths 8-16-32-64-128,...] [--steps 10] [--out profiles/unet_step.json] [--append]
+
+`--mesh healpix` times `dlwpbench.UNetHEALPix` instead: HPX8 (12 faces of 8 x 8), 16 spheres, 4 constant + 1 prescribed + 8
+prognostic channels, context_size 1, 5 frames (the protocol of tools/bench_convlstm.py --mesh healpix), the graphed step as
+above.  Widths: the first four levels of the three widths above (a fifth level does not exist below 1 x 1 faces) and the
+published 92-184-368-736.  Per width the per-kernel accounting of one eager step and the kernel time of one network call per
+level (faces of 8, 4, 2, 1 pixels) with its share.
+
+    python tools/bench_unet.py --mesh healpix [--widths ...] --out profiles/unet_hpx_step.json
 """
 import argparse
 import json
@@ -82,15 +90,104 @@ def level_kernel_ms(model, dev):
     return levels, timed(lambda: model.decoder.output_layer.forward_cl(r(H, hs[0])))
 
 
+HPX_B, HPX_FACE, HPX_SEQ = 16, 8, 5
+HPX_CH = dict(constant_channels=4, prescribed_channels=1, prognostic_channels=8, context_size=1)
+HPX_WIDTHS = "8-16-32-64,16-32-64-128,33-66-132-264,92-184-368-736"
+
+
+def hpx_level_kernel_ms(model, dev):
+    """as level_kernel_ms for the HEALPix model: [(face size, packed family?, ms)] per level, and the output layer's"""
+    from dlwp_benchmark_amd import lib as L
+    from dlwp_benchmark_amd.dlwpbench.unet import packs_faces
+    from dlwp_benchmark_amd.nsbench.unet import pack_all, run_level
+    packs = pack_all(model.encoder, model.decoder)
+    hs, n = model.hidden_channels, len(model.hidden_channels)
+    r = lambda f, c: torch.randn(HPX_B * 12, f, f, c, device=dev, requires_grad=True)      # noqa: E731
+
+    def timed(fn):
+        for _ in range(2):
+            with L.kernel_accounting() as acc:
+                out = fn()
+                out.backward(torch.randn_like(out))
+                torch.cuda.synchronize()
+        return sum(row["ms"] for row in acc.rows)
+
+    cin0 = HPX_CH["constant_channels"] + (HPX_CH["prescribed_channels"] + HPX_CH["prognostic_channels"]) * HPX_CH["context_size"]
+    levels = []
+    for lvl in range(n):
+        f = HPX_FACE >> lvl
+        enc, dec = model.encoder.layers[lvl], model.decoder.layers[n - 1 - lvl]
+        ms = timed(lambda: run_level(enc, r(f if lvl == 0 else 2 * f, cin0 if lvl == 0 else hs[lvl - 1]), packs))
+        ms += timed(lambda: run_level(dec, r(f, hs[lvl]), packs, skip=r(f, hs[lvl]) if lvl < n - 1 else None))
+        levels.append((f, packs_faces(f), ms))
+    return levels, timed(lambda: model.decoder.output_layer.forward_cl(r(HPX_FACE, hs[0])))
+
+
+def hpx_lines(a, dev, lines):
+    from dlwp_benchmark_amd import dlwpbench, lib as L
+    from dlwp_benchmark_amd.train_engine import GraphedTrainStep
+    for spec in (a.widths or HPX_WIDTHS).split(","):
+        hidden = [int(v) for v in spec.split("-")]
+        torch.manual_seed(0)
+        g = torch.Generator().manual_seed(1)
+        r = lambda t, c: torch.randn(HPX_B, t, c, 12, HPX_FACE, HPX_FACE, generator=g).to(dev)      # noqa: E731
+        kw = {"constants": r(1, HPX_CH["constant_channels"]), "prescribed": r(HPX_SEQ, HPX_CH["prescribed_channels"]),
+              "prognostic": r(HPX_SEQ, HPX_CH["prognostic_channels"])}
+        yd = r(HPX_SEQ - HPX_CH["context_size"], HPX_CH["prognostic_channels"])
+        model = dlwpbench.UNetHEALPix(hidden_channels=hidden, n_convolutions=2, activation="th.nn.ReLU()", device=dev, **HPX_CH).train()
+        line = {"model": f"dlwpbench.UNetHEALPix {spec}", "mesh": "healpix", "parameters": sum(p.numel() for p in model.parameters()),
+                "batch": HPX_B, "grid": [12, HPX_FACE, HPX_FACE], "sequence": HPX_SEQ, "context_size": HPX_CH["context_size"],
+                "precision": "fp32"}
+        for _ in range(2):
+            model.zero_grad(set_to_none=True)
+            with L.kernel_accounting() as acc:
+                torch.nn.functional.mse_loss(model(**kw), yd).backward()
+                torch.cuda.synchronize()
+        total_ms = sum(r_["ms"] for r_ in acc.rows)
+        line["eager_step_kernels"] = [
+            {"name": r_["name"], "calls": r_["calls"], "ms": round(r_["ms"], 3),
+             "tflops": round(r_["flops"] / (r_["ms"] * 1e9), 2) if r_["ms"] else 0.0,
+             "fraction_of_8TBs": round(r_["bytes"] / (r_["ms"] * 1e9) / ROOF_TBS, 4) if r_["ms"] else 0.0,
+             "share_of_kernel_time": round(r_["ms"] / total_ms, 4)} for r_ in acc.rows]
+        line["eager_step_kernel_ms"] = round(total_ms, 3)
+        levels, out_ms = hpx_level_kernel_ms(model, dev)
+        all_ms = sum(ms for _, _, ms in levels) + out_ms
+        line["kernel_ms_per_network_call_by_level"] = [{"face": f, "packed_kernels": pk, "ms": round(ms, 4), "share": round(ms / all_ms, 4)}
+                                                       for f, pk, ms in levels]
+        model.zero_grad(set_to_none=True)
+        step = GraphedTrainStep(model, kw, yd, lr=1e-3)
+        for _ in range(a.warmup):
+            step()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(max(a.steps, 10)):
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        ms = statistics.median(times) * 1e3
+        line.update({"step_ms": round(ms, 3), "step_ms_spread": round((max(times) - min(times)) * 1e3, 3),
+                     "samples_per_s": round(HPX_B / ms * 1e3, 2), "steps_timed": len(times), "loss": float(step.loss.item())})
+        del step, model
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(lines, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--widths", default="8-16-32-64-128,16-32-64-128-256,33-66-132-264-528")
+    ap.add_argument("--mesh", default="ns", choices=["ns", "healpix"], help="ns: the nsbench model (default); healpix: dlwpbench.UNetHEALPix")
+    ap.add_argument("--widths", default=None, help="default 8-16-32-64-128,16-32-64-128-256,33-66-132-264-528 (ns) or "
+                    "8-16-32-64,16-32-64-128,33-66-132-264,92-184-368-736 (healpix)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cpu-reps", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "unet_step.json"))
+    ap.add_argument("--out", default=None, help="default profiles/unet_step.json (ns) or profiles/unet_hpx_step.json (healpix)")
     ap.add_argument("--append", action="store_true", help="keep the lines already in --out (one width per invocation)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "unet_hpx_step.json" if a.mesh == "healpix" else "unet_step.json")
     from dlwp_benchmark_amd import lib as L, nsbench
     from dlwp_benchmark_amd.train_engine import GraphedTrainStep
     torch.set_num_threads(16)
@@ -99,7 +196,9 @@ def main():
     if a.append and os.path.exists(a.out):
         with open(a.out) as f:
             lines = json.load(f)
-    for spec in a.widths.split(","):
+    if a.mesh == "healpix":
+        return hpx_lines(a, dev, lines)
+    for spec in (a.widths or "8-16-32-64-128,16-32-64-128-256,33-66-132-264-528").split(","):
         hidden = [int(v) for v in spec.split("-")]
         torch.manual_seed(0)
         g = torch.Generator().manual_seed(1)
