@@ -557,6 +557,28 @@ int dlwp_hpx_canvas_gather(const float* src0, long long bs0, int C0, const float
                            void* stream);
 int dlwp_hpx_canvas_scatter(const float* tok, float* faces, int B, int n, int ph, int pw, int Ctot, int c0, int C,
                             void* stream);
+/* HEALPix <-> lat-lon remap (csrc/hpx_remap.hip; HEALPixRemap.ll2hpx / hpx2ll, data/processing/healpix_mapping.py:328-399, and   */
+/* the projection to lat-lon in front of compute_metrics, scripts/evaluate.py:71-109, 215-220).  A remap is a table of 4 source   */
+/* indices and 4 weights per output point (dlwp_benchmark_amd/hpx_geometry.py) applied to `planes` = B T C maps at once.          */
+/* PRECONDITION (the kernels cannot check device tables; the Python side checks in numpy before the upload):                      */
+/* 0 <= idx[i] < n_in, rowptr[0] = 0 <= rowptr[r] <= rowptr[r + 1], 0 <= col[e] < n_in.  idx and w are 16-byte aligned.           */
+/*   gather4: dst[p][o] = sum_{k<4} w[4o+k] src[p src_plane_stride + idx[4o+k]], p < planes, o < n_out; dst dense [planes][n_out], */
+/*            src_plane_stride >= n_in floats.  Two kernels: LDS-staged plane tiles while a plane fits 72 KiB, else global gathers */
+/*            with the taps in registers; the knob REMAP_PATH (0 auto, 1 LDS, 2 direct) forces one, a forced LDS path that does    */
+/*            not fit returns DLWP_E_UNSUPPORTED.                                                                                  */
+/*   csr    : dst[p][r] (+)= sum_{rowptr[r] <= e < rowptr[r+1]} val[e] src[p][col[e]] in ascending e, no atomics (bit-reproducible): */
+/*            the adjoint of gather4 with the transposed table; src dense [planes][n_in], dst dense [planes][n_out] (n_out rows),  */
+/*            accumulate != 0 adds to dst.                                                                                         */
+int dlwp_remap_gather4(const float* src, long long src_plane_stride, const int* idx, const float* w, float* dst,
+                       long long planes, int n_in, int n_out, void* stream);
+int dlwp_remap_csr(const float* src, const int* rowptr, const int* col, const float* val, float* dst, long long planes,
+                   int n_in, int n_out, int accumulate, void* stream);
+/* dlwp_error_moments of fields on the HEALPix mesh scored on a lat-lon grid: out / target [B][G][12][n][n] are interpolated   */
+/* through the hpx2ll table idx / w [H W][4] inside the kernel (no lat-lon tensor is written); climatology [B][G][H][W] or NULL */
+/* and row_weights [H] or NULL are on lat-lon.  moments [5][G] is ACCUMULATED into, as by dlwp_error_moments.                   */
+int dlwp_hpx_error_moments(const float* out_hpx, const float* target_hpx, const float* climatology_ll,
+                           const float* row_weights, const int* idx, const float* w, int B, int G, int n, int H, int W,
+                           float* moments, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Token-level building blocks of the AFNO / Swin / Pangu blocks (nn.Linear, nn.LayerNorm, */
