@@ -1,5 +1,5 @@
 // The two loops over the exact-fp32 MFMA (common.hip.h mfma16 / mfma16_chunk) that the row kernels share (unet_ops.hip: 1 x 1 and
-// 2 x 2 up-convolution; graph_ops.hip: the first Linear's backward), one workgroup of 4 waves each:
+// 2 x 2 up-convolution; graph_bwd.hip: the first Linear's backward; graph_wide.hip: one Linear), one workgroup of 4 waves each:
 //   row_gemm_chunks   Y[64 rows][NS*16] = A[64][K] . Wm[K][N], K in chunks of 16
 //   row_wgrad_tiles   gW = A^T . dZ with K = rows, split over S workgroups that each walk the 64-row tiles s, s + S, ...; the
 //                     partial sums are folded in the fixed order s = 0..S-1 (row_wgrad_fold_kernel), so no atomics: two launches

@@ -1,5 +1,6 @@
-"""Row MLPs on graphs over libdlwpmi (csrc/graph_ops.hip; include/dlwpmi.h dlwp_graph_*): the three blocks the reference's
-MeshGraphNet (and GraphCast) are built from -- MeshGraphMLP, MeshEdgeBlock, MeshNodeBlock of models/graphcast/gnn_layers/.
+"""Row MLPs on graphs over libdlwpmi (csrc/graph_ops.hip forward, csrc/graph_bwd.hip backward; include/dlwpmi.h dlwp_graph_*): the
+three blocks the reference's MeshGraphNet (and GraphCast) are built from -- MeshGraphMLP, MeshEdgeBlock, MeshNodeBlock of
+models/graphcast/gnn_layers/.
 
 Activations are fp32 row-major `[rows, width]`: node features `[B * N, D]`, edge features `[B * E, D]`, sample after sample.  A
 `Graph` holds the int32 index arrays of ONE sample's graph on the device; the kernels form row `b * N + i` / `b * E + k`
@@ -14,7 +15,8 @@ post-ReLU rows.  SiLU is not monotone, so its derivative cannot be read off `z s
 derivative rows, and the backward of a later Linear is ONE launch, `dz_{l-1} = (dz_l . W_l) * d_{l-1}` (dlwp_graph_dgrad_mul).
 
 Every width above is 1..128.  The second half of the module is the wide, bipartite family of the dlwpbench GraphCastNet
-(csrc/graph_wide.hip, dlwp_graph_wide_*): `BipartiteGraph`, `wide_graph_mlp`, `wide_edge_block`, `wide_node_block` at widths 1..512.
+(csrc/graph_wide.hip forward, the same csrc/graph_bwd.hip backward; dlwp_graph_wide_*): `BipartiteGraph`, `wide_graph_mlp`,
+`wide_edge_block`, `wide_node_block` at widths 1..512.
 """
 import ctypes as C
 
@@ -32,7 +34,26 @@ ACTIVATIONS = tuple(L.GRAPH_ACT)      # "relu", "silu"
 EPS = 1e-5      # nn.LayerNorm's default, which the reference's MeshGraphMLP uses
 
 
-class Graph:
+class _IndexArrays:
+    """The six int32 index arrays of one sample's graph -- src, dst, in_ptr, in_eid, out_ptr, out_eid -- kept on the host and moved to
+    a device on demand.  The subclasses check them at construction."""
+
+    def _store(self, src, dst, csr, device):
+        self._host = tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (src, dst) + tuple(csr))
+        self.device = None
+        if device is not None:
+            self.to(device)
+
+    def to(self, device):
+        device = torch.device(device)
+        if device != self.device:
+            (self.src, self.dst, self.in_ptr, self.in_eid, self.out_ptr, self.out_eid) = (torch.from_numpy(a).to(device)
+                                                                                          for a in self._host)
+            self.device = device
+        return self
+
+
+class Graph(_IndexArrays):
     """Device index arrays of one sample's directed graph: src, dst [E]; in_ptr [N + 1] / in_eid [E]: the edge ids grouped by
     destination; out_ptr / out_eid: grouped by source (all int32).  The CSR forms are built here when absent.  Everything is
     checked on the CPU at construction (indices in range, CSR consistent with src / dst): the kernels trust it."""
@@ -51,23 +72,12 @@ class Graph:
             csr = mgn_graph.build_csr(src, dst, num_nodes)
         mgn_graph.check_csr(src, dst, num_nodes, *csr)
         self.num_nodes, self.num_edges = int(num_nodes), len(src)
-        self._host = tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (src, dst) + tuple(csr))
-        self.device = None
-        if device is not None:
-            self.to(device)
+        self._store(src, dst, csr, device)
 
     @classmethod
     def from_mesh(cls, mesh, device=None):
         """from a mgn_graph.Graph"""
         return cls(mesh.src, mesh.dst, mesh.num_nodes, mesh.in_ptr, mesh.in_eid, mesh.out_ptr, mesh.out_eid, device=device)
-
-    def to(self, device):
-        device = torch.device(device)
-        if device != self.device:
-            (self.src, self.dst, self.in_ptr, self.in_eid, self.out_ptr, self.out_eid) = (torch.from_numpy(a).to(device)
-                                                                                          for a in self._host)
-            self.device = device
-        return self
 
 
 def _rows(t, what):
@@ -78,13 +88,15 @@ def _rows(t, what):
     return t.contiguous()
 
 
-def _check_params(what, params, norm, k0):
-    """(hidden layers, hidden width, output width) of [w0, b0, ..., wL, bL] on an operand of width k0"""
+def _check_params(what, params, norm, k0, max_width, check_k0):
+    """(hidden layers, hidden width, output width) of [w0, b0, ..., wL, bL] on an operand of width k0; every width (k0 too where
+    check_k0) is 1..max_width"""
     if len(params) < 4 or len(params) % 2:
         raise L.DlwpError(f"{what}: params is [w0, b0, ..., wL, bL] with at least one hidden layer, not {len(params)} tensors")
     nl = len(params) // 2 - 1
     if nl > L.GRAPH_MAX_HIDDEN_LAYERS:
-        raise L.DlwpError(f"{what}: {nl} hidden layers, the kernel takes 1..{L.GRAPH_MAX_HIDDEN_LAYERS}")
+        takes = "the kernel takes" if max_width == L.GRAPH_MAX_WIDTH else "the kernels take"
+        raise L.DlwpError(f"{what}: {nl} hidden layers, {takes} 1..{L.GRAPH_MAX_HIDDEN_LAYERS}")
     ws = params[0::2]
     hidden, out = ws[0].shape[0], ws[-1].shape[0]
     fan_in = k0
@@ -93,16 +105,16 @@ def _check_params(what, params, norm, k0):
         if w.dim() != 2 or tuple(w.shape) != want or b is None or tuple(b.shape) != (want[0],):
             raise L.DlwpError(f"{what}: Linear {i} has weight {tuple(w.shape)}, {want} is needed (all hidden layers share one width)")
         fan_in = hidden
-    for d in (k0 if what == "graph_mlp" else 1, hidden, out):
-        if not 1 <= d <= L.GRAPH_MAX_WIDTH:
-            raise L.DlwpError(f"{what}: width {d} outside 1..{L.GRAPH_MAX_WIDTH}")
+    for d in ((k0,) if check_k0 else ()) + (hidden, out):
+        if not 1 <= d <= max_width:
+            raise L.DlwpError(f"{what}: width {d} outside 1..{max_width}")
     if norm is not None and (len(norm) != 2 or any(tuple(t.shape) != (out,) for t in norm)):
         raise L.DlwpError(f"{what}: norm is (gamma, beta) of shape ({out},)")
     return nl, hidden, out
 
 
 class _GraphMlpFn(torch.autograd.Function):
-    """One fused launch forward (all three modes); backward as described in csrc/graph_ops.hip."""
+    """One fused launch forward (all three modes, csrc/graph_ops.hip); backward as described in csrc/graph_bwd.hip."""
 
     @staticmethod
     def forward(ctx, mode, graph, mean, residual, grad, act, x, v, gamma, beta, *params):
@@ -125,7 +137,7 @@ class _GraphMlpFn(torch.autograd.Function):
             B = x.shape[0] // E
             rows, k0 = (B * E, De + 2 * Dv) if mode == EDGE else (B * N, De + Dv)
         norm = (gamma, beta) if gamma is not None else None
-        nl, hidden, out = _check_params(what, params, norm, k0)
+        nl, hidden, out = _check_params(what, params, norm, k0, L.GRAPH_MAX_WIDTH, mode == ROWS)
         if rows == 0:
             raise L.DlwpError(f"{what}: no rows")
         ws = [p.detach().contiguous() for p in params]
@@ -293,9 +305,9 @@ def aggregate(e, graph, aggregation="sum"):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# The wide, bipartite family (csrc/graph_wide.hip; include/dlwpmi.h dlwp_graph_wide_*): widths 1..512, source and destination nodes
-# as two sets.  One Linear per launch on a (row tile x column block) grid; LayerNorm and the in-edge aggregation are launches of
-# their own.  Nothing above changes: graph_mlp / edge_block / node_block keep their 1..128 kernels.
+# The wide, bipartite family (csrc/graph_wide.hip, csrc/graph_bwd.hip; include/dlwpmi.h dlwp_graph_wide_*): widths 1..512, source
+# and destination nodes as two sets.  One Linear per launch on a (row tile x column block) grid; LayerNorm and the in-edge
+# aggregation are launches of their own.  The forward above keeps its fused 1..128 kernel; the backward kernels are the same ones.
 
 
 def _check_side(name, ptr, eid, key, n, E):
@@ -308,7 +320,7 @@ def _check_side(name, ptr, eid, key, n, E):
         raise ValueError(f"{name}_ptr / {name}_eid do not group the edges by their {'destination' if name == 'in' else 'source'}")
 
 
-class BipartiteGraph:
+class BipartiteGraph(_IndexArrays):
     """Device index arrays of one sample's directed graph from `num_src` source nodes to `num_dst` destination nodes: src, dst [E];
     in_ptr [num_dst + 1] / in_eid [E]: the edge ids grouped by destination; out_ptr [num_src + 1] / out_eid [E]: grouped by source
     (all int32).  A graph on one node set is the case num_src == num_dst with the same node rows on both sides.  The CSR forms are
@@ -337,47 +349,13 @@ class BipartiteGraph:
         _check_side("in", csr[0], csr[1], dst64, num_dst, E)
         _check_side("out", csr[2], csr[3], src64, num_src, E)
         self.num_src, self.num_dst, self.num_edges = num_src, num_dst, E
-        self._host = tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (src, dst) + tuple(csr))
-        self.device = None
-        if device is not None:
-            self.to(device)
-
-    def to(self, device):
-        device = torch.device(device)
-        if device != self.device:
-            (self.src, self.dst, self.in_ptr, self.in_eid, self.out_ptr, self.out_eid) = (torch.from_numpy(a).to(device)
-                                                                                          for a in self._host)
-            self.device = device
-        return self
+        self._store(src, dst, csr, device)
 
 
 def _wide_rows(t, what):
     if not t.is_cuda:
         raise L.DlwpError(f"{what}: a tensor on the CPU; the graph kernels run on the GPU and there is no CPU path")
     return _rows(t, what)
-
-
-def _wide_check_params(what, params, norm, k0):
-    """(hidden layers, hidden width, output width) of [w0, b0, ..., wL, bL] on an operand of width k0"""
-    if len(params) < 4 or len(params) % 2:
-        raise L.DlwpError(f"{what}: params is [w0, b0, ..., wL, bL] with at least one hidden layer, not {len(params)} tensors")
-    nl = len(params) // 2 - 1
-    if nl > L.GRAPH_MAX_HIDDEN_LAYERS:
-        raise L.DlwpError(f"{what}: {nl} hidden layers, the kernels take 1..{L.GRAPH_MAX_HIDDEN_LAYERS}")
-    ws = params[0::2]
-    hidden, out = ws[0].shape[0], ws[-1].shape[0]
-    fan_in = k0
-    for i, (w, b) in enumerate(zip(ws, params[1::2])):
-        want = (out if i == nl else hidden, fan_in)
-        if w.dim() != 2 or tuple(w.shape) != want or b is None or tuple(b.shape) != (want[0],):
-            raise L.DlwpError(f"{what}: Linear {i} has weight {tuple(w.shape)}, {want} is needed (all hidden layers share one width)")
-        fan_in = hidden
-    for d in (hidden, out):
-        if not 1 <= d <= L.GRAPH_WIDE_MAX_WIDTH:
-            raise L.DlwpError(f"{what}: width {d} outside 1..{L.GRAPH_WIDE_MAX_WIDTH}")
-    if norm is not None and (len(norm) != 2 or any(tuple(t.shape) != (out,) for t in norm)):
-        raise L.DlwpError(f"{what}: norm is (gamma, beta) of shape ({out},)")
-    return nl, hidden, out
 
 
 def _operand(mode, graph, B, rows, x, vs, vd):
@@ -427,7 +405,7 @@ def wide_forward(mode, graph, mean, residual, act, x, vs, vd, norm, params, keep
     for t in (x, vs, vd):
         if t is not None and not 1 <= t.shape[1] <= L.GRAPH_WIDE_MAX_WIDTH:
             raise L.DlwpError(f"{what}: width {t.shape[1]} outside 1..{L.GRAPH_WIDE_MAX_WIDTH}")
-    nl, hidden, out = _wide_check_params(what, params, norm, k0)
+    nl, hidden, out = _check_params(what, params, norm, k0, L.GRAPH_WIDE_MAX_WIDTH, False)
     if rows == 0:
         raise L.DlwpError(f"{what}: no rows")
     res = None
@@ -473,7 +451,7 @@ def wide_forward(mode, graph, mean, residual, act, x, vs, vd, norm, params, keep
 
 
 class _WideMlpFn(torch.autograd.Function):
-    """wide_forward, and the backward described in csrc/graph_wide.hip."""
+    """wide_forward, and the backward described in csrc/graph_bwd.hip."""
 
     @staticmethod
     def forward(ctx, mode, graph, mean, residual, grad, act, x, vs, vd, gamma, beta, *params):
