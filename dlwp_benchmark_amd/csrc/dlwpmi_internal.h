@@ -114,6 +114,13 @@ struct dlwp_fno_spatial_args {
 };
 int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* a, hipStream_t stream);
 long long dlwp_fno_gslab_stride(int C);
+// block 0's backward `spatial` (s: slab form, no activation in front, out == x1_out == NULL) and the lifting MLP's backward
+// (dlwp_pwmlp_bwd_ex's x / w1 / b1 / w2 / gx / slab, gy = the gradient `spatial` would have written) as one launch; every output
+// bit for bit the two launches'.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where the shapes need the two
+// launches -- other than 64-wide rows, wide or 3-D plans, C_pad 64, Cin > 32 -- or the knob FNO_FUSE_LIFT_BWD is 0.
+int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
+                              const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
+                              int slab_accumulate, int Cin, int Ch, hipStream_t stream);
 // every partial slab of a training step folded by ONE launch (slab-parallel, coalesced):
 //   plain job  (pwmlp == 0): d1[i] += sum_s slab[s*stride + i] (i < n1), d2[i] += sum_s slab[s*stride + n1 + i] (i < n2)
 //   pwmlp job  (pwmlp != 0): the accumulator-tile slabs of dlwp_pwmlp_bwd_ex -> d1 = gw1, d2 = gb1, d3 = gw2, d4 = gb2

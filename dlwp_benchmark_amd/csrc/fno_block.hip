@@ -17,6 +17,7 @@
 #include "common.hip.h"
 #include "dlwpmi_internal.h"
 #include "fno_rows.hip.h"
+#include "pwmlp_bwd.hip.h"
 #include <cmath>
 #include <vector>
 
@@ -443,143 +444,7 @@ template <int NCB, int NBN, int MODE>
 __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
     static_assert(MODE == 1 || MODE == 2, "backward modes only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int NTA = SPATIAL_NT;               // threads of role A (and of role B)
-    const SpatialLds L = carve_spatial_lds<true>(smem, a);
-    const int tid = threadIdx.x, lane = lane_id();
-    const int w = __builtin_amdgcn_readfirstlane(wave_id());   // wave-uniform: the role branches are scalar branches
-    const bool role_a = w < 4;
-    const int tb = tid - NTA, w2 = w - 4;         // role B's thread / wave index
-    const int r = lane & 15, g = lane >> 4;
-    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
-    const int W4 = a.W / 4, nwb = a.W / 16;
-    DLWP_SPAN_BEGIN();
-    DLWP_STAMP(0);
-    // ---- issue phase (role A: the chain's; role B: the running partials of this workgroup's gradient slab)
-    SpatialLoads R;
-    constexpr int SLQ = 4;
-    float slab_old[SLQ], slab_b_old = 0.f;
-#pragma unroll
-    for (int k = 0; k < SLQ; ++k) slab_old[k] = 0.f;
-    const long long slab_off = spatial_slab_off(a);
-    const bool slab_acc = a.gslab && a.gslab_accumulate;
-    const int bias_c = 4 * lane + w2;             // role B: bias-gradient channel of this lane (lanes 0-15 of each wave)
-    constexpr int BQ = 16;                        // ... its row pieces read ahead (a whole row at W = 64)
-    const bool bias_on = !role_a && (a.g_bias || a.gslab) && lane < 16 && bias_c < a.C;
-    if (role_a) {
-        spatial_issue<MODE>(a, b, h, true, R);
-    } else {
-        if (slab_acc) {
-#pragma unroll
-            for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tb + NTA * k, a.C * a.C - 1)];
-            slab_b_old = a.gslab[slab_off + a.C * a.C + min(bias_c, a.C - 1)];
-        }
-        // gK partial of wave w2: sum over its 16-pixel chunks of g_pre[o][w] * act(x)[i][w].  The MFMA fragments are 16 contiguous
-        // bytes of a row of `tin` / `pprev`: they come straight from global memory (the values role A is putting into tin_s /
-        // pprev_s; rows >= C are zero there), so this GEMM runs while role A waits for its own loads, not next to the main GEMM
-        f32x4 kacc[NCB][NCB];
-#pragma unroll
-        for (int ob = 0; ob < NCB; ++ob)
-#pragma unroll
-            for (int ib = 0; ib < NCB; ++ib) kacc[ob][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int kc = w2; kc < nwb; kc += 4) {
-            f32x4 ta[NCB], pb[NCB];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {   // clamped addresses, selects afterwards: all loads in flight together
-                const int c = cb * 16 + r;
-                const long long off = (((long long)b * a.C + min(c, a.C - 1)) * a.H + h) * a.W + kc * 16 + 4 * g;
-                ta[cb] = *reinterpret_cast<const f32x4*>(&a.tin[off]);
-                pb[cb] = *reinterpret_cast<const f32x4*>(&a.pprev[off]);
-            }
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                const bool ok = cb * 16 + r < a.C;
-                ta[cb] = ok ? ta[cb] : f32x4{0.f, 0.f, 0.f, 0.f};
-                pb[cb] = ok ? pb[cb] : f32x4{0.f, 0.f, 0.f, 0.f};
-                if (a.act_tin) ta[cb] = gelu4(ta[cb]);
-            }
-#pragma unroll
-            for (int ib = 0; ib < NCB; ++ib) {
-                f32x4 b4 = pb[ib];
-                if (a.act_prev) {
-                    b4 = gelu4(b4);
-                }
-#pragma unroll
-                for (int ob = 0; ob < NCB; ++ob) kacc[ob][ib] = mfma16_chunk(ta[ob], b4, kacc[ob][ib]);
-            }
-        }
-#pragma unroll
-        for (int ob = 0; ob < NCB; ++ob)
-#pragma unroll
-            for (int ib = 0; ib < NCB; ++ib)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    L.gks[((w2 * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
-        DLWP_STAMP_IF(blockIdx.x == 0 && tb == 0, 13);
-    }
-    DLWP_STAMP(1);
-
-    if (role_a) {
-        spatial_commit<MODE>(a, L, b, h, true, R);
-        DLWP_STAMP(3);
-        spatial_hstep(a, L, b, h, R);
-        DLWP_STAMP(4);
-    }
-    __syncthreads();   // 1: tin_s, pprev_s, gs, ks, s1 complete (role A); the four gK partials complete (role B)
-    DLWP_STAMP(5);
-
-    if (role_a) {
-        spatial_gemm<NCB, NBN, MODE>(a, L, w);
-        DLWP_STAMP(6);
-    } else {
-        // cross-wave sum of the gK partials (w2 = 0 .. 3 from 0.f), then old + v into the slab, or the atomics.  The first SLQ
-        // elements of a thread: all LDS reads first, then the sums (a read-then-use loop pays the LDS latency per element)
-        // Bias gradient: channel 4 lane + w2 on lanes 0-15 of every wave, its row of tin_s as 16-byte reads (the first BQ issued
-        // here, in front of the sums), additions in the order x = 0 .. W-1 from 0.f.
-        const float4* brow = reinterpret_cast<const float4*>(&L.tin_s[min(bias_c, a.C_pad - 1) * L.LDP]);
-        float4 bq[BQ];
-        if (bias_on) {
-#pragma unroll
-            for (int q = 0; q < BQ; ++q) bq[q] = brow[min(q, W4 - 1)];
-        }
-        float pq[SLQ][4];
-#pragma unroll
-        for (int k = 0; k < SLQ; ++k) {
-            const int idx = min(tb + NTA * k, a.C * a.C - 1), o = fastdiv(idx, a.dC), i = idx - o * a.C;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) pq[k][q] = L.gks[(q * a.C_pad + o) * a.C_pad + i];
-        }
-#pragma unroll
-        for (int k = 0; k < SLQ; ++k) {
-            const int idx = tb + NTA * k;
-            float v = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v += pq[k][q];
-            if (idx < a.C * a.C) spatial_flush(a, slab_off + idx, &a.g_wskip[idx], slab_old[k], v);
-        }
-        for (int idx = tb + NTA * SLQ; idx < a.C * a.C; idx += NTA) {
-            const int o = fastdiv(idx, a.dC), i = idx - o * a.C;
-            float v = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v += L.gks[(q * a.C_pad + o) * a.C_pad + i];
-            spatial_flush(a, slab_off + idx, &a.g_wskip[idx], slab_acc ? a.gslab[slab_off + idx] : 0.f, v);
-        }
-        if (bias_on) {
-            float bias_sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < BQ; ++q)
-                if (q < W4) { bias_sum += bq[q].x; bias_sum += bq[q].y; bias_sum += bq[q].z; bias_sum += bq[q].w; }
-            for (int x4 = BQ; x4 < W4; ++x4) {
-                const float4 v = brow[x4];
-                bias_sum += v.x; bias_sum += v.y; bias_sum += v.z; bias_sum += v.w;
-            }
-            spatial_flush(a, slab_off + a.C * a.C + bias_c, &a.g_bias[bias_c], slab_b_old, bias_sum);
-        }
-        DLWP_STAMP_IF(blockIdx.x == 0 && tb == 0, 15);
-    }
-    // 2: tout_s complete.  Role B is finished: it touches no LDS behind this barrier and must not wait for its slab stores in
-    // front of one (__syncthreads() is a fence as well: vmcnt(0)); it only arrives, here and at the third.
-    if (role_a) __syncthreads(); else __builtin_amdgcn_s_barrier();
-    DLWP_STAMP(7);
+#include "fno_spatial_roles_head.inc.h"
 
     if (role_a) {
         spatial_out_dft<NCB, NBN>(a, L, b, h);
@@ -591,6 +456,45 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
     if (role_a && a.x1_out) store_x1<NTA>(L.x1s, a.x1_out, b, h, a.H, a.m2c, a.C, a.C_pad, a.NP);
     DLWP_STAMP(12);
     DLWP_STAMP_WAVE(24);
+    DLWP_SPAN_END();
+}
+
+// Block 0's backward `spatial` and the lifting MLP's backward as ONE launch.  On 64-wide rows a `spatial` workgroup (one image row
+// (b, h)) and a pwmlp_bwd workgroup (64 consecutive pixels of one sample) are the same pixels under the same blockIdx, and the
+// gradient of h0 between them has no other reader: the row that role A finishes in tout_s[C_pad][W + 4] IS the gys[Cout_pad][PT + 4]
+// tile the lifting backward stages first, so the tensor is neither stored nor loaded again and one kernel boundary goes.
+//   phase 1: the two-role workgroup above up to its second barrier -- the same text (fno_spatial_roles_head.inc.h), so the same
+//            thread-to-element mapping, sum orders and slab layout; `out` is not written and there is no fused row DFT.
+//   phase 2: the body of pwmlp_bwd_kernel<NIB, NCB, 8> -- the same text (pwmlp_bwd_body.inc.h) -- on all eight waves with gys =
+//            tout_s.  Its part 1, the loads that do not depend on phase 1 (each wave's first weight fragments, each thread's unit
+//            of the input tile through the pointer table), is issued in front of phase 1 (25.2 -> 24.6 us at the headline shape).  Its input tile and the gx partial tiles lie behind tout_s, over regions of phase 1 that are dead after the
+//            second barrier (pprev_s, ft, x1s, gs, ks, s1, gks), so the launch needs no more LDS than the larger of its phases.
+// Same row, same blockIdx, hence the same skip-weight slab and the same lifting slab as the two launches: every output is bit for
+// bit theirs.  MODE is 2: the input of block 0 is the lifting MLP's output, which is not activated.
+struct SpatialLiftDev {
+    SpatialDev s;
+    BwdArgs m;
+};
+template <int NCB, int NBN, int NIB>
+__global__ __launch_bounds__(512) void fno_spatial_lift_bwd_kernel(SpatialLiftDev f) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NOB = NCB, NW = 8;
+    // three channel tiles with two input tiles hold 256 VGPRs as it is: the early loads would spill (4 VGPRs, 20 bytes of scratch)
+    constexpr bool PWMLP_BWD_EARLY = !(NCB == 3 && NIB == 2);
+    const BwdArgs& a = f.m;
+#define PWMLP_BWD_FUSED
+#define PWMLP_BWD_PART 1
+#include "pwmlp_bwd_body.inc.h"
+#undef PWMLP_BWD_PART
+    {
+        constexpr int MODE = 2;
+        const SpatialDev& a = f.s;
+#include "fno_spatial_roles_head.inc.h"
+    }
+#define PWMLP_BWD_PART 2
+#include "pwmlp_bwd_body.inc.h"
+#undef PWMLP_BWD_PART
+#undef PWMLP_BWD_FUSED
     DLWP_SPAN_END();
 }
 
@@ -1280,18 +1184,8 @@ int dlwp_fno_mix_bwd(const dlwp_fno_plan* p, const float2* g1, const float2* wsp
     return mix_launch(p, true, a, stream);
 }
 
-int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hipStream_t stream) {
-    if (dlwp_fno_is_wide(p)) {
-        // channel-blocked form: the fused by-products (next block's row DFT, skip-weight / bias gradients) are separate launches
-        int rc = dlwp_fno_spatial_wide(p, s, stream);
-        if (rc) return rc;
-        if (s->inverse_adjoint && (s->g_wskip || s->g_bias)) {
-            DLWP_REQUIRE(s->g_wskip && s->g_bias && !s->gslab, DLWP_E_INVALID, "fno_spatial (wide): needs g_wskip and g_bias, no slab");
-            if ((rc = dlwp_fno_skip_wgrad(p, s->tin, s->pprev, s->act_prev, s->g_wskip, s->g_bias, s->B, stream))) return rc;
-        }
-        if (s->x1_out) return dlwp_fno_rows_dft_wide(p, s->out, s->x1_act, s->x1_adjoint, s->x1_out, s->B, stream);
-        return DLWP_OK;
-    }
+// the device argument block of a `spatial` launch, and the LDS bytes of its two layouts (four-wave / two-role)
+static SpatialDev make_spatial_dev(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s) {
     SpatialDev a{};
     a.tin = s->tin; a.spec = s->spec; a.wskip = s->wskip; a.bias = s->bias; a.pprev = s->pprev;
     a.out = s->out; a.x1_out = s->x1_out; a.g_wskip = s->g_wskip; a.g_bias = s->g_bias;
@@ -1304,13 +1198,33 @@ int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hip
     a.vec_w = (reinterpret_cast<uintptr_t>(s->wskip) & 15) == 0;
     a.dC = make_fastdiv(p->C);
     a.C = p->C; a.H = p->H; a.W = p->W; a.m1 = p->m1; a.m2c = p->m2c; a.C_pad = p->C_pad; a.NP = p->NP;
+    return a;
+}
+static void spatial_lds_bytes(const dlwp_fno_plan* p, size_t& lds, size_t& lds_roles) {
     const int LDP = p->W + 4;
     const size_t gemm_ops = (size_t)p->NP * LDP + (size_t)p->C_pad * (p->C_pad + 4) + (size_t)p->C_pad * (p->NP + 4);   // gs, ks, s1
     const size_t gks = (size_t)4 * p->C_pad * p->C_pad;
     const size_t live = (size_t)3 * p->C_pad * LDP + (size_t)p->NP * LDP + (size_t)4 * p->C_pad * p->NP;
-    const size_t lds = sizeof(float) * (live + p->C_pad + (gemm_ops > gks ? gemm_ops : gks));
+    lds = sizeof(float) * (live + p->C_pad + (gemm_ops > gks ? gemm_ops : gks));
     // two-role form of the backward kernel: gks next to gs / ks / s1 instead of over them
-    const size_t lds_roles = sizeof(float) * (live + gemm_ops + gks);
+    lds_roles = sizeof(float) * (live + gemm_ops + gks);
+}
+
+int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hipStream_t stream) {
+    if (dlwp_fno_is_wide(p)) {
+        // channel-blocked form: the fused by-products (next block's row DFT, skip-weight / bias gradients) are separate launches
+        int rc = dlwp_fno_spatial_wide(p, s, stream);
+        if (rc) return rc;
+        if (s->inverse_adjoint && (s->g_wskip || s->g_bias)) {
+            DLWP_REQUIRE(s->g_wskip && s->g_bias && !s->gslab, DLWP_E_INVALID, "fno_spatial (wide): needs g_wskip and g_bias, no slab");
+            if ((rc = dlwp_fno_skip_wgrad(p, s->tin, s->pprev, s->act_prev, s->g_wskip, s->g_bias, s->B, stream))) return rc;
+        }
+        if (s->x1_out) return dlwp_fno_rows_dft_wide(p, s->out, s->x1_act, s->x1_adjoint, s->x1_out, s->B, stream);
+        return DLWP_OK;
+    }
+    const SpatialDev a = make_spatial_dev(p, s);
+    size_t lds, lds_roles;
+    spatial_lds_bytes(p, lds, lds_roles);
     const dim3 grid(s->B * p->H);
     int rc;
     const int mode = !a.is_bwd ? 0 : (a.act_prev ? 1 : 2);
@@ -1319,6 +1233,10 @@ int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hip
     // It does not fit for C_pad 64 on 64-wide rows (161.5 KiB: C 49 .. 64 at the published grid) nor for C_pad 32 on 256-wide
     // rows (161 KiB): those shapes keep the four-wave kernel, as does a backward launch without g_wskip / slab.
     const bool roles = a.is_bwd && (a.g_wskip || a.gslab) && lds_roles <= (size_t)160 * 1024;
+    const double pix = (double)s->B * p->H * p->W;
+    dlwp_prof_scope prof(stream, 2.0 * pix * p->C * (p->C * (roles ? 2 : 1) + 2 * p->m2c), 4.0 * pix * p->C * (a.is_bwd ? 3 : 2),
+                         roles ? "fno_spatial_roles_kernel<%d, %d, %d>" : "fno_spatial_kernel<%d, %d, %d>", p->C_pad / 16,
+                         p->NP / 16, mode);              // the instantiation this call launches, as the live accounting reports it
 #define LAUNCH_KERNEL(K, NT, BYTES)                                              \
     if ((rc = set_lds(K, BYTES, "fno_spatial")) != DLWP_OK) return rc;           \
     hipLaunchKernelGGL(K, grid, dim3(NT), BYTES, stream, a);
@@ -1395,6 +1313,96 @@ extern "C" int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* p, const float* x, i
     s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
     s.out = g_x; s.gslab = slab; s.gslab_accumulate = slab_accumulate; s.inverse_adjoint = 1; s.B = B;
     return dlwp_fno_spatial(p, &s, stream);
+}
+
+// ---- block 0's backward `spatial` + the lifting MLP's backward in one launch (fno_spatial_lift_bwd_kernel).
+// LDS bytes of that launch, or 0 where the shapes take the two launches: 64-wide rows (a `spatial` row is a pwmlp pixel tile),
+// a narrow 2-D plan whose two-role layout fits (C_pad <= 48), and the lifting phase's tiles -- behind tout_s, over the regions
+// the `spatial` phase no longer needs -- inside the 160 KiB of a CU.  Instantiated are the (C_pad / 16, Cin_pad / 16) pairs that
+// compile without scratch and without vector spills: (1, 1), (2, 1), (2, 2), (3, 1), (3, 2); like pwmlp_bwd_kernel's own, the
+// wider ones spill, and they keep the two launches.
+static size_t lift_bwd_fused_lds(const dlwp_fno_plan* p, int Cin) {
+    if (dlwp_fno_is_wide(p) || p->W != PT || Cin < 1 || Cin > 32 || (p->C_pad == 16 && Cin > 16)) return 0;
+    size_t lds, lds_roles;
+    spatial_lds_bytes(p, lds, lds_roles);
+    const size_t phase2 = sizeof(float) * ((size_t)2 * p->C_pad * LDP + (size_t)(1 + BWD_WAVES) * round_up(Cin, 16) * LDP);
+    const size_t need = lds_roles > phase2 ? lds_roles : phase2;
+    return lds_roles <= (size_t)160 * 1024 && need <= (size_t)160 * 1024 ? need : 0;
+}
+
+// `s`: the backward `spatial` arguments of block 0 (no activation in front of it, slab form, neither `out` nor a fused row DFT);
+// x / gx / w1 / b1 / w2 / slab: the lifting backward's, as for dlwp_pwmlp_bwd_ex with gy = the gradient `spatial` would have
+// written.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where the shapes or FNO_FUSE_LIFT_BWD = 0 ask for the
+// two launches: the caller issues them instead.
+int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
+                              const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
+                              int slab_accumulate, int Cin, int Ch, hipStream_t stream) {
+    const size_t lds = lift_bwd_fused_lds(p, Cin);
+    if (!lds || !s->inverse_adjoint || s->act_prev || s->act_tin || s->out || s->x1_out || !s->gslab || !slab || Ch < 1 ||
+        dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) == 0)
+        return DLWP_E_UNSUPPORTED;
+    SpatialLiftDev f{};
+    f.s = make_spatial_dev(p, s);
+    BwdArgs& a = f.m;
+    a.x = *x; a.w1 = w1; a.b1 = b1; a.w2 = w2;
+    if (gx) a.gx = *gx;
+    a.gx_accumulate = gx_accumulate;
+    a.B = s->B; a.Cin = Cin; a.Ch = Ch; a.Cout = p->C; a.P = p->H * p->W;
+    a.tiles_per_sample = p->H;
+    a.Cin_pad = round_up(Cin, 16); a.Ch_pad = round_up(Ch, 16); a.Cout_pad = p->C_pad;
+    a.slab = slab; a.slab_stride = dlwp_pwmlp_slab_stride(Cin, Ch, p->C); a.slab_accumulate = slab_accumulate;
+    a.vec_w = aligned16(w1);
+    a.dCin = make_fastdiv(Cin); a.dCh = make_fastdiv(Ch);
+    a.vec_x = view_vec_ok(a.x);
+    const int ncb = p->C_pad / 16, nbn = p->NP / 16, nib = a.Cin_pad / 16;
+    const dim3 grid(s->B * p->H);
+    const double pix = (double)s->B * a.P;
+    dlwp_prof_scope prof(stream, 2.0 * pix * (p->C * (2.0 * p->C + 2 * p->m2c) + Ch * (3.0 * Cin + 2.0 * p->C)),
+                         4.0 * pix * (2.0 * p->C + 2.0 * Cin), "fno_spatial_lift_bwd_kernel<%d, %d, %d>", ncb, nbn, nib);
+    int rc;
+#define LAUNCH(N, M, I)                                                                                       \
+    if ((rc = set_lds(fno_spatial_lift_bwd_kernel<N, M, I>, lds, "fno_spatial_lift_bwd")) != DLWP_OK) return rc; \
+    hipLaunchKernelGGL((fno_spatial_lift_bwd_kernel<N, M, I>), grid, dim3(512), lds, stream, f);
+#define ROW(N, M)                                      \
+    if (nib == 1) { LAUNCH(N, M, 1) } else { LAUNCH(N, M, 2) }
+    switch (ncb * 10 + nbn) {           // lift_bwd_fused_lds() has refused everything else
+        case 11: LAUNCH(1, 1, 1) break; case 12: LAUNCH(1, 2, 1) break;
+        case 21: ROW(2, 1) break; case 22: ROW(2, 2) break;
+        case 31: ROW(3, 1) break; case 32: ROW(3, 2) break;
+        default: return DLWP_E_UNSUPPORTED;
+    }
+#undef ROW
+#undef LAUNCH
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+extern "C" int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* p, const float* h0, const float* wspec, const float* wskip,
+                                            const float* g_pre, const float* xhat, float* g_wspec, float* slab_skip,
+                                            int slab_skip_accumulate, const float* x, const float* w1, const float* b1,
+                                            const float* w2, float* gx, int gx_accumulate, float* slab_lift,
+                                            int slab_lift_accumulate, int B, int Cin, int Ch, void* workspace, void* stream_) {
+    DLWP_REQUIRE(p && h0 && wspec && wskip && g_pre && xhat && g_wspec && slab_skip && x && w1 && b1 && w2 && slab_lift &&
+                     workspace && B > 0 && Cin > 0 && Ch > 0,
+                 DLWP_E_INVALID, "fno_block_lift_bwd_slab: NULL argument or non-positive dimension");
+    DLWP_REQUIRE(lift_bwd_fused_lds(p, Cin) != 0 && dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) != 0, DLWP_E_UNSUPPORTED,
+                 "fno_block_lift_bwd_slab: needs 64-wide rows, a narrow 2-D plan of at most 48 channels, Cin <= 32 and "
+                 "FNO_FUSE_LIFT_BWD != 0 (use dlwp_fno_block_bwd_slab + dlwp_pwmlp_bwd_slab)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    float2* g1 = static_cast<float2*>(workspace);
+    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
+    int rc;
+    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
+    if ((rc = dlwp_fno_mix_bwd(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat),
+                               gxhat, reinterpret_cast<float2*>(g_wspec), B, stream))) return rc;
+    dlwp_fno_spatial_args s{};
+    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = h0;
+    s.gslab = slab_skip; s.gslab_accumulate = slab_skip_accumulate; s.inverse_adjoint = 1; s.B = B;
+    const long long P = (long long)p->H * p->W;
+    dlwp_chan_src xs{x, (long long)Cin * P, P, nullptr, nullptr};
+    dlwp_chan_dst gxd{gx, (long long)Cin * P, P, nullptr, nullptr};
+    return dlwp_fno_spatial_lift_bwd(p, &s, &xs, w1, b1, w2, gx ? &gxd : nullptr, gx_accumulate, slab_lift,
+                                     slab_lift_accumulate, Cin, Ch, stream);
 }
 
 extern "C" int dlwp_fno_block_slab_fold(const dlwp_fno_plan* p, const float* slab, float* g_wskip, float* g_bias, int B,

@@ -331,6 +331,10 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
                                          grad_out ? nullptr : &targ, mse_scale, &gx, 0, ci.gres ? &gr : nullptr, g.pw1,
                                          g.pb1, g.pw2, g.pb2, tr->slab_proj, k != tr->ncalls - 1, c.B, C, c.projection,
                                          c.out_channels, HW, tr->plan, tr->x1, s))) return rc;
+        // lifting backward; input-channel gradients flow into the predictions that fed this step
+        dlwp_chan_src xs{nullptr, 0, 0, tr->src_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
+        dlwp_chan_dst gxd{nullptr, 0, 0, tr->gdst_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
+        bool lift_done = false;
         for (int l = NL - 1; l >= 0; --l) {
             if ((rc = dlwp_fno_mix_bwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)),
                                        xhat + l * xhatB, tr->spec, reinterpret_cast<float2*>(g.spec(l)), c.B, s))) return rc;
@@ -345,13 +349,21 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
             a.gslab_accumulate = k != tr->ncalls - 1;
             a.inverse_adjoint = 1;
             a.B = c.B;
+            if (l == 0) {
+                // block 0's `spatial` and the lifting backward as one launch where the shapes allow: the gradient of h0 stays in
+                // LDS (gnext is not written); otherwise the two launches below
+                dlwp_fno_spatial_args f = a;
+                f.out = nullptr;
+                rc = dlwp_fno_spatial_lift_bwd(tr->plan, &f, &xs, w.lw1, w.lb1, w.lw2, &gxd, 1, tr->slab_lift,
+                                               k != tr->ncalls - 1, tr->Cin, c.lifting, s);
+                if (rc == DLWP_OK) { lift_done = true; break; }
+                if (rc != DLWP_E_UNSUPPORTED) return rc;
+            }
             if ((rc = dlwp_fno_spatial(tr->plan, &a, s))) return rc;
             float* tmp = gcur; gcur = gnext; gnext = tmp;
         }
-        // lifting backward; input-channel gradients flow into the predictions that fed this step
-        dlwp_chan_src xs{nullptr, 0, 0, tr->src_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
+        if (lift_done) continue;
         dlwp_chan_src gh0{gcur, tr->act, HW, nullptr, nullptr};
-        dlwp_chan_dst gxd{nullptr, 0, 0, tr->gdst_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
         if ((rc = dlwp_pwmlp_bwd_ex(&xs, w.lw1, w.lb1, w.lw2, &gh0, nullptr, nullptr, 0.f, &gxd, 1, nullptr, g.lw1, g.lb1,
                                     g.lw2, g.lb2, tr->slab_lift, k != tr->ncalls - 1, c.B, tr->Cin, c.lifting, C,
                                     HW, s))) return rc;

@@ -147,6 +147,19 @@ int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* plan, const float* x, int act_i
                             void* stream);
 int dlwp_fno_block_slab_fold(const dlwp_fno_plan* plan, const float* slab, float* g_wskip, float* g_bias,
                              int B, void* stream);
+/* The backward of the FIRST block (its input h0 = the lifting MLP's output, not activated) fused with the lifting MLP's      */
+/* backward: rows DFT, per-mode stage, then ONE launch for `spatial` + the MLP backward -- the gradient of h0 stays in LDS and  */
+/* is never written.  Outputs bit for bit those of dlwp_fno_block_bwd_slab(act_in = 0) followed by dlwp_pwmlp_bwd_slab on its   */
+/* g_x: g_wspec, the skip slab (dlwp_fno_block_slab_fold), the lifting slab (dlwp_pwmlp_slab_fold; Cout = the plan's C,         */
+/* P = H * W) and gx.  x, gx: dense [B][Cin][H W]; gx nullable, gx_accumulate != 0 adds to it; each slab has its own            */
+/* accumulate flag.  DLWP_E_UNSUPPORTED, nothing launched, where the library itself takes the two launches: rows that are not  */
+/* 64 wide, more than 48 channels, wide / 3-D plans, Cin > 32 (Cin > 16 for at most 16 channels), or the knob                  */
+/* FNO_FUSE_LIFT_BWD = 0.                                                                                                      */
+int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* plan, const float* h0, const float* wspec, const float* wskip,
+                                 const float* g_pre, const float* xhat, float* g_wspec, float* slab_skip,
+                                 int slab_skip_accumulate, const float* x, const float* w1, const float* b1,
+                                 const float* w2, float* gx, int gx_accumulate, float* slab_lift,
+                                 int slab_lift_accumulate, int B, int Cin, int Ch, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Training-step pieces (nsbench/scripts/train.py:113-131: MSELoss, Adam).               */
