@@ -225,6 +225,21 @@ __device__ __forceinline__ void stage_matrix(float* dst, int ld, const float* __
     }
 }
 
+// Stride of a loop that the threads of a workgroup share: blockDim.x, or NT where NT threads of a larger workgroup share it
+// (MatLoad, stage_matrix_tail, zero_padding, store_x1).  A compile-time parameter, and each form keeps its own type: a run-time
+// stride changed the registers of every caller.  wg_thread: a thread's index among those NT threads when they begin at thread
+// T0 (a role of whole waves behind the first T0 threads); the plain threadIdx.x for T0 == 0.
+template <int NT>
+__device__ __forceinline__ auto wg_stride() {
+    if constexpr (NT != 0) return NT;
+    else return (unsigned)blockDim.x;
+}
+template <int T0>
+__device__ __forceinline__ auto wg_thread() {
+    if constexpr (T0 != 0) return (int)threadIdx.x - T0;
+    else return (unsigned)threadIdx.x;
+}
+
 // Split staging: issue() puts up to MAXU 16-byte loads per thread in flight (no LDS traffic yet);
 // commit() scatters them into the padded LDS image.  Kernels issue ALL their independent inputs
 // first and commit afterwards, so a workgroup pays one global-memory latency instead of one per
@@ -232,18 +247,20 @@ __device__ __forceinline__ void stage_matrix(float* dst, int ld, const float* __
 template <int MAXU>
 struct MatLoad {
     float4 v[MAXU];
+    // NT, T0: see wg_stride / wg_thread above (threads T0 .. T0 + NT - 1 of a larger workgroup share the matrix)
+    template <int NT = 0, int T0 = 0>
     __device__ __forceinline__ void issue(const float* __restrict__ src, int n4, int base = 0) {
 #pragma unroll
         for (int k = 0; k < MAXU; ++k) {
-            const int u = base + threadIdx.x + k * blockDim.x;
+            const int u = base + wg_thread<T0>() + k * wg_stride<NT>();
             v[k] = u < n4 ? reinterpret_cast<const float4*>(src)[u] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    template <bool TR>
+    template <bool TR, int NT = 0, int T0 = 0>
     __device__ __forceinline__ void commit(float* dst, int ld, int cols, FastDiv dcols, int n4, int base = 0) const {
 #pragma unroll
         for (int k = 0; k < MAXU; ++k) {
-            const int u = base + threadIdx.x + k * blockDim.x;
+            const int u = base + wg_thread<T0>() + k * wg_stride<NT>();
             if (u < n4) {
                 const float vv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
 #pragma unroll
@@ -259,25 +276,18 @@ struct MatLoad {
 };
 // number of 16-byte units MatLoad handles for a dense [rows][cols] matrix (0 when not 16-byte loadable);
 // the remainder (and the unaligned case) goes through stage_matrix_tail.
+template <int NT = 0>
 __device__ __forceinline__ int matload_units(int rows, int cols, bool vec_ok, int maxu) {
     const int n4 = vec_ok ? (rows * cols) >> 2 : 0;
-    const int cap = maxu * (int)blockDim.x;
+    const int cap = maxu * (int)wg_stride<NT>();
     return n4 < cap ? n4 : cap;
 }
-// Stride of a loop that the threads of a workgroup share: blockDim.x, or NT where the first NT threads of a larger workgroup
-// share it (stage_matrix_tail, zero_padding, store_x1).  A compile-time parameter, and each form keeps its own type: a run-time
-// stride changed the registers of every caller.
-template <int NT>
-__device__ __forceinline__ auto wg_stride() {
-    if constexpr (NT != 0) return NT;
-    else return (unsigned)blockDim.x;
-}
-template <bool TR, int NT = 0>
+template <bool TR, int NT = 0, int T0 = 0>
 __device__ __forceinline__ void stage_matrix_tail(float* dst, int ld, const float* __restrict__ src, int rows, int cols,
                                                   FastDiv dcols, int done4) {
     const int n = rows * cols;
 #pragma unroll 4
-    for (int e = 4 * done4 + threadIdx.x; e < n; e += wg_stride<NT>()) {
+    for (int e = 4 * done4 + wg_thread<T0>(); e < n; e += wg_stride<NT>()) {
         const int rr = fastdiv(e, dcols);
         const int cc = e - rr * cols;
         dst[TR ? cc * ld + rr : rr * ld + cc] = src[e];
@@ -285,13 +295,13 @@ __device__ __forceinline__ void stage_matrix_tail(float* dst, int ld, const floa
 }
 
 // zero the padding of an LDS image holding a [rows][cols] matrix inside [rows_pad][cols_pad] (row stride ld)
-template <int NT = 0>
+template <int NT = 0, int T0 = 0>
 __device__ __forceinline__ void zero_padding(float* dst, int ld, int rows, int cols, int rows_pad, int cols_pad) {
     if (cols_pad > cols)
-        for (int rr = threadIdx.x; rr < rows; rr += wg_stride<NT>())
+        for (int rr = wg_thread<T0>(); rr < rows; rr += wg_stride<NT>())
             for (int cc = cols; cc < cols_pad; ++cc) dst[rr * ld + cc] = 0.f;
     for (int rr = rows; rr < rows_pad; ++rr)
-        for (int cc = threadIdx.x; cc < cols_pad; cc += wg_stride<NT>()) dst[rr * ld + cc] = 0.f;
+        for (int cc = wg_thread<T0>(); cc < cols_pad; cc += wg_stride<NT>()) dst[rr * ld + cc] = 0.f;
 }
 
 // ---- in-kernel phase stamps (diagnostic build only: -DDLWP_STAMPS; never in the shipped library)

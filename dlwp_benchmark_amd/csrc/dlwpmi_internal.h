@@ -121,6 +121,17 @@ long long dlwp_fno_gslab_stride(int C);
 int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
                               const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
                               int slab_accumulate, int Cin, int Ch, hipStream_t stream);
+// the last block's forward `spatial` (s: forward form, out = pre of that block, x1_out == NULL) and the projection MLP on its
+// result (pw1 .. pb2, y1, optional residual res1; dlwp_pwmlp_fwd_ex's arguments with x = s->out) as one launch; with x2v != NULL
+// also the next net call's lifting MLP and its rows DFT into x1_out, as dlwp_pwmlp_fwd_chain_ex chains them (Cout2 = plan->C).
+// Every output, `pre` included, bit for bit the two launches'.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched)
+// where the shapes need the two launches -- other than 64-wide rows, wide or 3-D plans, C_pad 64 (with the lifting MLP: C_pad 48,
+// NP 32), Cout1 > 8, whatever dlwp_pwmlp_fwd_chain_ex refuses, more than 160 KiB of LDS -- or the knob FNO_FUSE_PROJ_FWD is 0.
+int dlwp_fno_spatial_proj_fwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const float* pw1, const float* pb1,
+                              const float* pw2, const float* pb2, const dlwp_chan_dst* y1, const dlwp_chan_src* res1, int Ch1,
+                              int Cout1, const dlwp_chan_src* x2v, const float* lw1, const float* lb1, const float* lw2,
+                              const float* lb2, const dlwp_chan_dst* y2, int Cin2, int Ch2, const signed char* next_ch,
+                              float2* x1_out, hipStream_t stream);
 // every partial slab of a training step folded by ONE launch (slab-parallel, coalesced):
 //   plain job  (pwmlp == 0): d1[i] += sum_s slab[s*stride + i] (i < n1), d2[i] += sum_s slab[s*stride + n1 + i] (i < n2)
 //   pwmlp job  (pwmlp != 0): the accumulator-tile slabs of dlwp_pwmlp_bwd_ex -> d1 = gw1, d2 = gb1, d3 = gw2, d4 = gb2

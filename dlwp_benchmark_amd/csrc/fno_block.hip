@@ -18,6 +18,7 @@
 #include "dlwpmi_internal.h"
 #include "fno_rows.hip.h"
 #include "pwmlp_bwd.hip.h"
+#include "pwmlp_fwd.hip.h"
 #include <cmath>
 #include <vector>
 
@@ -496,6 +497,82 @@ __global__ __launch_bounds__(512) void fno_spatial_lift_bwd_kernel(SpatialLiftDe
 #undef PWMLP_BWD_PART
 #undef PWMLP_BWD_FUSED
     DLWP_SPAN_END();
+}
+
+// The last block's forward `spatial` and the projection MLP (chained, as in pwmlp_fwd_chain_kernel, with the next net call's lifting
+// MLP and its rows DFT; NOB2 == 0: projection only) as ONE launch of 16 waves.  On 64-wide rows a `spatial` workgroup (one image row
+// (b, h)) and a pointwise-MLP workgroup (64 consecutive pixels of one sample) are the same pixels under the same blockIdx: the row
+// that spatial_gemm finishes in tout_s[C_pad][W + 4] IS the xs[Cin_pad][PT + 4] tile the projection stages first, in place.  `pre` of
+// the last block is still written (the projection backward reads it) but not read back, one kernel boundary goes, and the MLPs'
+// prologue -- two weight sets, about 100 KB of LDS images -- runs next to the `spatial` chain instead of behind it.
+//   phase 1: waves 0-3 run the forward chain of fno_spatial_kernel<NCB, NBN, 0> (the same phase functions in the same order on the
+//            same 256 threads, so every sum keeps its order; no pprev, no fused row DFT); waves 4-15 meanwhile request and commit the
+//            weights and biases of the MLP(s) and the lifting input tile (768 threads share those loops: NTB, T0).
+//   hand-over: tout_s = P.xs.  Its rows c >= C hold +0.f, which is what stage_pixels puts there: for such a row ks and s1 are zero
+//            (zero_padding of ks up to C_pad rows; spatial_hstep writes 0.f for o >= C) and so is bias_s, so the accumulator is a
+//            sum of (+-0) products from +0.f, plus 0.f.  `pre` leaves through spatial_out_dft's store loop.
+//   phase 2: the sequence of pwmlp_fwd_chain_kernel / pwmlp_fwd_kernel behind its staging, on all 16 waves.
+// Every barrier is at the top level and all 16 waves reach each of them.  The operands of the `spatial` GEMM lie behind the MLP
+// images (20 KB at the headline shape: 160,320 bytes in all).
+struct SpatialProjDev {
+    SpatialDev s;
+    ChainArgs c;
+};
+template <int NCB, int NBN, int NOB2>
+__global__ __launch_bounds__(1024) void fno_spatial_proj_fwd_kernel(SpatialProjDev f) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NW = FWD_WAVES, HQ = NW / 4, T0 = SPATIAL_NT, NTB = NW * 64 - SPATIAL_NT;
+    static_assert(NW * 64 == 1024 && 16 * (PT / 4) == SPATIAL_NT, "waves 0-3 hold the DFT table of fwd_finish");
+    const SpatialDev& a = f.s;
+    const ChainArgs& c = f.c;
+    const FwdLds P = fwd_carve(smem, c.p, nullptr);
+    float* behind = P.outs + HQ * c.p.Cout_pad * LDP;
+    FwdLds Lq = P;
+    if constexpr (NOB2 != 0) {     // second MLP: its partial tiles alias the first one's W1 image (dead by then)
+        Lq = fwd_carve(behind, c.l, P.w1s);
+        behind = Lq.b2s + c.l.Cout_pad;
+    }
+    SpatialLds S;
+    S.LDP = a.W + 4; S.LDK = a.C_pad + 4; S.LDS1 = a.NP + 4;
+    S.tout_s = P.xs;
+    S.tin_s = behind;
+    S.gs = S.tin_s + a.C_pad * S.LDP;
+    S.ks = S.gs + a.NP * S.LDP;
+    S.s1 = S.ks + a.C_pad * S.LDK;
+    S.bias_s = S.s1 + a.C_pad * S.LDS1;
+    S.pprev_s = S.ft = S.x1s = S.gks = nullptr;
+    const int w = wave_id();
+    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H, p0 = h * PT;
+    float4 ftv = make_float4(0.f, 0.f, 0.f, 0.f);      // DFT table of the lifting MLP's fused rows step: threads 0 .. 255
+    if (w < 4) {
+        SpatialLoads R;
+        spatial_issue<0>(a, b, h, false, R);
+        if constexpr (NOB2 != 0) if (c.l.x1_out) ftv = reinterpret_cast<const float4*>(c.l.FT)[threadIdx.x];
+        spatial_commit<0>(a, S, b, h, false, R);
+        spatial_hstep(a, S, b, h, R);
+    } else {
+        FwdLoadsT<3> qp, ql;
+        fwd_issue<NTB, T0>(c.p, qp);
+        if constexpr (NOB2 != 0) {
+            fwd_issue<NTB, T0>(c.l, ql);
+            stage_pixels<NTB, T0>(Lq.xs, c.l.x, b, c.l.Cin, c.l.Cin_pad, p0, c.l.P, c.l.vec_x != 0, c.skip);
+        }
+        fwd_commit<NTB, T0>(c.p, P, qp);
+        if constexpr (NOB2 != 0) fwd_commit<NTB, T0>(c.l, Lq, ql);
+    }
+    __syncthreads();   // 1: the operands of the `spatial` GEMM and every MLP image but P.xs complete
+    if (w < 4) spatial_gemm<NCB, NBN, 0>(a, S, w);
+    __syncthreads();   // 2: tout_s = P.xs complete
+    if (w < 4) spatial_out_dft<NCB, NBN>(a, S, b, h);      // `pre` (a.x1_out is NULL: no row DFT here)
+    fwd_compute<1, NW>(c.p, P);
+    __syncthreads();   // 3
+    fwd_finish<1, NW>(c.p, P, make_float4(0.f, 0.f, 0.f, 0.f), b, p0, h, NOB2 != 0 ? Lq.xs : nullptr, c.next_ch);
+    if constexpr (NOB2 != 0) {
+        __syncthreads();   // 4
+        fwd_compute<NOB2, NW>(c.l, Lq);
+        __syncthreads();   // 5
+        fwd_finish<NOB2, NW>(c.l, Lq, ftv, b, p0, h);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1403,6 +1480,134 @@ extern "C" int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* p, const float*
     dlwp_chan_dst gxd{gx, (long long)Cin * P, P, nullptr, nullptr};
     return dlwp_fno_spatial_lift_bwd(p, &s, &xs, w1, b1, w2, gx ? &gxd : nullptr, gx_accumulate, slab_lift,
                                      slab_lift_accumulate, Cin, Ch, stream);
+}
+
+// ---- the last block's forward `spatial` + the projection MLP (+ the next net call's lifting MLP) in one launch
+// (fno_spatial_proj_fwd_kernel).  Dispatched are the instantiations that compile for gfx950 without scratch and without vector
+// spills: C_pad 16 / 32 / 48 projection only, C_pad 16 / 32 with the chained lifting MLP (whose fused rows DFT needs NP == 16).
+struct ProjFwdLaunch {
+    SpatialProjDev f;
+    size_t lds;
+    int nob2;
+    double flops, bytes;
+};
+// validates and fills the launch; DLWP_E_UNSUPPORTED (error string untouched) where the two launches have to stay
+static int proj_fwd_prepare(ProjFwdLaunch& q, const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const float* pw1,
+                            const float* pb1, const float* pw2, const float* pb2, const dlwp_chan_dst* y1,
+                            const dlwp_chan_src* res1, int Ch1, int Cout1, const dlwp_chan_src* x2v, const float* lw1,
+                            const float* lb1, const float* lw2, const float* lb2, const dlwp_chan_dst* y2, int Cin2, int Ch2,
+                            const signed char* next_ch, float2* x1_out) {
+    const bool second = x2v != nullptr;
+    if (dlwp_fno_is_wide(p) || p->W != PT || p->C_pad > 48 || (second && (p->C_pad > 32 || p->NP != 16 || !x1_out || !y2)) ||
+        s->inverse_adjoint || s->x1_out || !s->out || !y1 || Ch1 < 1 || Cout1 < 1 || Cout1 > 8 || (second && (Cin2 < 1 || Cin2 > 64 || Ch2 < 1)) ||
+        dlwp_tune_or("FNO_FUSE_PROJ_FWD", 1) == 0)
+        return DLWP_E_UNSUPPORTED;
+    const int HW = p->H * p->W;
+    const dlwp_chan_src ps{s->out, (long long)p->C * HW, HW, nullptr, nullptr};     // what the projection would read back
+    size_t lds_floats;
+    const int rc = chain_make_args(q.f.c, lds_floats, &ps, pw1, pb1, pw2, pb2, y1, res1, p->C, Ch1, Cout1, second, x2v, lw1, lb1, lw2,
+                                   lb2, y2, Cin2, Ch2, p->C, next_ch, s->B, HW, p, x1_out);
+    if (rc) return rc;
+    if (second && !q.f.c.l.x1_out) return DLWP_E_UNSUPPORTED;
+    // the operands of the `spatial` GEMM behind the MLP images: tin_s, gs, ks, s1, bias_s
+    lds_floats += (size_t)p->C_pad * LDP + (size_t)p->NP * LDP + (size_t)p->C_pad * (p->C_pad + 4) + (size_t)p->C_pad * (p->NP + 4) + p->C_pad;
+    q.lds = sizeof(float) * lds_floats;
+    if (q.lds > (size_t)160 * 1024) return DLWP_E_UNSUPPORTED;
+    q.f.s = make_spatial_dev(p, s);
+    q.nob2 = second ? p->C_pad / 16 : 0;
+    const double pix = (double)s->B * HW;
+    q.flops = 2.0 * pix * p->C * (p->C + 2 * p->m2c) + 2.0 * pix * Ch1 * (p->C + Cout1);
+    q.bytes = 4.0 * pix * p->C * 2 + 4.0 * pix * (p->C + Cout1);
+    if (second) { q.flops += 2.0 * pix * Ch2 * (Cin2 + p->C); q.bytes += 4.0 * pix * (Cin2 + p->C); }
+    return DLWP_OK;
+}
+static int proj_fwd_launch(const ProjFwdLaunch& q, const dlwp_fno_plan* p, int B, hipStream_t stream) {
+    const int ncb = p->C_pad / 16, nbn = p->NP / 16;
+    const dim3 grid(B * p->H);
+    dlwp_prof_scope prof(stream, q.flops, q.bytes, "fno_spatial_proj_fwd_kernel<%d, %d, %d>", ncb, nbn, q.nob2);
+    int rc;
+#define LAUNCH(N, M, O)                                                                                            \
+    {                                                                                                              \
+        if ((rc = set_lds(fno_spatial_proj_fwd_kernel<N, M, O>, q.lds, "fno_spatial_proj_fwd")) != DLWP_OK) return rc; \
+        hipLaunchKernelGGL((fno_spatial_proj_fwd_kernel<N, M, O>), grid, dim3(1024), q.lds, stream, q.f);           \
+    }
+    switch (ncb * 100 + nbn * 10 + q.nob2) {       // proj_fwd_prepare() has refused everything else
+        case 110: LAUNCH(1, 1, 0) break; case 120: LAUNCH(1, 2, 0) break;
+        case 210: LAUNCH(2, 1, 0) break; case 220: LAUNCH(2, 2, 0) break;
+        case 310: LAUNCH(3, 1, 0) break; case 320: LAUNCH(3, 2, 0) break;
+        case 111: LAUNCH(1, 1, 1) break; case 212: LAUNCH(2, 1, 2) break;
+        default: return DLWP_E_UNSUPPORTED;
+    }
+#undef LAUNCH
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+int dlwp_fno_spatial_proj_fwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const float* pw1, const float* pb1,
+                              const float* pw2, const float* pb2, const dlwp_chan_dst* y1, const dlwp_chan_src* res1, int Ch1,
+                              int Cout1, const dlwp_chan_src* x2v, const float* lw1, const float* lb1, const float* lw2,
+                              const float* lb2, const dlwp_chan_dst* y2, int Cin2, int Ch2, const signed char* next_ch,
+                              float2* x1_out, hipStream_t stream) {
+    ProjFwdLaunch q;
+    const int rc = proj_fwd_prepare(q, p, s, pw1, pb1, pw2, pb2, y1, res1, Ch1, Cout1, x2v, lw1, lb1, lw2, lb2, y2, Cin2, Ch2,
+                                    next_ch, x1_out);
+    return rc ? rc : proj_fwd_launch(q, p, s->B, stream);
+}
+
+// Test entry points on contiguous tensors.  dlwp_fno_block_proj_fwd: one FNO block (rows DFT, per-mode stage) whose `spatial` stage
+// is the fused launch: pre, xhat as dlwp_fno_block_fwd; frame [B, Cout1, H, W] = projection(pre) (+ res); and, with window != NULL,
+// h0_next [B, C, H, W] = lifting(window [B, Cin2, H, W] with channel next_ch[o] >= 0 taken from frame channel o, in LDS) and its
+// rows DFT x1_next [B][H][m2c][C] complex.  DLWP_E_UNSUPPORTED, nothing launched, where the trainer keeps the two launches.
+// dlwp_pwmlp_proj_lift_fwd: the second of those two launches (pwmlp_fwd_chain_kernel, or pwmlp_fwd_kernel without a window) on
+// the same tensors, behind dlwp_fno_block_fwd.
+extern "C" int dlwp_fno_block_proj_fwd(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec, const float* wskip,
+                                       const float* bias, float* pre, float* xhat, const float* pw1, const float* pb1,
+                                       const float* pw2, const float* pb2, const float* res, float* frame, int Ch1, int Cout1,
+                                       const float* window, const float* lw1, const float* lb1, const float* lw2, const float* lb2,
+                                       float* h0_next, float* x1_next, int Cin2, int Ch2, const signed char* next_ch, int B,
+                                       void* workspace, void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && pre && xhat && pw1 && pb1 && pw2 && pb2 && frame && workspace && B > 0 &&
+                     (!window || (lw1 && lb1 && lw2 && lb2 && h0_next && x1_next && next_ch)),
+                 DLWP_E_INVALID, "fno_block_proj_fwd: NULL argument or B<=0");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    float2* x1 = static_cast<float2*>(workspace);
+    float2* y = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
+    const long long HW = (long long)p->H * p->W;
+    dlwp_fno_spatial_args s{};
+    s.tin = x; s.act_tin = act_in; s.spec = y; s.wskip = wskip; s.bias = bias; s.out = pre; s.B = B;
+    const dlwp_chan_dst fd{frame, Cout1 * HW, HW, nullptr, nullptr};
+    const dlwp_chan_src rs{res, Cout1 * HW, HW, nullptr, nullptr};
+    const dlwp_chan_src wsrc{window, Cin2 * HW, HW, nullptr, nullptr};
+    const dlwp_chan_dst hd{h0_next, p->C * HW, HW, nullptr, nullptr};
+    ProjFwdLaunch q;
+    int rc = proj_fwd_prepare(q, p, &s, pw1, pb1, pw2, pb2, &fd, res ? &rs : nullptr, Ch1, Cout1, window ? &wsrc : nullptr, lw1, lb1,
+                              lw2, lb2, &hd, Cin2, Ch2, next_ch, reinterpret_cast<float2*>(x1_next));
+    if (rc) return rc;
+    if ((rc = dlwp_fno_rows_dft(p, x, act_in, 0, x1, B, stream))) return rc;
+    if ((rc = dlwp_fno_mix_fwd(p, x1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<float2*>(xhat), y, B, stream))) return rc;
+    return proj_fwd_launch(q, p, B, stream);
+}
+
+extern "C" int dlwp_pwmlp_proj_lift_fwd(const dlwp_fno_plan* p, const float* pre, const float* pw1, const float* pb1,
+                                        const float* pw2, const float* pb2, const float* res, float* frame, int Ch1, int Cout1,
+                                        const float* window, const float* lw1, const float* lb1, const float* lw2,
+                                        const float* lb2, float* h0_next, float* x1_next, int Cin2, int Ch2,
+                                        const signed char* next_ch, int B, void* stream_) {
+    DLWP_REQUIRE(p && pre && pw1 && pb1 && pw2 && pb2 && frame && B > 0 &&
+                     (!window || (lw1 && lb1 && lw2 && lb2 && h0_next && x1_next && next_ch)),
+                 DLWP_E_INVALID, "pwmlp_proj_lift_fwd: NULL argument or B<=0");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const long long HW = (long long)p->H * p->W;
+    const dlwp_chan_src ps{pre, p->C * HW, HW, nullptr, nullptr};
+    const dlwp_chan_dst fd{frame, Cout1 * HW, HW, nullptr, nullptr};
+    const dlwp_chan_src rs{res, Cout1 * HW, HW, nullptr, nullptr};
+    if (!window) return dlwp_pwmlp_fwd_ex(&ps, pw1, pb1, pw2, pb2, &fd, res ? &rs : nullptr, B, p->C, Ch1, Cout1, (int)HW, stream);
+    const dlwp_chan_src wsrc{window, Cin2 * HW, HW, nullptr, nullptr};
+    const dlwp_chan_dst hd{h0_next, p->C * HW, HW, nullptr, nullptr};
+    const int rc = dlwp_pwmlp_fwd_chain_ex(&ps, pw1, pb1, pw2, pb2, &fd, res ? &rs : nullptr, p->C, Ch1, Cout1, &wsrc, lw1, lb1, lw2, lb2,
+                                           &hd, Cin2, Ch2, p->C, next_ch, B, (int)HW, p, reinterpret_cast<float2*>(x1_next), stream);
+    DLWP_REQUIRE(rc != DLWP_E_UNSUPPORTED, DLWP_E_UNSUPPORTED, "pwmlp_proj_lift_fwd: these shapes do not take the chained launch");
+    return rc;
 }
 
 extern "C" int dlwp_fno_block_slab_fold(const dlwp_fno_plan* p, const float* slab, float* g_wskip, float* g_bias, int B,

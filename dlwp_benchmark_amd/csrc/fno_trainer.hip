@@ -213,6 +213,23 @@ int enqueue_forward(dlwp_fno_trainer* tr, bool keep, hipStream_t s, bool fused =
                                              tr->plan, tr->x1, s))) return rc;
         }
         lifted = false;
+        dlwp_chan_src ps{pre + (NL - 1) * actB, tr->act, HW, nullptr, nullptr};
+        float* oplane = tr->out + (long long)ci.out_slot * tr->frame;
+        dlwp_chan_dst od{oplane, tr->traj_out, HW, nullptr, nullptr};
+        dlwp_chan_src rs{ci.res, ci.res_bs, HW, nullptr, nullptr};  // out = last frame + net (dlwp fno.py:103)
+        // projection of this call chained with the lifting of the next: the frame(s) just produced go to the next window in LDS
+        const bool chain = k + 1 < tr->ncalls && c.out_channels <= 8;
+        signed char next_ch[8];
+        for (int o = 0; o < 8; ++o) next_ch[o] = -1;
+        const size_t t1 = (size_t)(k + 1) * tr->Cin;
+        if (chain)
+            for (int o = 0; o < c.out_channels; ++o)
+                for (int ch = 0; ch < tr->Cin; ++ch)
+                    if (tr->h_src[t1 + ch] == oplane + (long long)o * HW && tr->h_bs[t1 + ch] == tr->traj_out) next_ch[o] = (signed char)ch;
+        const int k1 = keep ? k + 1 : 0;
+        dlwp_chan_src xs1{nullptr, 0, 0, tr->src_tab + (long long)(k + 1) * tr->Cin, tr->bstride_tab + (long long)(k + 1) * tr->Cin};
+        dlwp_chan_dst h0d1{tr->h0 + k1 * actB, tr->act, HW, nullptr, nullptr};
+        bool projected = false;          // the last block's `spatial` launch has run the projection (and the next lifting) too
         for (int l = 0; l < NL; ++l) {
             if ((rc = dlwp_fno_mix_fwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)),
                                        xhat + l * xhatB, tr->spec, c.B, s))) return rc;
@@ -224,23 +241,21 @@ int enqueue_forward(dlwp_fno_trainer* tr, bool keep, hipStream_t s, bool fused =
             a.x1_out = l < NL - 1 ? tr->x1 : nullptr;
             a.x1_act = 1;
             a.B = c.B;
+            if (l == NL - 1 && keep) {
+                // training rollout (activations kept): the last block's `spatial`, the projection and, behind it, the next call's
+                // lifting MLP as one launch where the shapes allow; otherwise the launches below.  The evaluation path
+                // (keep == false) always keeps them: the fused launch was built for and measured on the training step, and
+                // pwmlp_fwd_chain_kernel stays the kernel an evaluation rollout is tested on
+                rc = dlwp_fno_spatial_proj_fwd(tr->plan, &a, w.pw1, w.pb1, w.pw2, w.pb2, &od, ci.res ? &rs : nullptr, c.projection,
+                                               c.out_channels, chain ? &xs1 : nullptr, w.lw1, w.lb1, w.lw2, w.lb2, &h0d1, tr->Cin,
+                                               c.lifting, next_ch, tr->x1, s);
+                if (rc == DLWP_OK) { projected = true; lifted = chain; break; }
+                if (rc != DLWP_E_UNSUPPORTED) return rc;
+            }
             if ((rc = dlwp_fno_spatial(tr->plan, &a, s))) return rc;
         }
-        dlwp_chan_src ps{pre + (NL - 1) * actB, tr->act, HW, nullptr, nullptr};
-        float* oplane = tr->out + (long long)ci.out_slot * tr->frame;
-        dlwp_chan_dst od{oplane, tr->traj_out, HW, nullptr, nullptr};
-        dlwp_chan_src rs{ci.res, ci.res_bs, HW, nullptr, nullptr};  // out = last frame + net (dlwp fno.py:103)
-        if (k + 1 < tr->ncalls && c.out_channels <= 8) {
-            // projection of this call chained with the lifting of the next: the frame(s) just produced go to the next window in LDS
-            signed char next_ch[8];
-            for (int o = 0; o < 8; ++o) next_ch[o] = -1;
-            const size_t t1 = (size_t)(k + 1) * tr->Cin;
-            for (int o = 0; o < c.out_channels; ++o)
-                for (int ch = 0; ch < tr->Cin; ++ch)
-                    if (tr->h_src[t1 + ch] == oplane + (long long)o * HW && tr->h_bs[t1 + ch] == tr->traj_out) next_ch[o] = (signed char)ch;
-            const int k1 = keep ? k + 1 : 0;
-            dlwp_chan_src xs1{nullptr, 0, 0, tr->src_tab + (long long)(k + 1) * tr->Cin, tr->bstride_tab + (long long)(k + 1) * tr->Cin};
-            dlwp_chan_dst h0d1{tr->h0 + k1 * actB, tr->act, HW, nullptr, nullptr};
+        if (projected) continue;
+        if (chain) {
             rc = dlwp_pwmlp_fwd_chain_ex(&ps, w.pw1, w.pb1, w.pw2, w.pb2, &od, ci.res ? &rs : nullptr, C, c.projection, c.out_channels,
                                          &xs1, w.lw1, w.lb1, w.lw2, w.lb2, &h0d1, tr->Cin, c.lifting, C, next_ch, c.B, HW,
                                          tr->plan, tr->x1, s);

@@ -53,13 +53,13 @@ __device__ __forceinline__ f32x4 frag_col(const float* __restrict__ M, int R, in
 }
 
 // pixel tile [C_pad][PT] of a channel view -> LDS (row stride LDP); 16-byte loads along pixels
-// (channels in `skip` are left alone: a fused producer in the same workgroup writes them)
-template <typename SRC>
+// (channels in `skip` are left alone: a fused producer in the same workgroup writes them); NT, T0: see wg_stride / wg_thread
+template <int NT = 0, int T0 = 0, typename SRC>
 __device__ __forceinline__ void stage_pixels(float* dst, const SRC& s, int b, int C, int C_pad, int p0, int P,
                                              bool vec_ok, unsigned long long skip = 0ull) {
     if (vec_ok) {
 #pragma unroll 2
-        for (int u = threadIdx.x; u < C_pad * (PT / 4); u += blockDim.x) {
+        for (int u = wg_thread<T0>(); u < C_pad * (PT / 4); u += wg_stride<NT>()) {
             const int c = u / (PT / 4), q = u % (PT / 4);
             if (c < 64 && ((skip >> c) & 1ull)) continue;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -70,7 +70,7 @@ __device__ __forceinline__ void stage_pixels(float* dst, const SRC& s, int b, in
             *reinterpret_cast<float4*>(&dst[c * LDP + 4 * q]) = v;
         }
     } else {
-        for (int idx = threadIdx.x; idx < C_pad * PT; idx += blockDim.x) {
+        for (int idx = wg_thread<T0>(); idx < C_pad * PT; idx += wg_stride<NT>()) {
             const int c = idx / PT, p = idx % PT;
             if (c < 64 && ((skip >> c) & 1ull)) continue;
             float v = 0.f;

@@ -161,6 +161,26 @@ int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* plan, const float* h0, con
                                  const float* w2, float* gx, int gx_accumulate, float* slab_lift,
                                  int slab_lift_accumulate, int B, int Cin, int Ch, void* workspace, void* stream);
 
+/* The forward of the LAST block fused with the projection MLP on its result, as the training rollout runs it: rows DFT,         */
+/* per-mode stage, then ONE launch for `spatial` + projection (+ the next net call's lifting MLP with its rows DFT) -- the row  */
+/* `spatial` finishes in LDS is the projection's input tile; pre is written, not read back.  pre, xhat as dlwp_fno_block_fwd;   */
+/* frame [B][Cout1][H W] = projection(pre) (+ res, nullable, frame's layout).  window != NULL adds the second MLP:              */
+/* h0_next [B][C][H W] = lifting(window [B][Cin2][H W], whose channel next_ch[o] >= 0 (host array of 8) is taken from frame      */
+/* channel o in LDS and not read) and x1_next [B][H][m2c][C][2] its W-axis DFT.  Outputs bit for bit those of                   */
+/* dlwp_fno_block_fwd followed by dlwp_pwmlp_proj_lift_fwd (the two-launch form on the same tensors: pwmlp_fwd_chain_kernel, or */
+/* pwmlp_fwd_kernel without a window).  DLWP_E_UNSUPPORTED, nothing launched, where the library keeps the two launches: rows    */
+/* that are not 64 wide, more than 48 channels (32 with a window, which also needs m2c <= 8), wide / 3-D plans, Cout1 > 8,       */
+/* shapes the chained launch refuses, more than 160 KiB of LDS, or the knob FNO_FUSE_PROJ_FWD = 0.                              */
+int dlwp_fno_block_proj_fwd(const dlwp_fno_plan* plan, const float* x, int act_in, const float* wspec, const float* wskip,
+                            const float* bias, float* pre, float* xhat, const float* pw1, const float* pb1, const float* pw2,
+                            const float* pb2, const float* res, float* frame, int Ch1, int Cout1, const float* window,
+                            const float* lw1, const float* lb1, const float* lw2, const float* lb2, float* h0_next,
+                            float* x1_next, int Cin2, int Ch2, const signed char* next_ch, int B, void* workspace, void* stream);
+int dlwp_pwmlp_proj_lift_fwd(const dlwp_fno_plan* plan, const float* pre, const float* pw1, const float* pb1, const float* pw2,
+                             const float* pb2, const float* res, float* frame, int Ch1, int Cout1, const float* window,
+                             const float* lw1, const float* lb1, const float* lw2, const float* lb2, float* h0_next,
+                             float* x1_next, int Cin2, int Ch2, const signed char* next_ch, int B, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Training-step pieces (nsbench/scripts/train.py:113-131: MSELoss, Adam).               */
 /* loss_out (device, 1 float) += sum((a-b)^2) * scale                                    */
