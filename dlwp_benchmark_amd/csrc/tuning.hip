@@ -74,6 +74,7 @@ Knob g_knobs[] = {
     {"DHCONV_APPLY", "1: the round-4 spectral-convolution kernel (one 256-row chunk per workgroup) instead of the pipelined one", 0, false},
     {"DHCONV_RC", "rows per chunk of the pipelined spectral-convolution kernel: 64 or 128 (default 128)", 0, false},
     {"REMAP_PATH", "dlwp_remap_gather4: 0 by plane size (default), 1 the LDS-staged kernel (refused when a plane does not fit), 2 the direct kernel", 0, false},
+    {"DIAG_PATH", "dlwp_rollout_diag on HPX planes: 0 by plane size (default), 1 the LDS-staged kernel (refused when two planes do not fit), 2 the direct kernel", 0, false},
     {"FNO_FUSE_LIFT_BWD", "0: block 0's backward `spatial` and the lifting backward of the FNO rollout stay two launches (default 1: one launch, fno_spatial_lift_bwd_kernel, where the shapes allow)", 0, false},
     {"FNO_FUSE_PROJ_FWD", "0: the last block's forward `spatial` and the projection (+ next lifting) MLP of the FNO training rollout stay two launches (default 1: one launch, fno_spatial_proj_fwd_kernel, where the shapes allow)", 0, false},
     {"CHAIN_ROT", "0: no rotation of the wave -> feature-tile assignment in the one-launch MLP chains (default 1)", 0, false},

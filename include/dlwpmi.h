@@ -612,6 +612,39 @@ int dlwp_remap_csr(const float* src, const int* rowptr, const int* col, const fl
 int dlwp_hpx_error_moments(const float* out_hpx, const float* target_hpx, const float* climatology_ll,
                            const float* row_weights, const int* idx, const float* w, int B, int G, int n, int H, int W,
                            float* moments, void* stream);
+/* Long-rollout diagnostics in one read of a chunk of outputs and targets (csrc/rollout_diag.hip; the physical-soundness half of      */
+/* compute_metrics, scripts/evaluate.py:548-588, beside its per-lead RMSE / ACC :514-546, and the persistence / climatology forecasts */
+/* of scripts/build_baselines.py:23-67).  ONE entry point for both meshes: idx / w == NULL scores lat-lon planes, out / target        */
+/* [Bc][Tc][V][H][W]; with the hpx2ll table idx / w [H W][4] (both, 16-byte aligned; 0 <= idx < 12 n^2 is the caller's precondition)  */
+/* out / target are [Bc][Tc][V][12][n][n] and are interpolated inside the kernel (no lat-lon tensor is written).                      */
+/*   out      : frame (b, t) of variable v starts at out + b out_bstride + t out_tstride + v plane (element strides >= 0, plane = H W  */
+/*              or 12 n^2; a time stride of 0 is the persistence forecast, one frame per sample read in place); NULL with clim given: */
+/*              the forecast is the climatology.  target is dense.                                                                    */
+/*   scale, shift [V] or NULL (identity): physical = x * scale + shift.  row_weights [H] or NULL.                                      */
+/*   clim [M][V][H][W] on lat-lon in PHYSICAL units with month [Bc][Tc] (int32, 0 <= month < M: the caller's precondition; the kernel */
+/*              clamps), both or neither.                                                                                             */
+/*   t_begin  : global index of the chunk's first frame in a rollout of T frames; [w0, w1): a window of global frame indices.         */
+/*   moments [Bc][T][V][5] : the five sums of dlwp_error_moments per sample, lead time and variable in physical units; WRITTEN for the */
+/*              chunk's frames (columns 2-4 are 0 without clim)                                                                       */
+/*   zonal [2][Bc][T][V][H]: the longitude mean of the de-normalised out (0) and target (1); WRITTEN for the chunk's frames           */
+/*   wsum [2][Bc][V][H][W] : the sum of the NORMALISED out / target over the chunk's frames inside the window, ACCUMULATED into: the  */
+/*              caller zeroes it before the first chunk; the window mean is wsum / (w1 - w0) * scale + shift                           */
+/*   ws       : dlwp_rollout_diag_ws_floats(Bc, Tc, V, H, W, hpx) floats of scratch (per-wave moment partials)                         */
+/* All sums are taken of the normalised values (the climatology is brought into normalised units per pixel) and scaled afterwards.    */
+/* No atomics, one writer per address, a summation order that depends on (H, W, mesh) only: two runs give the same bits, and scoring  */
+/* a rollout in time chunks and batch chunks gives the bits of one call (order: csrc/rollout_diag.hip).  HPX planes are staged in LDS */
+/* while two planes fit 72 KiB, else gathered from global memory; the knob DIAG_PATH (0 auto, 1 LDS, 2 direct) forces one.  W <= 512.  */
+long long dlwp_rollout_diag_ws_floats(int Bc, int Tc, int V, int H, int W, int hpx);
+int dlwp_rollout_diag(const float* out, long long out_bstride, long long out_tstride, const float* target,
+                      const float* scale, const float* shift, const float* row_weights, const float* clim,
+                      const int* month, int M, const int* idx, const float* w, int n, int Bc, int Tc, int V, int H, int W,
+                      int t_begin, int T, int w0, int w1, float* moments, float* zonal, float* wsum, float* ws,
+                      void* stream);
+/* Group means (the monthly climatology of scripts/build_baselines.py:52-62): frames [N][P], group [N] (int32, 0 <= group < G: the    */
+/* caller's precondition; other values are skipped) -> mean [G][P], count [G] (int32).  Each frame is read once, added in ascending   */
+/* n, no atomics; an empty group gives count 0 and a zero row.  G <= 64.                                                              */
+int dlwp_group_mean(const float* frames, const int* group, float* mean, int* count, long long N, long long P, int G,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Token-level building blocks of the AFNO / Swin / Pangu blocks (nn.Linear, nn.LayerNorm, */
