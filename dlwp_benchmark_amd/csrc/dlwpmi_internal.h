@@ -91,6 +91,14 @@ int dlwp_fno_mix_fwd(const dlwp_fno_plan* p, const float2* x1, const float2* wsp
 // backward: ghat = H-step of g1; gx[b][j][kx][i] = sum_o ghat conj(w); gw += conj(xhat) ghat
 int dlwp_fno_mix_bwd(const dlwp_fno_plan* p, const float2* g1, const float2* wspec,
                      const float2* xhat, float2* gxhat, float2* g_wspec, int B, hipStream_t stream);
+// the same launch also forming the by-products of the block's backward `spatial` (narrow 2-D plans): the skip-weight / bias
+// gradient partial of every image row from tin (g_pre of the block) and pprev (the block's stored input; GELU applied when
+// act_prev) into gslab, bit for bit what the two-role `spatial` launch writes; the caller then runs `spatial` with neither gslab nor
+// g_wskip / g_bias.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) for wide and 3-D plans, for shapes whose
+// backward `spatial` does not take the two-role kernel, and with the knob FNO_SKIP_WGRAD_IN_MIX = 0.
+int dlwp_fno_mix_bwd_skipgrad(const dlwp_fno_plan* p, const float2* g1, const float2* wspec, const float2* xhat, float2* gxhat,
+                              float2* g_wspec, const float* tin, const float* pprev, int act_prev, float* gslab,
+                              int gslab_accumulate, int B, hipStream_t stream);
 // spatial stage (one workgroup per image row, all channels).
 struct dlwp_fno_spatial_args {
     const float* tin;        // [B,C,H,W] GEMM input (fwd: x, bwd: g_pre)
@@ -118,6 +126,9 @@ long long dlwp_fno_gslab_stride(int C);
 // (dlwp_pwmlp_bwd_ex's x / w1 / b1 / w2 / gx / slab, gy = the gradient `spatial` would have written) as one launch; every output
 // bit for bit the two launches'.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where the shapes need the two
 // launches -- other than 64-wide rows, wide or 3-D plans, C_pad 64, Cin > 32 -- or the knob FNO_FUSE_LIFT_BWD is 0.
+// s->gslab == NULL: the by-products were formed by dlwp_fno_mix_bwd_skipgrad and the `spatial` phase runs its chain alone.
+// dlwp_fno_spatial_lift_bwd_fuses: whether shapes and knob allow the one launch (what the call decides on besides `s`).
+bool dlwp_fno_spatial_lift_bwd_fuses(const dlwp_fno_plan* p, int Cin, int Ch);
 int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
                               const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
                               int slab_accumulate, int Cin, int Ch, hipStream_t stream);

@@ -445,6 +445,7 @@ template <int NCB, int NBN, int MODE>
 __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
     static_assert(MODE == 1 || MODE == 2, "backward modes only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr bool ROLE_B = true;
 #include "fno_spatial_roles_head.inc.h"
 
     if (role_a) {
@@ -472,11 +473,13 @@ __global__ __launch_bounds__(512) void fno_spatial_roles_kernel(SpatialDev a) {
 //            second barrier (pprev_s, ft, x1s, gs, ks, s1, gks), so the launch needs no more LDS than the larger of its phases.
 // Same row, same blockIdx, hence the same skip-weight slab and the same lifting slab as the two launches: every output is bit for
 // bit theirs.  MODE is 2: the input of block 0 is the lifting MLP's output, which is not activated.
+// ROLE_B == false: phase 1 without role B's work, for a sweep whose per-mode launch has formed the by-products of block 0
+// (fno_mix_bwd_skipgrad_kernel); waves 4-7 then only arrive at the two barriers of phase 1.
 struct SpatialLiftDev {
     SpatialDev s;
     BwdArgs m;
 };
-template <int NCB, int NBN, int NIB>
+template <int NCB, int NBN, int NIB, bool ROLE_B = true>
 __global__ __launch_bounds__(512) void fno_spatial_lift_bwd_kernel(SpatialLiftDev f) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NOB = NCB, NW = 8;
@@ -840,8 +843,11 @@ __global__ __launch_bounds__(MIXT) void fno_mix_fwd_kernel(MixDev a) {
     DLWP_STAMP(24);
 }
 
-template <bool LDSW>
-__global__ __launch_bounds__(MIXT) void fno_mix_bwd_kernel(MixDev a) {
+// The per-mode backward workgroup: the whole of fno_mix_bwd_kernel, and the mode workgroups of fno_mix_bwd_skipgrad_kernel.
+// The XCD-aware order below needs the workgroup's index among the mode workgroups and their count: blockIdx.x and gridDim.x in
+// the first kernel (read where they always were: its instruction stream stays what it was), `block` and `nmodes` when HOSTED.
+template <bool LDSW, bool HOSTED>
+__device__ __forceinline__ void mix_bwd_body(const MixDev& a, const int block, const int nmodes) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int BC = a.B * a.C, C = a.C;
     const int NS = mix_split(BC, a.H < C ? a.H : C);
@@ -851,9 +857,9 @@ __global__ __launch_bounds__(MIXT) void fno_mix_bwd_kernel(MixDev a) {
     float2* part = xsv + BC;                       // [max(NS, NS2)][BC]
     float2* tws = part + (NS > NS2 ? NS : NS2) * BC;   // [H]
     float2* ws = tws + a.H;                        // [C][C+1]   (LDSW)
-    int mode = blockIdx.x;
+    int mode = HOSTED ? block : (int)blockIdx.x;
     {
-        const int nm = gridDim.x, full = (nm / 8) * 8;
+        const int nm = HOSTED ? nmodes : (int)gridDim.x, full = (nm / 8) * 8;
         if (mode < full) mode = (mode % 8) * (nm / 8) + mode / 8;
     }
     const int kx = mode / a.m1, j = mode - kx * a.m1;
@@ -913,6 +919,159 @@ __global__ __launch_bounds__(MIXT) void fno_mix_bwd_kernel(MixDev a) {
     // gx[b][i] = sum_o ghat[b][o] conj(w[i][o])
     if (LDSW) mix_contract<1, 1>(gh, ws, C + 1, a.y + mofs, bstr, a.B, C);
     else mix_contract<1, 1>(gh, wm, C, a.y + mofs, bstr, a.B, C);
+}
+
+template <bool LDSW>
+__global__ __launch_bounds__(MIXT) void fno_mix_bwd_kernel(MixDev a) {
+    mix_bwd_body<LDSW, false>(a, 0, 0);
+}
+
+// ---- the per-mode backward launch as host of the backward `spatial` by-products.  The skip-weight gradient gK and the bias
+// gradient of block l need only g_pre of the block (`tin`) and its stored input (`pprev`), both complete before the block's
+// per-mode launch starts, and feed nothing on the chain; the per-mode launch has one workgroup per kept mode (84 at the headline
+// shape), so most CUs idle through it.  Here the launch has m1 * m2c + ceil(B * H / 2) workgroups:
+//   blockIdx.x <  m1 * m2c : mix_bwd_body, unchanged (lowest indices: dispatched first)
+//   the others             : TWO image rows each, rows 2 p and 2 p + 1 with p = blockIdx.x - m1 * m2c.  Waves 0-3 form the first
+//                            row's gK partial and bias gradient into that row's slab, waves 4-7 the second row's: each half does
+//                            what role B of fno_spatial_roles_kernel does for its row, with the same mapping of chunks to waves
+//                            and of elements to threads, so every slab float is bit for bit role B's: partial w2 is one
+//                            mfma16_chunk chain from zero over the chunks kc = w2, w2 + 4, ... on fragments read straight from
+//                            global memory; the partials are summed w2 = 0 .. 3 from 0.f, then old + v; the bias gradient is the
+//                            sequential sum over x = 0 .. W-1 from 0.f (read from global `tin`, the values tin_s holds), then
+//                            old + s.
+// Two rows per workgroup keep the launch at 212 workgroups for the headline's 256 rows, one per CU: with one row per workgroup
+// (340 workgroups) mode and row workgroups shared CUs and the launch took 7.3 us instead of 6.1; with two it takes 6.4
+// (profiles/r12_experiments.md).  The `spatial` launch behind it runs the chain alone.  No workgroup reads what another one of
+// the launch writes.
+struct SkipGradDev {
+    const float* tin; const float* pprev; float* gslab;
+    int gslab_accumulate, act_prev;
+    int C, H, W, C_pad, nmodes, nrows;
+    FastDiv dC;
+};
+struct MixSkipDev {
+    MixDev m;
+    SkipGradDev s;
+};
+
+template <int NCB>
+__device__ __forceinline__ void skipgrad_rows(const SkipGradDev& a, float* smem, const int pair) {
+    constexpr int NTB = 256;                      // threads of one half
+    const int tid = threadIdx.x, lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane(wave_id());   // wave-uniform: `live` and the loop bounds are scalar
+    const int w2 = w & 3, half = w >> 2, tb = tid & (NTB - 1);
+    const int r = lane & 15, g = lane >> 4;
+    const int row = 2 * pair + half;
+    const bool live = row < a.nrows;              // an odd row count leaves the last workgroup's second half idle
+    const int b = row / a.H, h = row - b * a.H;
+    const int W4 = a.W / 4, nwb = a.W / 16, CC = a.C * a.C;
+    float* gks = smem + half * 4 * a.C_pad * a.C_pad;   // [4 waves][C_pad][C_pad] of this half
+    const long long slab_off = (long long)row * (((long long)CC + a.C + 3) & ~3LL);   // spatial_slab_off of the row's index
+    const bool slab_acc = a.gslab_accumulate != 0;
+    constexpr int SLQ = 4;
+    float slab_old[SLQ], slab_b_old = 0.f;
+#pragma unroll
+    for (int k = 0; k < SLQ; ++k) slab_old[k] = 0.f;
+    const int bias_c = 4 * lane + w2;             // bias-gradient channel of this lane (lanes 0-15 of each wave)
+    constexpr int BQ = 16;                        // ... its row pieces read ahead (a whole row at W = 64)
+    const bool bias_on = live && lane < 16 && bias_c < a.C;
+    float4 bq[BQ];
+    const float4* brow = nullptr;
+    if (live) {
+        // ---- issue phase: the running partials of the row's slab, the bias rows, then the fragments of the first chunk
+        if (slab_acc) {
+#pragma unroll
+            for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tb + NTB * k, CC - 1)];
+            slab_b_old = a.gslab[slab_off + CC + min(bias_c, a.C - 1)];
+        }
+        brow = reinterpret_cast<const float4*>(a.tin + (((long long)b * a.C + min(bias_c, a.C - 1)) * a.H + h) * a.W);
+        if (bias_on) {
+#pragma unroll
+            for (int q = 0; q < BQ; ++q) bq[q] = brow[min(q, W4 - 1)];
+        }
+        // gK partial of wave w2: sum over its 16-pixel chunks of g_pre[o][w] * act(x)[i][w]
+        f32x4 kacc[NCB][NCB];
+#pragma unroll
+        for (int ob = 0; ob < NCB; ++ob)
+#pragma unroll
+            for (int ib = 0; ib < NCB; ++ib) kacc[ob][ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kc = w2; kc < nwb; kc += 4) {
+            f32x4 ta[NCB], pb[NCB];
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {   // clamped addresses, selects afterwards: all loads in flight together
+                const int c = cb * 16 + r;
+                const long long off = (((long long)b * a.C + min(c, a.C - 1)) * a.H + h) * a.W + kc * 16 + 4 * g;
+                ta[cb] = *reinterpret_cast<const f32x4*>(&a.tin[off]);
+                pb[cb] = *reinterpret_cast<const f32x4*>(&a.pprev[off]);
+            }
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) {
+                const bool ok = cb * 16 + r < a.C;
+                ta[cb] = ok ? ta[cb] : f32x4{0.f, 0.f, 0.f, 0.f};
+                pb[cb] = ok ? pb[cb] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int ib = 0; ib < NCB; ++ib) {
+                f32x4 b4 = pb[ib];
+                if (a.act_prev) {
+                    b4 = gelu4(b4);
+                }
+#pragma unroll
+                for (int ob = 0; ob < NCB; ++ob) kacc[ob][ib] = mfma16_chunk(ta[ob], b4, kacc[ob][ib]);
+            }
+        }
+#pragma unroll
+        for (int ob = 0; ob < NCB; ++ob)
+#pragma unroll
+            for (int ib = 0; ib < NCB; ++ib)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) gks[((w2 * NCB + ob) * 16 + 4 * g + j) * a.C_pad + ib * 16 + r] = kacc[ob][ib][j];
+    }
+    __syncthreads();   // the four gK partials of both rows complete
+    if (!live) return;
+    // cross-wave sum of the partials (w2 = 0 .. 3 from 0.f), then old + v into the slab: all LDS reads first, then the sums
+    float pq[SLQ][4];
+#pragma unroll
+    for (int k = 0; k < SLQ; ++k) {
+        const int idx = min(tb + NTB * k, CC - 1), o = fastdiv(idx, a.dC), i = idx - o * a.C;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pq[k][q] = gks[(q * a.C_pad + o) * a.C_pad + i];
+    }
+#pragma unroll
+    for (int k = 0; k < SLQ; ++k) {
+        const int idx = tb + NTB * k;
+        float v = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v += pq[k][q];
+        if (idx < CC) a.gslab[slab_off + idx] = slab_old[k] + v;
+    }
+    for (int idx = tb + NTB * SLQ; idx < CC; idx += NTB) {
+        const int o = fastdiv(idx, a.dC), i = idx - o * a.C;
+        float v = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v += gks[(q * a.C_pad + o) * a.C_pad + i];
+        const float old = slab_acc ? a.gslab[slab_off + idx] : 0.f;
+        a.gslab[slab_off + idx] = old + v;
+    }
+    if (bias_on) {
+        float bias_sum = 0.f;
+#pragma unroll
+        for (int q = 0; q < BQ; ++q)
+            if (q < W4) { bias_sum += bq[q].x; bias_sum += bq[q].y; bias_sum += bq[q].z; bias_sum += bq[q].w; }
+        for (int x4 = BQ; x4 < W4; ++x4) {
+            const float4 v = brow[x4];
+            bias_sum += v.x; bias_sum += v.y; bias_sum += v.z; bias_sum += v.w;
+        }
+        a.gslab[slab_off + CC + bias_c] = slab_b_old + bias_sum;
+    }
+}
+
+template <bool LDSW, int NCB>
+__global__ __launch_bounds__(MIXT) void fno_mix_bwd_skipgrad_kernel(MixSkipDev f) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int block = __builtin_amdgcn_readfirstlane(blockIdx.x);
+    if (block < f.s.nmodes) mix_bwd_body<LDSW, true>(f.m, block, f.s.nmodes);
+    else skipgrad_rows<NCB>(f.s, smem, block - f.s.nmodes);
 }
 
 // ---- wide layers (and 3-D plans): the per-mode stage as TWO launches, so that the weight stream can be split over the chip.
@@ -1174,7 +1333,7 @@ int dlwp_fno_rows_dft(const dlwp_fno_plan* p, const float* x, int act_in, int ad
     return DLWP_OK;
 }
 
-static int mix_launch(const dlwp_fno_plan* p, bool bwd, MixDev& a, hipStream_t stream) {
+static size_t mix_lds_bytes(const MixDev& a, bool bwd, bool ldsw) {
     const int BC = a.B * a.C;
     int ns = MIXT / BC;
     if (ns < 1) ns = 1;
@@ -1182,8 +1341,12 @@ static int mix_launch(const dlwp_fno_plan* p, bool bwd, MixDev& a, hipStream_t s
     if (ns > lim) ns = lim;
     const int ns2 = mix_slots2(a.B, a.C, a.H);
     if (ns2 > ns) ns = ns2;
+    return sizeof(float2) * ((size_t)BC * ((bwd ? 2 : 1) + ns) + a.H + (ldsw ? (size_t)a.C * (a.C + 1) : 0));
+}
+
+static int mix_launch(const dlwp_fno_plan* p, bool bwd, MixDev& a, hipStream_t stream) {
     const bool ldsw = a.C <= 64;                    // the [C][C+1] complex weight image fits beside the H-step partials
-    const size_t lds = sizeof(float2) * ((size_t)BC * ((bwd ? 2 : 1) + ns) + a.H + (ldsw ? (size_t)a.C * (a.C + 1) : 0));
+    const size_t lds = mix_lds_bytes(a, bwd, ldsw);
     const dim3 grid(p->m1 * p->m2c), block(MIXT);
     int rc;
 #define MIX_LAUNCH(KERNEL, NAME)                                                    \
@@ -1259,6 +1422,48 @@ int dlwp_fno_mix_bwd(const dlwp_fno_plan* p, const float2* g1, const float2* wsp
     MixDev a{g1, wspec, xhat, nullptr, gxhat, g_wspec, p->twH, B, p->C, p->H, p->m1, p->m2c,
              make_fastdiv(p->C), make_fastdiv(B * p->C), make_fastdiv(B * p->C / 2 > 0 ? B * p->C / 2 : 1)};
     return mix_launch(p, true, a, stream);
+}
+
+static void spatial_lds_bytes(const dlwp_fno_plan* p, size_t& lds, size_t& lds_roles);
+
+// dlwp_fno_mix_bwd whose launch also forms the by-products of the block's backward `spatial` (fno_mix_bwd_skipgrad_kernel): the
+// gK partial and bias gradient of every image row from tin (g_pre of the block) and pprev (its stored input, GELU applied when
+// act_prev) into gslab, as the two-role `spatial` launch would.  The caller then runs `spatial` with neither gslab nor g_wskip /
+// g_bias.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) for wide and 3-D plans, for shapes whose plain
+// dispatch does not take the two-role kernel (they keep the four-wave kernel with its by-products), and with the knob
+// FNO_SKIP_WGRAD_IN_MIX = 0.
+int dlwp_fno_mix_bwd_skipgrad(const dlwp_fno_plan* p, const float2* g1, const float2* wspec, const float2* xhat, float2* gxhat,
+                              float2* g_wspec, const float* tin, const float* pprev, int act_prev, float* gslab,
+                              int gslab_accumulate, int B, hipStream_t stream) {
+    if (dlwp_fno_is_wide(p) || !tin || !pprev || !gslab || dlwp_tune_or("FNO_SKIP_WGRAD_IN_MIX", 1) == 0) return DLWP_E_UNSUPPORTED;
+    size_t lds_chain, lds_roles;
+    spatial_lds_bytes(p, lds_chain, lds_roles);
+    const int ncb = p->C_pad / 16;
+    if (lds_roles > (size_t)160 * 1024 || ncb < 1 || ncb > 4 || p->W % 16 != 0) return DLWP_E_UNSUPPORTED;
+    MixSkipDev f{};
+    f.m = MixDev{g1, wspec, xhat, nullptr, gxhat, g_wspec, p->twH, B, p->C, p->H, p->m1, p->m2c,
+                 make_fastdiv(p->C), make_fastdiv(B * p->C), make_fastdiv(B * p->C / 2 > 0 ? B * p->C / 2 : 1)};
+    f.s = SkipGradDev{tin, pprev, gslab, gslab_accumulate, act_prev, p->C, p->H, p->W, p->C_pad, p->m1 * p->m2c, B * p->H,
+                      make_fastdiv(p->C)};
+    const size_t lds_mix = mix_lds_bytes(f.m, true, true), lds_rows = sizeof(float) * (size_t)2 * 4 * p->C_pad * p->C_pad;
+    const size_t lds = lds_mix > lds_rows ? lds_mix : lds_rows;
+    const dim3 grid(p->m1 * p->m2c + (B * p->H + 1) / 2), block(MIXT);
+    const double pix = (double)B * p->H * p->W;
+    dlwp_prof_scope prof(stream, 2.0 * pix * p->C * p->C + 8.0 * B * p->C * p->C * 2.0 * p->m1 * p->m2c,
+                         8.0 * pix * p->C + 16.0 * p->m1 * p->m2c * p->C * p->C, "fno_mix_bwd_skipgrad_kernel<true, %d>", ncb);
+    int rc;
+#define LAUNCH(N)                                                                                                     \
+    if ((rc = set_lds(fno_mix_bwd_skipgrad_kernel<true, N>, lds, "fno_mix_bwd_skipgrad")) != DLWP_OK) return rc;      \
+    hipLaunchKernelGGL((fno_mix_bwd_skipgrad_kernel<true, N>), grid, block, lds, stream, f);
+    switch (ncb) {
+        case 1: LAUNCH(1) break;
+        case 2: LAUNCH(2) break;
+        case 3: LAUNCH(3) break;
+        default: LAUNCH(4) break;
+    }
+#undef LAUNCH
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
 }
 
 // the device argument block of a `spatial` launch, and the LDS bytes of its two layouts (four-wave / two-role)
@@ -1392,6 +1597,34 @@ extern "C" int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* p, const float* x, i
     return dlwp_fno_spatial(p, &s, stream);
 }
 
+// dlwp_fno_block_bwd_slab as the rollout trainer runs a block with FNO_SKIP_WGRAD_IN_MIX on: rows DFT, the per-mode launch that
+// also forms the slab (dlwp_fno_mix_bwd_skipgrad), then the four-wave `spatial` chain without by-products.  Every output bit for
+// bit dlwp_fno_block_bwd_slab's.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where dlwp_fno_mix_bwd_skipgrad
+// refuses.
+extern "C" int dlwp_fno_block_bwd_slab_split(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                             const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                                             float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
+                                             void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && slab && workspace && B > 0,
+                 DLWP_E_INVALID, "fno_block_bwd_slab_split: NULL argument or B<=0");
+    size_t lds_chain, lds_roles;
+    spatial_lds_bytes(p, lds_chain, lds_roles);
+    if (dlwp_fno_is_wide(p) || lds_roles > (size_t)160 * 1024 || dlwp_tune_or("FNO_SKIP_WGRAD_IN_MIX", 1) == 0)
+        return DLWP_E_UNSUPPORTED;       // in front of the rows DFT: nothing is launched
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    float2* g1 = static_cast<float2*>(workspace);
+    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
+    int rc;
+    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
+    if ((rc = dlwp_fno_mix_bwd_skipgrad(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat), gxhat,
+                                        reinterpret_cast<float2*>(g_wspec), g_pre, x, act_in, slab, slab_accumulate, B, stream)))
+        return rc;
+    dlwp_fno_spatial_args s{};
+    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
+    s.out = g_x; s.inverse_adjoint = 1; s.B = B;
+    return dlwp_fno_spatial(p, &s, stream);
+}
+
 // ---- block 0's backward `spatial` + the lifting MLP's backward in one launch (fno_spatial_lift_bwd_kernel).
 // LDS bytes of that launch, or 0 where the shapes take the two launches: 64-wide rows (a `spatial` row is a pwmlp pixel tile),
 // a narrow 2-D plan whose two-role layout fits (C_pad <= 48), and the lifting phase's tiles -- behind tout_s, over the regions
@@ -1410,14 +1643,19 @@ static size_t lift_bwd_fused_lds(const dlwp_fno_plan* p, int Cin) {
 // `s`: the backward `spatial` arguments of block 0 (no activation in front of it, slab form, neither `out` nor a fused row DFT);
 // x / gx / w1 / b1 / w2 / slab: the lifting backward's, as for dlwp_pwmlp_bwd_ex with gy = the gradient `spatial` would have
 // written.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where the shapes or FNO_FUSE_LIFT_BWD = 0 ask for the
-// two launches: the caller issues them instead.
+// two launches: the caller issues them instead.  s->gslab == NULL: the by-products of block 0 were formed by the per-mode launch
+// (dlwp_fno_mix_bwd_skipgrad), and phase 1 runs the chain alone.
+bool dlwp_fno_spatial_lift_bwd_fuses(const dlwp_fno_plan* p, int Cin, int Ch) {
+    return lift_bwd_fused_lds(p, Cin) != 0 && Ch >= 1 && dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) != 0;
+}
 int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
                               const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
                               int slab_accumulate, int Cin, int Ch, hipStream_t stream) {
     const size_t lds = lift_bwd_fused_lds(p, Cin);
-    if (!lds || !s->inverse_adjoint || s->act_prev || s->act_tin || s->out || s->x1_out || !s->gslab || !slab || Ch < 1 ||
-        dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) == 0)
+    if (!dlwp_fno_spatial_lift_bwd_fuses(p, Cin, Ch) || !s->inverse_adjoint || s->act_prev || s->act_tin || s->out || s->x1_out ||
+        s->g_wskip || s->g_bias || !slab)
         return DLWP_E_UNSUPPORTED;
+    const bool role_b = s->gslab != nullptr;
     SpatialLiftDev f{};
     f.s = make_spatial_dev(p, s);
     BwdArgs& a = f.m;
@@ -1435,11 +1673,17 @@ int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_arg
     const dim3 grid(s->B * p->H);
     const double pix = (double)s->B * a.P;
     dlwp_prof_scope prof(stream, 2.0 * pix * (p->C * (2.0 * p->C + 2 * p->m2c) + Ch * (3.0 * Cin + 2.0 * p->C)),
-                         4.0 * pix * (2.0 * p->C + 2.0 * Cin), "fno_spatial_lift_bwd_kernel<%d, %d, %d>", ncb, nbn, nib);
+                         4.0 * pix * (2.0 * p->C + 2.0 * Cin),
+                         "fno_spatial_lift_bwd_kernel<%d, %d, %d>", ncb, nbn, nib);   // one accounting row for both forms of phase 1
     int rc;
-#define LAUNCH(N, M, I)                                                                                       \
-    if ((rc = set_lds(fno_spatial_lift_bwd_kernel<N, M, I>, lds, "fno_spatial_lift_bwd")) != DLWP_OK) return rc; \
-    hipLaunchKernelGGL((fno_spatial_lift_bwd_kernel<N, M, I>), grid, dim3(512), lds, stream, f);
+#define LAUNCH(N, M, I)                                                                                                 \
+    if (role_b) {                                                                                                       \
+        if ((rc = set_lds(fno_spatial_lift_bwd_kernel<N, M, I>, lds, "fno_spatial_lift_bwd")) != DLWP_OK) return rc;    \
+        hipLaunchKernelGGL((fno_spatial_lift_bwd_kernel<N, M, I>), grid, dim3(512), lds, stream, f);                    \
+    } else {                                                                                                            \
+        if ((rc = set_lds(fno_spatial_lift_bwd_kernel<N, M, I, false>, lds, "fno_spatial_lift_bwd")) != DLWP_OK) return rc; \
+        hipLaunchKernelGGL((fno_spatial_lift_bwd_kernel<N, M, I, false>), grid, dim3(512), lds, stream, f);             \
+    }
 #define ROW(N, M)                                      \
     if (nib == 1) { LAUNCH(N, M, 1) } else { LAUNCH(N, M, 2) }
     switch (ncb * 10 + nbn) {           // lift_bwd_fused_lds() has refused everything else

@@ -1,7 +1,10 @@
 // Head of the two-role backward `spatial` workgroup, up to and including its second barrier (tout_s complete, role B finished):
 // the text of fno_spatial_roles_kernel<NCB, NBN, MODE> and the first phase of fno_spatial_lift_bwd_kernel (both fno_block.hip).
-// Included as text.  Expects in scope: `a` (SpatialDev), `smem`, and the constants NCB, NBN, MODE.
+// Included as text.  Expects in scope: `a` (SpatialDev), `smem`, and the constants NCB, NBN, MODE, ROLE_B.  ROLE_B == false: the
+// by-products were formed elsewhere (fno_mix_bwd_skipgrad_kernel); waves 4-7 touch neither `pprev` nor the slab and only arrive
+// at the barriers.
     constexpr int NTA = SPATIAL_NT;               // threads of role A (and of role B)
+    constexpr bool need_prev = ROLE_B || MODE == 1;   // pprev feeds role B and the GELU' epilogue only
     const SpatialLds L = carve_spatial_lds<true>(smem, a);
     const int tid = threadIdx.x, lane = lane_id();
     const int w = __builtin_amdgcn_readfirstlane(wave_id());   // wave-uniform: the role branches are scalar branches
@@ -24,8 +27,8 @@
     constexpr int BQ = 16;                        // ... its row pieces read ahead (a whole row at W = 64)
     const bool bias_on = !role_a && (a.g_bias || a.gslab) && lane < 16 && bias_c < a.C;
     if (role_a) {
-        spatial_issue<MODE>(a, b, h, true, R);
-    } else {
+        spatial_issue<MODE>(a, b, h, need_prev, R);
+    } else if constexpr (ROLE_B) {
         if (slab_acc) {
 #pragma unroll
             for (int k = 0; k < SLQ; ++k) slab_old[k] = a.gslab[slab_off + min(tb + NTA * k, a.C * a.C - 1)];
@@ -77,7 +80,7 @@
     DLWP_STAMP(1);
 
     if (role_a) {
-        spatial_commit<MODE>(a, L, b, h, true, R);
+        spatial_commit<MODE>(a, L, b, h, need_prev, R);
         DLWP_STAMP(3);
         spatial_hstep(a, L, b, h, R);
         DLWP_STAMP(4);
@@ -88,7 +91,7 @@
     if (role_a) {
         spatial_gemm<NCB, NBN, MODE>(a, L, w);
         DLWP_STAMP(6);
-    } else {
+    } else if constexpr (ROLE_B) {
         // cross-wave sum of the gK partials (w2 = 0 .. 3 from 0.f), then old + v into the slab, or the atomics.  The first SLQ
         // elements of a thread: all LDS reads first, then the sums (a read-then-use loop pays the LDS latency per element)
         // Bias gradient: channel 4 lane + w2 on lanes 0-15 of every wave, its row of tin_s as 16-byte reads (the first BQ issued

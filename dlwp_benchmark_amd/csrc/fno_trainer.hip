@@ -351,8 +351,6 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
         dlwp_chan_dst gxd{nullptr, 0, 0, tr->gdst_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
         bool lift_done = false;
         for (int l = NL - 1; l >= 0; --l) {
-            if ((rc = dlwp_fno_mix_bwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)),
-                                       xhat + l * xhatB, tr->spec, reinterpret_cast<float2*>(g.spec(l)), c.B, s))) return rc;
             dlwp_fno_spatial_args a{};
             a.tin = gcur; a.spec = tr->spec; a.wskip = w.skip(l); a.transpose_w = 1;
             a.pprev = l == 0 ? h0 : pre + (l - 1) * actB;
@@ -364,6 +362,19 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
             a.gslab_accumulate = k != tr->ncalls - 1;
             a.inverse_adjoint = 1;
             a.B = c.B;
+            // The skip-weight / bias gradient partials of the block need only gcur and pprev, which are complete here: where the
+            // shapes allow, extra workgroups of the per-mode launch (most CUs idle through it) form them into the slab and the
+            // `spatial` launch behind it runs its chain alone.  Block 0 takes this form together with its fused launch; where
+            // that one is refused it keeps the two-role `spatial` launch.
+            rc = (l > 0 || dlwp_fno_spatial_lift_bwd_fuses(tr->plan, tr->Cin, c.lifting))
+                     ? dlwp_fno_mix_bwd_skipgrad(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)), xhat + l * xhatB,
+                                                 tr->spec, reinterpret_cast<float2*>(g.spec(l)), a.tin, a.pprev, a.act_prev, a.gslab,
+                                                 a.gslab_accumulate, c.B, s)
+                     : DLWP_E_UNSUPPORTED;
+            if (rc == DLWP_OK) a.gslab = nullptr;
+            else if (rc != DLWP_E_UNSUPPORTED) return rc;
+            else if ((rc = dlwp_fno_mix_bwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)), xhat + l * xhatB, tr->spec,
+                                            reinterpret_cast<float2*>(g.spec(l)), c.B, s))) return rc;
             if (l == 0) {
                 // block 0's `spatial` and the lifting backward as one launch where the shapes allow: the gradient of h0 stays in
                 // LDS (gnext is not written); otherwise the two launches below

@@ -77,6 +77,7 @@ Knob g_knobs[] = {
     {"DIAG_PATH", "dlwp_rollout_diag on HPX planes: 0 by plane size (default), 1 the LDS-staged kernel (refused when two planes do not fit), 2 the direct kernel", 0, false},
     {"FNO_FUSE_LIFT_BWD", "0: block 0's backward `spatial` and the lifting backward of the FNO rollout stay two launches (default 1: one launch, fno_spatial_lift_bwd_kernel, where the shapes allow)", 0, false},
     {"FNO_FUSE_PROJ_FWD", "0: the last block's forward `spatial` and the projection (+ next lifting) MLP of the FNO training rollout stay two launches (default 1: one launch, fno_spatial_proj_fwd_kernel, where the shapes allow)", 0, false},
+    {"FNO_SKIP_WGRAD_IN_MIX", "0: the backward `spatial` launches of the FNO rollout form their skip-weight / bias gradients themselves (default 1: extra workgroups of the per-mode backward launch form them, fno_mix_bwd_skipgrad_kernel, and `spatial` runs its chain alone, where the shapes allow)", 0, false},
     {"CHAIN_ROT", "0: no rotation of the wave -> feature-tile assignment in the one-launch MLP chains (default 1)", 0, false},
 };
 constexpr int NKNOBS = sizeof(g_knobs) / sizeof(g_knobs[0]);

@@ -74,6 +74,7 @@ SIGNATURES = {
     "dlwp_fno_block_bwd": (_I, [_V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _V, _I, _V, _V]),
     "dlwp_fno_block_slab_floats": (C.c_longlong, [_V, _I]),
     "dlwp_fno_block_bwd_slab": (_I, [_V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _I, _I, _V, _V]),
+    "dlwp_fno_block_bwd_slab_split": (_I, [_V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _I, _I, _V, _V]),
     "dlwp_fno_block_slab_fold": (_I, [_V, _V, _V, _V, _I, _V]),
     "dlwp_fno_block_proj_fwd": (_I, [_V, _V, _I] + [_V] * 11 + [_I, _I] + [_V] * 7 + [_I, _I, C.c_char_p, _I, _V, _V]),
     "dlwp_pwmlp_proj_lift_fwd": (_I, [_V] * 8 + [_I, _I] + [_V] * 7 + [_I, _I, C.c_char_p, _I, _V]),

@@ -147,6 +147,14 @@ int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* plan, const float* x, int act_i
                             void* stream);
 int dlwp_fno_block_slab_fold(const dlwp_fno_plan* plan, const float* slab, float* g_wskip, float* g_bias,
                              int B, void* stream);
+/* dlwp_fno_block_bwd_slab as the rollout trainer runs a block by default: the slab is formed by extra workgroups of the     */
+/* per-mode launch (fno_mix_bwd_skipgrad_kernel) and the `spatial` launch behind it runs without by-products.  Every output   */
+/* bit for bit dlwp_fno_block_bwd_slab's.  DLWP_E_UNSUPPORTED, nothing launched, for wide / 3-D plans, for shapes whose        */
+/* backward `spatial` keeps its four-wave kernel (C_pad 64 on 64-wide rows), or with the knob FNO_SKIP_WGRAD_IN_MIX = 0.      */
+int dlwp_fno_block_bwd_slab_split(const dlwp_fno_plan* plan, const float* x, int act_in, const float* wspec,
+                                  const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                                  float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
+                                  void* stream);
 /* The backward of the FIRST block (its input h0 = the lifting MLP's output, not activated) fused with the lifting MLP's      */
 /* backward: rows DFT, per-mode stage, then ONE launch for `spatial` + the MLP backward -- the gradient of h0 stays in LDS and  */
 /* is never written.  Outputs bit for bit those of dlwp_fno_block_bwd_slab(act_in = 0) followed by dlwp_pwmlp_bwd_slab on its   */
