@@ -68,7 +68,8 @@ int dlwp_pwmlp_slab_count(int B, int P);
 int dlwp_pwmlp_slab_reduce(const float* slab, int nslab, int Cin, int Ch, int Cout, float* gw1, float* gb1,
                            float* gw2, float* gb2, hipStream_t stream);
 
-// fno_block.hip — the three stages of a block, exposed so the trainer can interleave them
+// fno_block.hip — the three stages of a block (the trainer runs the rows DFT itself where no MLP epilogue has formed it; the
+// other two are sequenced by dlwp_fno_block_fwd_run / dlwp_fno_block_bwd_run below)
 struct dlwp_fno_plan {
     int C, H, W, m1, m2c;
     int C_pad, NP;            // channels padded to 16; 2*m2c padded to 16
@@ -91,14 +92,6 @@ int dlwp_fno_mix_fwd(const dlwp_fno_plan* p, const float2* x1, const float2* wsp
 // backward: ghat = H-step of g1; gx[b][j][kx][i] = sum_o ghat conj(w); gw += conj(xhat) ghat
 int dlwp_fno_mix_bwd(const dlwp_fno_plan* p, const float2* g1, const float2* wspec,
                      const float2* xhat, float2* gxhat, float2* g_wspec, int B, hipStream_t stream);
-// the same launch also forming the by-products of the block's backward `spatial` (narrow 2-D plans): the skip-weight / bias
-// gradient partial of every image row from tin (g_pre of the block) and pprev (the block's stored input; GELU applied when
-// act_prev) into gslab, bit for bit what the two-role `spatial` launch writes; the caller then runs `spatial` with neither gslab nor
-// g_wskip / g_bias.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) for wide and 3-D plans, for shapes whose
-// backward `spatial` does not take the two-role kernel, and with the knob FNO_SKIP_WGRAD_IN_MIX = 0.
-int dlwp_fno_mix_bwd_skipgrad(const dlwp_fno_plan* p, const float2* g1, const float2* wspec, const float2* xhat, float2* gxhat,
-                              float2* g_wspec, const float* tin, const float* pprev, int act_prev, float* gslab,
-                              int gslab_accumulate, int B, hipStream_t stream);
 // spatial stage (one workgroup per image row, all channels).
 struct dlwp_fno_spatial_args {
     const float* tin;        // [B,C,H,W] GEMM input (fwd: x, bwd: g_pre)
@@ -122,27 +115,91 @@ struct dlwp_fno_spatial_args {
 };
 int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* a, hipStream_t stream);
 long long dlwp_fno_gslab_stride(int C);
-// block 0's backward `spatial` (s: slab form, no activation in front, out == x1_out == NULL) and the lifting MLP's backward
-// (dlwp_pwmlp_bwd_ex's x / w1 / b1 / w2 / gx / slab, gy = the gradient `spatial` would have written) as one launch; every output
-// bit for bit the two launches'.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where the shapes need the two
-// launches -- other than 64-wide rows, wide or 3-D plans, C_pad 64, Cin > 32 -- or the knob FNO_FUSE_LIFT_BWD is 0.
-// s->gslab == NULL: the by-products were formed by dlwp_fno_mix_bwd_skipgrad and the `spatial` phase runs its chain alone.
-// dlwp_fno_spatial_lift_bwd_fuses: whether shapes and knob allow the one launch (what the call decides on besides `s`).
-bool dlwp_fno_spatial_lift_bwd_fuses(const dlwp_fno_plan* p, int Cin, int Ch);
-int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
-                              const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
-                              int slab_accumulate, int Cin, int Ch, hipStream_t stream);
-// the last block's forward `spatial` (s: forward form, out = pre of that block, x1_out == NULL) and the projection MLP on its
-// result (pw1 .. pb2, y1, optional residual res1; dlwp_pwmlp_fwd_ex's arguments with x = s->out) as one launch; with x2v != NULL
-// also the next net call's lifting MLP and its rows DFT into x1_out, as dlwp_pwmlp_fwd_chain_ex chains them (Cout2 = plan->C).
-// Every output, `pre` included, bit for bit the two launches'.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched)
-// where the shapes need the two launches -- other than 64-wide rows, wide or 3-D plans, C_pad 64 (with the lifting MLP: C_pad 48,
-// NP 32), Cout1 > 8, whatever dlwp_pwmlp_fwd_chain_ex refuses, more than 160 KiB of LDS -- or the knob FNO_FUSE_PROJ_FWD is 0.
-int dlwp_fno_spatial_proj_fwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const float* pw1, const float* pb1,
-                              const float* pw2, const float* pb2, const dlwp_chan_dst* y1, const dlwp_chan_src* res1, int Ch1,
-                              int Cout1, const dlwp_chan_src* x2v, const float* lw1, const float* lb1, const float* lw2,
-                              const float* lb2, const dlwp_chan_dst* y2, int Cin2, int Ch2, const signed char* next_ch,
-                              float2* x1_out, hipStream_t stream);
+
+// ---- one block, sequenced: per-mode launch, then `spatial`, in the forms one decision function per direction picks.
+// Refusal protocol: the decision is taken in front of every launch, from the plan, the argument struct and the knobs FNO_SKIP_WGRAD_IN_MIX,
+// FNO_FUSE_LIFT_BWD and FNO_FUSE_PROJ_FWD (each read once per call).  With route AUTO a form the shapes or knobs do not take is
+// simply not chosen and the call runs the launches that remain.  A forced route that is not available gives DLWP_E_UNSUPPORTED
+// with the error string untouched and nothing launched.  The one refusal that shows later -- the projection chain's, while its
+// arguments are built -- is still in front of every launch: AUTO falls back to the separate launches, a forced route returns it.
+enum dlwp_fno_route {
+    DLWP_FNO_ROUTE_AUTO = 0,      // as the decision function says
+    DLWP_FNO_ROUTE_PLAIN,         // per-mode launch alone, then `spatial` alone (bwd: it forms the skip gradients); any tail separate
+    DLWP_FNO_ROUTE_HOSTED,        // bwd: the per-mode launch hosts the skip-gradient workgroups, `spatial` runs its chain alone
+    DLWP_FNO_ROUTE_FUSED_TAIL     // `spatial` and the tail in one launch; bwd: the per-mode form as AUTO would pick it beside that
+};
+enum dlwp_fno_spatial_form {
+    DLWP_FNO_SPATIAL_FOUR_WAVE,   // fno_spatial_kernel (wide plans: the channel-blocked launches of fno_wide.hip)
+    DLWP_FNO_SPATIAL_TWO_ROLE,    // bwd: fno_spatial_roles_kernel, the skip gradients on waves of their own
+    DLWP_FNO_SPATIAL_FUSED_TAIL   // bwd: fno_spatial_lift_bwd_kernel; fwd: fno_spatial_proj_fwd_kernel
+};
+struct dlwp_fno_forms {
+    int rc;                       // DLWP_OK, or DLWP_E_UNSUPPORTED: the forced route is not available
+    bool hosted;                  // bwd: fno_mix_bwd_skipgrad_kernel instead of fno_mix_bwd_kernel
+    int spatial;                  // dlwp_fno_spatial_form
+};
+// the lifting MLP's backward behind block 0: dlwp_pwmlp_bwd_ex's operands with gy = the block's g_x (which the fused launch
+// keeps in LDS and does not write); gw1 .. gb2 are read by the separate launch only
+struct dlwp_fno_lift_bwd_tail {
+    const dlwp_chan_src* x;
+    const float *w1, *b1, *w2;
+    const dlwp_chan_dst* gx;      // nullable
+    int gx_accumulate;
+    float *gw1, *gb1, *gw2, *gb2;
+    float* slab;
+    int slab_accumulate, Cin, Ch;
+};
+// the projection MLP behind the last block (dlwp_pwmlp_fwd_ex's operands with x = the block's pre) and, with x2v != NULL, the next
+// net call's lifting MLP with its rows DFT chained behind it (dlwp_pwmlp_fwd_chain_ex's second half, Cout2 = plan->C)
+struct dlwp_fno_proj_fwd_tail {
+    const float *pw1, *pb1, *pw2, *pb2;
+    const dlwp_chan_dst* y1;
+    const dlwp_chan_src* res1;    // nullable
+    int Ch1, Cout1;
+    const dlwp_chan_src* x2v;
+    const float *lw1, *lb1, *lw2, *lb2;
+    const dlwp_chan_dst* y2;
+    int Cin2, Ch2;
+    const signed char* next_ch;
+    float2* x1_next;
+    int* lifted;                  // out, nullable: the next lifting MLP ran with this call (fused or chained)
+};
+struct dlwp_fno_block_fwd_args {
+    const float* x;               // [B,C,H,W] block input; GELU applied on load when act_in
+    int act_in;
+    const float2* wspec;
+    const float *wskip, *bias;
+    float* pre;                   // [B,C,H,W]
+    float2* xhat;                 // [B][m1][m2c][C], kept for the backward
+    float2 *x1, *spec;            // work: x1 holds the rows DFT of act(x) on entry (rows_dft: the routine forms it first)
+    int rows_dft;
+    float2* x1_out;               // optional: rows DFT of gelu(pre) for the next block
+    const dlwp_fno_proj_fwd_tail* proj;   // last block: the projection runs with this call, fused or as separate launches
+    int keep;                     // training path: only there the fused projection launch is tried
+    int route, B;
+};
+struct dlwp_fno_block_bwd_args {
+    const float* g_pre;           // [B,C,H,W]
+    const float* x;               // the block's stored input (pre-activation when act_in)
+    int act_in, first;            // first: block 0 of the net
+    const float2* wspec;
+    const float* wskip;
+    const float2* xhat;
+    float* g_x;                   // [B,C,H,W] (not written when the lifting backward is fused)
+    float2* g_wspec;              // +=
+    float *g_wskip, *g_bias;      // skip gradients, direct (+=) ...
+    float* gslab;                 // ... or as per-row partials [B*H][dlwp_fno_gslab_stride]
+    int gslab_accumulate;
+    float2 *x1, *spec;            // work: x1 holds the adjoint rows DFT of g_pre on entry (rows_dft: the routine forms it first)
+    int rows_dft;
+    float2* x1_out;               // optional: adjoint rows DFT of g_x for the next block down
+    const dlwp_fno_lift_bwd_tail* lift;   // block 0: the lifting backward runs with this call, fused or as a separate launch
+    int route, B;
+};
+dlwp_fno_forms dlwp_fno_fwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_fwd_args* a);
+dlwp_fno_forms dlwp_fno_bwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args* a);
+int dlwp_fno_block_fwd_run(const dlwp_fno_plan* p, const dlwp_fno_block_fwd_args* a, hipStream_t stream);
+int dlwp_fno_block_bwd_run(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args* a, hipStream_t stream);
 // every partial slab of a training step folded by ONE launch (slab-parallel, coalesced):
 //   plain job  (pwmlp == 0): d1[i] += sum_s slab[s*stride + i] (i < n1), d2[i] += sum_s slab[s*stride + n1 + i] (i < n2)
 //   pwmlp job  (pwmlp != 0): the accumulator-tile slabs of dlwp_pwmlp_bwd_ex -> d1 = gw1, d2 = gb1, d3 = gw2, d4 = gb2

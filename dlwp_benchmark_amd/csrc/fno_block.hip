@@ -1300,10 +1300,18 @@ extern "C" void dlwp_fno_plan_destroy(dlwp_fno_plan* p) {
 static size_t x1_elems(const dlwp_fno_plan* p, int B) { return (size_t)B * p->H * p->m2c * p->C; }
 static size_t spec_elems(const dlwp_fno_plan* p, int B) { return (size_t)B * p->m1 * p->m2c * p->C; }
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+static size_t ws_x1_bytes(const dlwp_fno_plan* p, int B) { return align256(x1_elems(p, B) * sizeof(float2)); }
 
 extern "C" size_t dlwp_fno_block_workspace_bytes(const dlwp_fno_plan* p, int B) {
-    return align256(x1_elems(p, B) * sizeof(float2)) + align256(spec_elems(p, B) * sizeof(float2));
+    return ws_x1_bytes(p, B) + align256(spec_elems(p, B) * sizeof(float2));
 }
+// the two halves of a block workspace: the rows DFT (x1 / g1) and the per-mode stage's result (y / gxhat)
+struct BlockWs { float2 *x1, *spec; };
+static BlockWs carve_ws(const dlwp_fno_plan* p, int B, void* workspace) {
+    return BlockWs{static_cast<float2*>(workspace), reinterpret_cast<float2*>(static_cast<char*>(workspace) + ws_x1_bytes(p, B))};
+}
+
+constexpr size_t CU_LDS_BYTES = (size_t)160 * 1024;      // LDS of one gfx950 CU: the most a workgroup can ask for
 
 #define DISPATCH_NCB_NBN(NCBV, NBNV, MACRO)                      \
     switch ((NCBV) * 10 + (NBNV)) {                              \
@@ -1331,6 +1339,13 @@ int dlwp_fno_rows_dft(const dlwp_fno_plan* p, const float* x, int act_in, int ad
 #undef LAUNCH
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
+}
+
+// the argument block of a per-mode launch (forward: xhat_in == g_wspec == NULL; backward: xhat == NULL)
+static MixDev make_mix_dev(const dlwp_fno_plan* p, const float2* x1, const float2* wspec, const float2* xhat_in, float2* xhat,
+                           float2* y, float2* g_wspec, int B) {
+    return MixDev{x1, wspec, xhat_in, xhat, y, g_wspec, p->twH, B, p->C, p->H, p->m1, p->m2c,
+                  make_fastdiv(p->C), make_fastdiv(B * p->C), make_fastdiv(B * p->C / 2 > 0 ? B * p->C / 2 : 1)};
 }
 
 static size_t mix_lds_bytes(const MixDev& a, bool bwd, bool ldsw) {
@@ -1394,8 +1409,7 @@ int dlwp_fno_mix_fwd(const dlwp_fno_plan* p, const float2* x1, const float2* wsp
         DLWP_LAUNCH_CHECK();
         return DLWP_OK;
     }
-    MixDev a{x1, wspec, nullptr, xhat, y, nullptr, p->twH, B, p->C, p->H, p->m1, p->m2c,
-             make_fastdiv(p->C), make_fastdiv(B * p->C), make_fastdiv(B * p->C / 2 > 0 ? B * p->C / 2 : 1)};
+    MixDev a = make_mix_dev(p, x1, wspec, nullptr, xhat, y, nullptr, B);
     return mix_launch(p, false, a, stream);
 }
 
@@ -1419,30 +1433,20 @@ int dlwp_fno_mix_bwd(const dlwp_fno_plan* p, const float2* g1, const float2* wsp
         DLWP_LAUNCH_CHECK();
         return DLWP_OK;
     }
-    MixDev a{g1, wspec, xhat, nullptr, gxhat, g_wspec, p->twH, B, p->C, p->H, p->m1, p->m2c,
-             make_fastdiv(p->C), make_fastdiv(B * p->C), make_fastdiv(B * p->C / 2 > 0 ? B * p->C / 2 : 1)};
+    MixDev a = make_mix_dev(p, g1, wspec, xhat, nullptr, gxhat, g_wspec, B);
     return mix_launch(p, true, a, stream);
 }
-
-static void spatial_lds_bytes(const dlwp_fno_plan* p, size_t& lds, size_t& lds_roles);
 
 // dlwp_fno_mix_bwd whose launch also forms the by-products of the block's backward `spatial` (fno_mix_bwd_skipgrad_kernel): the
 // gK partial and bias gradient of every image row from tin (g_pre of the block) and pprev (its stored input, GELU applied when
 // act_prev) into gslab, as the two-role `spatial` launch would.  The caller then runs `spatial` with neither gslab nor g_wskip /
-// g_bias.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) for wide and 3-D plans, for shapes whose plain
-// dispatch does not take the two-role kernel (they keep the four-wave kernel with its by-products), and with the knob
-// FNO_SKIP_WGRAD_IN_MIX = 0.
-int dlwp_fno_mix_bwd_skipgrad(const dlwp_fno_plan* p, const float2* g1, const float2* wspec, const float2* xhat, float2* gxhat,
-                              float2* g_wspec, const float* tin, const float* pprev, int act_prev, float* gslab,
-                              int gslab_accumulate, int B, hipStream_t stream) {
-    if (dlwp_fno_is_wide(p) || !tin || !pprev || !gslab || dlwp_tune_or("FNO_SKIP_WGRAD_IN_MIX", 1) == 0) return DLWP_E_UNSUPPORTED;
-    size_t lds_chain, lds_roles;
-    spatial_lds_bytes(p, lds_chain, lds_roles);
+// g_bias.  Only where dlwp_fno_bwd_decide() says `hosted`: a narrow plan whose two-role layout fits.
+static int mix_bwd_skipgrad_launch(const dlwp_fno_plan* p, const float2* g1, const float2* wspec, const float2* xhat, float2* gxhat,
+                                   float2* g_wspec, const float* tin, const float* pprev, int act_prev, float* gslab,
+                                   int gslab_accumulate, int B, hipStream_t stream) {
     const int ncb = p->C_pad / 16;
-    if (lds_roles > (size_t)160 * 1024 || ncb < 1 || ncb > 4 || p->W % 16 != 0) return DLWP_E_UNSUPPORTED;
     MixSkipDev f{};
-    f.m = MixDev{g1, wspec, xhat, nullptr, gxhat, g_wspec, p->twH, B, p->C, p->H, p->m1, p->m2c,
-                 make_fastdiv(p->C), make_fastdiv(B * p->C), make_fastdiv(B * p->C / 2 > 0 ? B * p->C / 2 : 1)};
+    f.m = make_mix_dev(p, g1, wspec, xhat, nullptr, gxhat, g_wspec, B);
     f.s = SkipGradDev{tin, pprev, gslab, gslab_accumulate, act_prev, p->C, p->H, p->W, p->C_pad, p->m1 * p->m2c, B * p->H,
                       make_fastdiv(p->C)};
     const size_t lds_mix = mix_lds_bytes(f.m, true, true), lds_rows = sizeof(float) * (size_t)2 * 4 * p->C_pad * p->C_pad;
@@ -1491,6 +1495,14 @@ static void spatial_lds_bytes(const dlwp_fno_plan* p, size_t& lds, size_t& lds_r
     // two-role form of the backward kernel: gks next to gs / ks / s1 instead of over them
     lds_roles = sizeof(float) * (live + gemm_ops + gks);
 }
+// The two-role layout fits the LDS of a CU: on 64-wide rows C_pad 16 / 32 / 48 (65 KiB at C_pad 32), on 32-wide rows C_pad 64 too.
+// It does not fit for C_pad 64 on 64-wide rows (161.5 KiB: C 49 .. 64 at the published grid) nor for C_pad 32 on 256-wide rows
+// (161 KiB).
+static bool two_role_fits(const dlwp_fno_plan* p) {
+    size_t lds, lds_roles;
+    spatial_lds_bytes(p, lds, lds_roles);
+    return lds_roles <= CU_LDS_BYTES;
+}
 
 int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hipStream_t stream) {
     if (dlwp_fno_is_wide(p)) {
@@ -1511,10 +1523,8 @@ int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hip
     int rc;
     const int mode = !a.is_bwd ? 0 : (a.act_prev ? 1 : 2);
     // The by-products get waves of their own when the backward launch has a skip-weight gradient to form and the larger
-    // footprint fits the 160 KiB of a CU: on 64-wide rows C_pad 16 / 32 / 48 (65 KiB at C_pad 32), on 32-wide rows C_pad 64 too.
-    // It does not fit for C_pad 64 on 64-wide rows (161.5 KiB: C 49 .. 64 at the published grid) nor for C_pad 32 on 256-wide
-    // rows (161 KiB): those shapes keep the four-wave kernel, as does a backward launch without g_wskip / slab.
-    const bool roles = a.is_bwd && (a.g_wskip || a.gslab) && lds_roles <= (size_t)160 * 1024;
+    // footprint fits: other shapes keep the four-wave kernel, as does a backward launch without g_wskip / slab.
+    const bool roles = a.is_bwd && (a.g_wskip || a.gslab) && two_role_fits(p);
     const double pix = (double)s->B * p->H * p->W;
     dlwp_prof_scope prof(stream, 2.0 * pix * p->C * (p->C * (roles ? 2 : 1) + 2 * p->m2c), 4.0 * pix * p->C * (a.is_bwd ? 3 : 2),
                          roles ? "fno_spatial_roles_kernel<%d, %d, %d>" : "fno_spatial_kernel<%d, %d, %d>", p->C_pad / 16,
@@ -1538,97 +1548,14 @@ int dlwp_fno_spatial(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, hip
     return DLWP_OK;
 }
 
-extern "C" int dlwp_fno_block_fwd(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
-                                  const float* wskip, const float* bias, float* pre, float* xhat, int B,
-                                  void* workspace, void* stream_) {
-    DLWP_REQUIRE(p && x && wspec && wskip && pre && xhat && workspace && B > 0, DLWP_E_INVALID,
-                 "fno_block_fwd: NULL argument or B<=0");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float2* x1 = static_cast<float2*>(workspace);
-    float2* y = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
-    int rc;
-    if ((rc = dlwp_fno_rows_dft(p, x, act_in, 0, x1, B, stream))) return rc;
-    if ((rc = dlwp_fno_mix_fwd(p, x1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<float2*>(xhat), y, B, stream))) return rc;
-    dlwp_fno_spatial_args s{};
-    s.tin = x; s.act_tin = act_in; s.spec = y; s.wskip = wskip; s.bias = bias; s.out = pre; s.B = B;
-    return dlwp_fno_spatial(p, &s, stream);
-}
-
-extern "C" int dlwp_fno_block_bwd(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
-                                  const float* wskip, const float* g_pre, const float* xhat, float* g_x,
-                                  float* g_wspec, float* g_wskip, float* g_bias, int B, void* workspace,
-                                  void* stream_) {
-    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && workspace && B > 0,
-                 DLWP_E_INVALID, "fno_block_bwd: NULL argument or B<=0");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float2* g1 = static_cast<float2*>(workspace);
-    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
-    int rc;
-    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
-    if ((rc = dlwp_fno_mix_bwd(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat),
-                               gxhat, reinterpret_cast<float2*>(g_wspec), B, stream))) return rc;
-    dlwp_fno_spatial_args s{};
-    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
-    s.out = g_x; s.g_wskip = g_wskip; s.g_bias = g_bias; s.inverse_adjoint = 1; s.B = B;
-    return dlwp_fno_spatial(p, &s, stream);
-}
-
 extern "C" long long dlwp_fno_block_slab_floats(const dlwp_fno_plan* p, int B) {
     return p && B > 0 ? (long long)B * p->H * dlwp_fno_gslab_stride(p->C) : 0;
-}
-
-extern "C" int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
-                                       const float* wskip, const float* g_pre, const float* xhat, float* g_x,
-                                       float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
-                                       void* stream_) {
-    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && slab && workspace && B > 0,
-                 DLWP_E_INVALID, "fno_block_bwd_slab: NULL argument or B<=0");
-    DLWP_REQUIRE(!dlwp_fno_is_wide(p), DLWP_E_UNSUPPORTED, "fno_block_bwd_slab: narrow layers only (hidden_channels <= 64, 2-D plan)");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float2* g1 = static_cast<float2*>(workspace);
-    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
-    int rc;
-    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
-    if ((rc = dlwp_fno_mix_bwd(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat),
-                               gxhat, reinterpret_cast<float2*>(g_wspec), B, stream))) return rc;
-    dlwp_fno_spatial_args s{};
-    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
-    s.out = g_x; s.gslab = slab; s.gslab_accumulate = slab_accumulate; s.inverse_adjoint = 1; s.B = B;
-    return dlwp_fno_spatial(p, &s, stream);
-}
-
-// dlwp_fno_block_bwd_slab as the rollout trainer runs a block with FNO_SKIP_WGRAD_IN_MIX on: rows DFT, the per-mode launch that
-// also forms the slab (dlwp_fno_mix_bwd_skipgrad), then the four-wave `spatial` chain without by-products.  Every output bit for
-// bit dlwp_fno_block_bwd_slab's.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where dlwp_fno_mix_bwd_skipgrad
-// refuses.
-extern "C" int dlwp_fno_block_bwd_slab_split(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
-                                             const float* wskip, const float* g_pre, const float* xhat, float* g_x,
-                                             float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
-                                             void* stream_) {
-    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && slab && workspace && B > 0,
-                 DLWP_E_INVALID, "fno_block_bwd_slab_split: NULL argument or B<=0");
-    size_t lds_chain, lds_roles;
-    spatial_lds_bytes(p, lds_chain, lds_roles);
-    if (dlwp_fno_is_wide(p) || lds_roles > (size_t)160 * 1024 || dlwp_tune_or("FNO_SKIP_WGRAD_IN_MIX", 1) == 0)
-        return DLWP_E_UNSUPPORTED;       // in front of the rows DFT: nothing is launched
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float2* g1 = static_cast<float2*>(workspace);
-    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
-    int rc;
-    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
-    if ((rc = dlwp_fno_mix_bwd_skipgrad(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat), gxhat,
-                                        reinterpret_cast<float2*>(g_wspec), g_pre, x, act_in, slab, slab_accumulate, B, stream)))
-        return rc;
-    dlwp_fno_spatial_args s{};
-    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = x; s.act_prev = act_in;
-    s.out = g_x; s.inverse_adjoint = 1; s.B = B;
-    return dlwp_fno_spatial(p, &s, stream);
 }
 
 // ---- block 0's backward `spatial` + the lifting MLP's backward in one launch (fno_spatial_lift_bwd_kernel).
 // LDS bytes of that launch, or 0 where the shapes take the two launches: 64-wide rows (a `spatial` row is a pwmlp pixel tile),
 // a narrow 2-D plan whose two-role layout fits (C_pad <= 48), and the lifting phase's tiles -- behind tout_s, over the regions
-// the `spatial` phase no longer needs -- inside the 160 KiB of a CU.  Instantiated are the (C_pad / 16, Cin_pad / 16) pairs that
+// the `spatial` phase no longer needs -- inside the LDS of a CU.  Instantiated are the (C_pad / 16, Cin_pad / 16) pairs that
 // compile without scratch and without vector spills: (1, 1), (2, 1), (2, 2), (3, 1), (3, 2); like pwmlp_bwd_kernel's own, the
 // wider ones spill, and they keep the two launches.
 static size_t lift_bwd_fused_lds(const dlwp_fno_plan* p, int Cin) {
@@ -1637,36 +1564,29 @@ static size_t lift_bwd_fused_lds(const dlwp_fno_plan* p, int Cin) {
     spatial_lds_bytes(p, lds, lds_roles);
     const size_t phase2 = sizeof(float) * ((size_t)2 * p->C_pad * LDP + (size_t)(1 + BWD_WAVES) * round_up(Cin, 16) * LDP);
     const size_t need = lds_roles > phase2 ? lds_roles : phase2;
-    return lds_roles <= (size_t)160 * 1024 && need <= (size_t)160 * 1024 ? need : 0;
+    return need <= CU_LDS_BYTES ? need : 0;       // need >= lds_roles: the two-role layout fits too
 }
 
-// `s`: the backward `spatial` arguments of block 0 (no activation in front of it, slab form, neither `out` nor a fused row DFT);
-// x / gx / w1 / b1 / w2 / slab: the lifting backward's, as for dlwp_pwmlp_bwd_ex with gy = the gradient `spatial` would have
-// written.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) where the shapes or FNO_FUSE_LIFT_BWD = 0 ask for the
-// two launches: the caller issues them instead.  s->gslab == NULL: the by-products of block 0 were formed by the per-mode launch
-// (dlwp_fno_mix_bwd_skipgrad), and phase 1 runs the chain alone.
-bool dlwp_fno_spatial_lift_bwd_fuses(const dlwp_fno_plan* p, int Cin, int Ch) {
-    return lift_bwd_fused_lds(p, Cin) != 0 && Ch >= 1 && dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) != 0;
-}
-int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_chan_src* x, const float* w1,
-                              const float* b1, const float* w2, const dlwp_chan_dst* gx, int gx_accumulate, float* slab,
-                              int slab_accumulate, int Cin, int Ch, hipStream_t stream) {
+// `s`: the backward `spatial` arguments of block 0 (no activation in front of it, neither `out` nor a fused row DFT); t: the lifting
+// backward's operands, as for dlwp_pwmlp_bwd_ex with gy = the gradient `spatial` would have written.  Only where
+// dlwp_fno_bwd_decide() names the fused form.  s->gslab == NULL: the by-products of block 0 were formed by the per-mode launch
+// (mix_bwd_skipgrad_launch), and phase 1 runs the chain alone.
+static int spatial_lift_bwd_launch(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_fno_lift_bwd_tail* t,
+                                   hipStream_t stream) {
+    const int Cin = t->Cin, Ch = t->Ch;
     const size_t lds = lift_bwd_fused_lds(p, Cin);
-    if (!dlwp_fno_spatial_lift_bwd_fuses(p, Cin, Ch) || !s->inverse_adjoint || s->act_prev || s->act_tin || s->out || s->x1_out ||
-        s->g_wskip || s->g_bias || !slab)
-        return DLWP_E_UNSUPPORTED;
     const bool role_b = s->gslab != nullptr;
     SpatialLiftDev f{};
     f.s = make_spatial_dev(p, s);
     BwdArgs& a = f.m;
-    a.x = *x; a.w1 = w1; a.b1 = b1; a.w2 = w2;
-    if (gx) a.gx = *gx;
-    a.gx_accumulate = gx_accumulate;
+    a.x = *t->x; a.w1 = t->w1; a.b1 = t->b1; a.w2 = t->w2;
+    if (t->gx) a.gx = *t->gx;
+    a.gx_accumulate = t->gx_accumulate;
     a.B = s->B; a.Cin = Cin; a.Ch = Ch; a.Cout = p->C; a.P = p->H * p->W;
     a.tiles_per_sample = p->H;
     a.Cin_pad = round_up(Cin, 16); a.Ch_pad = round_up(Ch, 16); a.Cout_pad = p->C_pad;
-    a.slab = slab; a.slab_stride = dlwp_pwmlp_slab_stride(Cin, Ch, p->C); a.slab_accumulate = slab_accumulate;
-    a.vec_w = aligned16(w1);
+    a.slab = t->slab; a.slab_stride = dlwp_pwmlp_slab_stride(Cin, Ch, p->C); a.slab_accumulate = t->slab_accumulate;
+    a.vec_w = aligned16(t->w1);
     a.dCin = make_fastdiv(Cin); a.dCh = make_fastdiv(Ch);
     a.vec_x = view_vec_ok(a.x);
     const int ncb = p->C_pad / 16, nbn = p->NP / 16, nib = a.Cin_pad / 16;
@@ -1698,34 +1618,6 @@ int dlwp_fno_spatial_lift_bwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_arg
     return DLWP_OK;
 }
 
-extern "C" int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* p, const float* h0, const float* wspec, const float* wskip,
-                                            const float* g_pre, const float* xhat, float* g_wspec, float* slab_skip,
-                                            int slab_skip_accumulate, const float* x, const float* w1, const float* b1,
-                                            const float* w2, float* gx, int gx_accumulate, float* slab_lift,
-                                            int slab_lift_accumulate, int B, int Cin, int Ch, void* workspace, void* stream_) {
-    DLWP_REQUIRE(p && h0 && wspec && wskip && g_pre && xhat && g_wspec && slab_skip && x && w1 && b1 && w2 && slab_lift &&
-                     workspace && B > 0 && Cin > 0 && Ch > 0,
-                 DLWP_E_INVALID, "fno_block_lift_bwd_slab: NULL argument or non-positive dimension");
-    DLWP_REQUIRE(lift_bwd_fused_lds(p, Cin) != 0 && dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) != 0, DLWP_E_UNSUPPORTED,
-                 "fno_block_lift_bwd_slab: needs 64-wide rows, a narrow 2-D plan of at most 48 channels, Cin <= 32 and "
-                 "FNO_FUSE_LIFT_BWD != 0 (use dlwp_fno_block_bwd_slab + dlwp_pwmlp_bwd_slab)");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float2* g1 = static_cast<float2*>(workspace);
-    float2* gxhat = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
-    int rc;
-    if ((rc = dlwp_fno_rows_dft(p, g_pre, 0, 1, g1, B, stream))) return rc;
-    if ((rc = dlwp_fno_mix_bwd(p, g1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<const float2*>(xhat),
-                               gxhat, reinterpret_cast<float2*>(g_wspec), B, stream))) return rc;
-    dlwp_fno_spatial_args s{};
-    s.tin = g_pre; s.spec = gxhat; s.wskip = wskip; s.transpose_w = 1; s.pprev = h0;
-    s.gslab = slab_skip; s.gslab_accumulate = slab_skip_accumulate; s.inverse_adjoint = 1; s.B = B;
-    const long long P = (long long)p->H * p->W;
-    dlwp_chan_src xs{x, (long long)Cin * P, P, nullptr, nullptr};
-    dlwp_chan_dst gxd{gx, (long long)Cin * P, P, nullptr, nullptr};
-    return dlwp_fno_spatial_lift_bwd(p, &s, &xs, w1, b1, w2, gx ? &gxd : nullptr, gx_accumulate, slab_lift,
-                                     slab_lift_accumulate, Cin, Ch, stream);
-}
-
 // ---- the last block's forward `spatial` + the projection MLP (+ the next net call's lifting MLP) in one launch
 // (fno_spatial_proj_fwd_kernel).  Dispatched are the instantiations that compile for gfx950 without scratch and without vector
 // spills: C_pad 16 / 32 / 48 projection only, C_pad 16 / 32 with the chained lifting MLP (whose fused rows DFT needs NP == 16).
@@ -1735,28 +1627,23 @@ struct ProjFwdLaunch {
     int nob2;
     double flops, bytes;
 };
-// validates and fills the launch; DLWP_E_UNSUPPORTED (error string untouched) where the two launches have to stay
-static int proj_fwd_prepare(ProjFwdLaunch& q, const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const float* pw1,
-                            const float* pb1, const float* pw2, const float* pb2, const dlwp_chan_dst* y1,
-                            const dlwp_chan_src* res1, int Ch1, int Cout1, const dlwp_chan_src* x2v, const float* lw1,
-                            const float* lb1, const float* lw2, const float* lb2, const dlwp_chan_dst* y2, int Cin2, int Ch2,
-                            const signed char* next_ch, float2* x1_out) {
-    const bool second = x2v != nullptr;
-    if (dlwp_fno_is_wide(p) || p->W != PT || p->C_pad > 48 || (second && (p->C_pad > 32 || p->NP != 16 || !x1_out || !y2)) ||
-        s->inverse_adjoint || s->x1_out || !s->out || !y1 || Ch1 < 1 || Cout1 < 1 || Cout1 > 8 || (second && (Cin2 < 1 || Cin2 > 64 || Ch2 < 1)) ||
-        dlwp_tune_or("FNO_FUSE_PROJ_FWD", 1) == 0)
-        return DLWP_E_UNSUPPORTED;
+// fills the launch where dlwp_fno_fwd_decide() names the fused form.  What only shows while the projection chain's arguments are
+// built is refused here, still in front of every launch: DLWP_E_UNSUPPORTED from chain_make_args (vector access to the views, the
+// chained lifting's own limits) or for more LDS than a CU has.
+static int proj_fwd_prepare(ProjFwdLaunch& q, const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_fno_proj_fwd_tail* t) {
+    const bool second = t->x2v != nullptr;
+    const int Ch1 = t->Ch1, Cout1 = t->Cout1, Cin2 = t->Cin2, Ch2 = t->Ch2;
     const int HW = p->H * p->W;
     const dlwp_chan_src ps{s->out, (long long)p->C * HW, HW, nullptr, nullptr};     // what the projection would read back
     size_t lds_floats;
-    const int rc = chain_make_args(q.f.c, lds_floats, &ps, pw1, pb1, pw2, pb2, y1, res1, p->C, Ch1, Cout1, second, x2v, lw1, lb1, lw2,
-                                   lb2, y2, Cin2, Ch2, p->C, next_ch, s->B, HW, p, x1_out);
+    const int rc = chain_make_args(q.f.c, lds_floats, &ps, t->pw1, t->pb1, t->pw2, t->pb2, t->y1, t->res1, p->C, Ch1, Cout1, second,
+                                   t->x2v, t->lw1, t->lb1, t->lw2, t->lb2, t->y2, Cin2, Ch2, p->C, t->next_ch, s->B, HW, p, t->x1_next);
     if (rc) return rc;
     if (second && !q.f.c.l.x1_out) return DLWP_E_UNSUPPORTED;
     // the operands of the `spatial` GEMM behind the MLP images: tin_s, gs, ks, s1, bias_s
     lds_floats += (size_t)p->C_pad * LDP + (size_t)p->NP * LDP + (size_t)p->C_pad * (p->C_pad + 4) + (size_t)p->C_pad * (p->NP + 4) + p->C_pad;
     q.lds = sizeof(float) * lds_floats;
-    if (q.lds > (size_t)160 * 1024) return DLWP_E_UNSUPPORTED;
+    if (q.lds > CU_LDS_BYTES) return DLWP_E_UNSUPPORTED;
     q.f.s = make_spatial_dev(p, s);
     q.nob2 = second ? p->C_pad / 16 : 0;
     const double pix = (double)s->B * HW;
@@ -1787,19 +1674,204 @@ static int proj_fwd_launch(const ProjFwdLaunch& q, const dlwp_fno_plan* p, int B
     return DLWP_OK;
 }
 
-int dlwp_fno_spatial_proj_fwd(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const float* pw1, const float* pb1,
-                              const float* pw2, const float* pb2, const dlwp_chan_dst* y1, const dlwp_chan_src* res1, int Ch1,
-                              int Cout1, const dlwp_chan_src* x2v, const float* lw1, const float* lb1, const float* lw2,
-                              const float* lb2, const dlwp_chan_dst* y2, int Cin2, int Ch2, const signed char* next_ch,
-                              float2* x1_out, hipStream_t stream) {
-    ProjFwdLaunch q;
-    const int rc = proj_fwd_prepare(q, p, s, pw1, pb1, pw2, pb2, y1, res1, Ch1, Cout1, x2v, lw1, lb1, lw2, lb2, y2, Cin2, Ch2,
-                                    next_ch, x1_out);
-    return rc ? rc : proj_fwd_launch(q, p, s->B, stream);
+// ---- one block: which launch forms, and their sequence.  The only readers of the three FNO knobs.
+// (A narrow plan has 16 | W, one to four channel tiles and one or two frequency tiles -- plan_create_impl -- so every launcher
+// below has an instantiation for what these functions let through.)
+
+// Backward.  hosted: extra workgroups of the per-mode launch (most CUs idle through it) form the skip-weight / bias partials,
+// which need only g_pre and the block's input, into the slab, and `spatial` runs its chain alone -- wherever that `spatial` would
+// have taken the two-role kernel.  Block 0 takes this form only together with its fused lifting launch; where that one is
+// refused it keeps the two-role `spatial`.
+dlwp_fno_forms dlwp_fno_bwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args* a) {
+    const bool skip_in_mix = dlwp_tune_or("FNO_SKIP_WGRAD_IN_MIX", 1) != 0, fuse_lift = dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) != 0;
+    const bool slab = a->gslab != nullptr, fits = !dlwp_fno_is_wide(p) && two_role_fits(p);
+    const bool can_host = slab && fits && skip_in_mix;
+    const dlwp_fno_lift_bwd_tail* t = a->lift;
+    const bool can_lift = t && slab && !a->g_wskip && !a->g_bias && !a->act_in && !a->x1_out && t->slab && t->Ch >= 1 &&
+                          lift_bwd_fused_lds(p, t->Cin) != 0 && fuse_lift;
+    dlwp_fno_forms d{DLWP_OK, false, DLWP_FNO_SPATIAL_FOUR_WAVE};
+    bool lift = false;
+    switch (a->route) {
+        case DLWP_FNO_ROUTE_PLAIN: break;
+        case DLWP_FNO_ROUTE_HOSTED: d.hosted = true; if (!can_host) d.rc = DLWP_E_UNSUPPORTED; break;
+        case DLWP_FNO_ROUTE_FUSED_TAIL: lift = true; d.hosted = can_host; if (!can_lift) d.rc = DLWP_E_UNSUPPORTED; break;
+        default: lift = a->first && can_lift; d.hosted = can_host && (!a->first || lift); break;
+    }
+    if (lift) d.spatial = DLWP_FNO_SPATIAL_FUSED_TAIL;
+    else if (!d.hosted && (slab || a->g_wskip) && fits) d.spatial = DLWP_FNO_SPATIAL_TWO_ROLE;   // dlwp_fno_spatial's own choice
+    return d;
 }
 
-// Test entry points on contiguous tensors.  dlwp_fno_block_proj_fwd: one FNO block (rows DFT, per-mode stage) whose `spatial` stage
-// is the fused launch: pre, xhat as dlwp_fno_block_fwd; frame [B, Cout1, H, W] = projection(pre) (+ res); and, with window != NULL,
+// Forward.  The last block's `spatial`, the projection and, behind it, the next call's lifting MLP as one launch on the training
+// path (activations kept): the fused launch was built for and measured on the training step, and pwmlp_fwd_chain_kernel stays the
+// kernel an evaluation rollout is tested on.  Instantiated without scratch and vector spills are C_pad 16 / 32 / 48 with the
+// projection only, C_pad 16 / 32 with the chained lifting MLP (whose fused rows DFT needs NP == 16).
+dlwp_fno_forms dlwp_fno_fwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_fwd_args* a) {
+    const bool fuse_proj = dlwp_tune_or("FNO_FUSE_PROJ_FWD", 1) != 0;
+    const dlwp_fno_proj_fwd_tail* t = a->proj;
+    const bool second = t && t->x2v;
+    const bool can_fuse = t && a->keep && fuse_proj && !dlwp_fno_is_wide(p) && p->W == PT && p->C_pad <= 48 && !a->x1_out && t->y1 &&
+                          t->Ch1 >= 1 && t->Cout1 >= 1 && t->Cout1 <= 8 &&
+                          (!second || (p->C_pad <= 32 && p->NP == 16 && t->x1_next && t->y2 && t->Cin2 >= 1 && t->Cin2 <= 64 && t->Ch2 >= 1));
+    dlwp_fno_forms d{DLWP_OK, false, DLWP_FNO_SPATIAL_FOUR_WAVE};
+    const bool fused = a->route == DLWP_FNO_ROUTE_FUSED_TAIL || (a->route == DLWP_FNO_ROUTE_AUTO && can_fuse);
+    if (fused) d.spatial = DLWP_FNO_SPATIAL_FUSED_TAIL;
+    if (fused && !can_fuse) d.rc = DLWP_E_UNSUPPORTED;
+    return d;
+}
+
+int dlwp_fno_block_bwd_run(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args* a, hipStream_t stream) {
+    const dlwp_fno_forms d = dlwp_fno_bwd_decide(p, a);
+    if (d.rc) return d.rc;
+    const bool fused = d.spatial == DLWP_FNO_SPATIAL_FUSED_TAIL;
+    int rc;
+    if (a->rows_dft && (rc = dlwp_fno_rows_dft(p, a->g_pre, 0, 1, a->x1, a->B, stream))) return rc;
+    rc = d.hosted ? mix_bwd_skipgrad_launch(p, a->x1, a->wspec, a->xhat, a->spec, a->g_wspec, a->g_pre, a->x, a->act_in, a->gslab,
+                                            a->gslab_accumulate, a->B, stream)
+                  : dlwp_fno_mix_bwd(p, a->x1, a->wspec, a->xhat, a->spec, a->g_wspec, a->B, stream);
+    if (rc) return rc;
+    dlwp_fno_spatial_args s{};
+    s.tin = a->g_pre; s.spec = a->spec; s.wskip = a->wskip; s.transpose_w = 1; s.pprev = a->x; s.act_prev = a->act_in;
+    s.out = fused ? nullptr : a->g_x;            // fused: the gradient of the lifting output stays in LDS
+    s.x1_out = a->x1_out; s.x1_adjoint = 1; s.inverse_adjoint = 1; s.B = a->B;
+    s.gslab_accumulate = a->gslab_accumulate;
+    if (!d.hosted) { s.g_wskip = a->g_wskip; s.g_bias = a->g_bias; s.gslab = a->gslab; }
+    const dlwp_fno_lift_bwd_tail* t = a->lift;
+    if (fused) return spatial_lift_bwd_launch(p, &s, t, stream);
+    if ((rc = dlwp_fno_spatial(p, &s, stream)) || !t) return rc;
+    const int HW = p->H * p->W;
+    const dlwp_chan_src gy{a->g_x, (long long)p->C * HW, HW, nullptr, nullptr};
+    return dlwp_pwmlp_bwd_ex(t->x, t->w1, t->b1, t->w2, &gy, nullptr, nullptr, 0.f, t->gx, t->gx_accumulate, nullptr, t->gw1, t->gb1,
+                             t->gw2, t->gb2, t->slab, t->slab_accumulate, a->B, t->Cin, t->Ch, p->C, HW, stream);
+}
+
+int dlwp_fno_block_fwd_run(const dlwp_fno_plan* p, const dlwp_fno_block_fwd_args* a, hipStream_t stream) {
+    const dlwp_fno_forms d = dlwp_fno_fwd_decide(p, a);
+    if (d.rc) return d.rc;
+    const dlwp_fno_proj_fwd_tail* t = a->proj;
+    bool fused = d.spatial == DLWP_FNO_SPATIAL_FUSED_TAIL;
+    dlwp_fno_spatial_args s{};
+    s.tin = a->x; s.act_tin = a->act_in; s.spec = a->spec; s.wskip = a->wskip; s.bias = a->bias; s.out = a->pre;
+    s.x1_out = a->x1_out; s.x1_act = 1; s.B = a->B;
+    ProjFwdLaunch q;
+    int rc;
+    if (fused && (rc = proj_fwd_prepare(q, p, &s, t))) {
+        if (rc != DLWP_E_UNSUPPORTED || a->route != DLWP_FNO_ROUTE_AUTO) return rc;
+        fused = false;                           // the projection chain's own refusal: the separate launches below
+    }
+    if (a->rows_dft && (rc = dlwp_fno_rows_dft(p, a->x, a->act_in, 0, a->x1, a->B, stream))) return rc;
+    if ((rc = dlwp_fno_mix_fwd(p, a->x1, a->wspec, a->xhat, a->spec, a->B, stream))) return rc;
+    if (t && t->lifted) *t->lifted = fused && t->x2v;
+    if (fused) return proj_fwd_launch(q, p, a->B, stream);
+    if ((rc = dlwp_fno_spatial(p, &s, stream)) || !t) return rc;
+    // the projection chained with the next call's lifting MLP (the frames just produced go to the next window in LDS), or alone
+    const int HW = p->H * p->W;
+    const dlwp_chan_src ps{a->pre, (long long)p->C * HW, HW, nullptr, nullptr};
+    if (t->x2v) {
+        rc = dlwp_pwmlp_fwd_chain_ex(&ps, t->pw1, t->pb1, t->pw2, t->pb2, t->y1, t->res1, p->C, t->Ch1, t->Cout1, t->x2v, t->lw1, t->lb1,
+                                     t->lw2, t->lb2, t->y2, t->Cin2, t->Ch2, p->C, t->next_ch, a->B, HW, p, t->x1_next, stream);
+        if (rc == DLWP_OK && t->lifted) *t->lifted = 1;
+        if (rc != DLWP_E_UNSUPPORTED) return rc;
+    }
+    return dlwp_pwmlp_fwd_ex(&ps, t->pw1, t->pb1, t->pw2, t->pb2, t->y1, t->res1, a->B, p->C, t->Ch1, t->Cout1, HW, stream);
+}
+
+// ---- exported entry points on contiguous tensors: argument adapters around the two routines (they add the leading rows DFT)
+static dlwp_fno_block_bwd_args bwd_entry_args(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                              const float* wskip, const float* g_pre, const float* xhat, float* g_x, float* g_wspec,
+                                              int B, void* workspace, int route) {
+    const BlockWs ws = carve_ws(p, B, workspace);
+    dlwp_fno_block_bwd_args a{};
+    a.g_pre = g_pre; a.x = x; a.act_in = act_in; a.wspec = reinterpret_cast<const float2*>(wspec); a.wskip = wskip;
+    a.xhat = reinterpret_cast<const float2*>(xhat); a.g_x = g_x; a.g_wspec = reinterpret_cast<float2*>(g_wspec);
+    a.x1 = ws.x1; a.spec = ws.spec; a.rows_dft = 1; a.route = route; a.B = B;
+    return a;
+}
+static dlwp_fno_block_fwd_args fwd_entry_args(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                              const float* wskip, const float* bias, float* pre, float* xhat, int B,
+                                              void* workspace) {
+    const BlockWs ws = carve_ws(p, B, workspace);
+    dlwp_fno_block_fwd_args a{};
+    a.x = x; a.act_in = act_in; a.wspec = reinterpret_cast<const float2*>(wspec); a.wskip = wskip; a.bias = bias; a.pre = pre;
+    a.xhat = reinterpret_cast<float2*>(xhat); a.x1 = ws.x1; a.spec = ws.spec; a.rows_dft = 1; a.B = B;
+    return a;
+}
+
+extern "C" int dlwp_fno_block_fwd(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                  const float* wskip, const float* bias, float* pre, float* xhat, int B,
+                                  void* workspace, void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && pre && xhat && workspace && B > 0, DLWP_E_INVALID,
+                 "fno_block_fwd: NULL argument or B<=0");
+    const dlwp_fno_block_fwd_args a = fwd_entry_args(p, x, act_in, wspec, wskip, bias, pre, xhat, B, workspace);
+    return dlwp_fno_block_fwd_run(p, &a, static_cast<hipStream_t>(stream_));
+}
+
+// dlwp_fno_block_bwd / _bwd_slab: `spatial` forms the skip gradients whatever the knobs say -- the reference of the bit-for-bit tests
+extern "C" int dlwp_fno_block_bwd(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                  const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                                  float* g_wspec, float* g_wskip, float* g_bias, int B, void* workspace,
+                                  void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && workspace && B > 0,
+                 DLWP_E_INVALID, "fno_block_bwd: NULL argument or B<=0");
+    dlwp_fno_block_bwd_args a = bwd_entry_args(p, x, act_in, wspec, wskip, g_pre, xhat, g_x, g_wspec, B, workspace, DLWP_FNO_ROUTE_PLAIN);
+    a.g_wskip = g_wskip; a.g_bias = g_bias;
+    return dlwp_fno_block_bwd_run(p, &a, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int dlwp_fno_block_bwd_slab(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                       const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                                       float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
+                                       void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && slab && workspace && B > 0,
+                 DLWP_E_INVALID, "fno_block_bwd_slab: NULL argument or B<=0");
+    DLWP_REQUIRE(!dlwp_fno_is_wide(p), DLWP_E_UNSUPPORTED, "fno_block_bwd_slab: narrow layers only (hidden_channels <= 64, 2-D plan)");
+    dlwp_fno_block_bwd_args a = bwd_entry_args(p, x, act_in, wspec, wskip, g_pre, xhat, g_x, g_wspec, B, workspace, DLWP_FNO_ROUTE_PLAIN);
+    a.gslab = slab; a.gslab_accumulate = slab_accumulate;
+    return dlwp_fno_block_bwd_run(p, &a, static_cast<hipStream_t>(stream_));
+}
+
+// dlwp_fno_block_bwd_slab as the rollout trainer runs a block l > 0 with FNO_SKIP_WGRAD_IN_MIX on: rows DFT, the per-mode launch
+// that also forms the slab, then the four-wave `spatial` chain without by-products.  Every output bit for bit
+// dlwp_fno_block_bwd_slab's.  DLWP_E_UNSUPPORTED (error string untouched, nothing launched) for wide and 3-D plans, for shapes
+// whose two-role layout does not fit, and with the knob at 0.
+extern "C" int dlwp_fno_block_bwd_slab_split(const dlwp_fno_plan* p, const float* x, int act_in, const float* wspec,
+                                             const float* wskip, const float* g_pre, const float* xhat, float* g_x,
+                                             float* g_wspec, float* slab, int slab_accumulate, int B, void* workspace,
+                                             void* stream_) {
+    DLWP_REQUIRE(p && x && wspec && wskip && g_pre && xhat && g_x && g_wspec && slab && workspace && B > 0,
+                 DLWP_E_INVALID, "fno_block_bwd_slab_split: NULL argument or B<=0");
+    dlwp_fno_block_bwd_args a = bwd_entry_args(p, x, act_in, wspec, wskip, g_pre, xhat, g_x, g_wspec, B, workspace, DLWP_FNO_ROUTE_HOSTED);
+    a.gslab = slab; a.gslab_accumulate = slab_accumulate;
+    return dlwp_fno_block_bwd_run(p, &a, static_cast<hipStream_t>(stream_));
+}
+
+// block 0's backward with the lifting MLP's backward in its `spatial` launch, the per-mode form as the trainer picks it for
+// block 0 (hosting the skip-gradient workgroups unless FNO_SKIP_WGRAD_IN_MIX = 0)
+extern "C" int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* p, const float* h0, const float* wspec, const float* wskip,
+                                            const float* g_pre, const float* xhat, float* g_wspec, float* slab_skip,
+                                            int slab_skip_accumulate, const float* x, const float* w1, const float* b1,
+                                            const float* w2, float* gx, int gx_accumulate, float* slab_lift,
+                                            int slab_lift_accumulate, int B, int Cin, int Ch, void* workspace, void* stream_) {
+    DLWP_REQUIRE(p && h0 && wspec && wskip && g_pre && xhat && g_wspec && slab_skip && x && w1 && b1 && w2 && slab_lift &&
+                     workspace && B > 0 && Cin > 0 && Ch > 0,
+                 DLWP_E_INVALID, "fno_block_lift_bwd_slab: NULL argument or non-positive dimension");
+    const long long P = (long long)p->H * p->W;
+    const dlwp_chan_src xs{x, (long long)Cin * P, P, nullptr, nullptr};
+    const dlwp_chan_dst gxd{gx, (long long)Cin * P, P, nullptr, nullptr};
+    dlwp_fno_lift_bwd_tail t{};
+    t.x = &xs; t.w1 = w1; t.b1 = b1; t.w2 = w2; t.gx = gx ? &gxd : nullptr; t.gx_accumulate = gx_accumulate;
+    t.slab = slab_lift; t.slab_accumulate = slab_lift_accumulate; t.Cin = Cin; t.Ch = Ch;
+    dlwp_fno_block_bwd_args a = bwd_entry_args(p, h0, 0, wspec, wskip, g_pre, xhat, nullptr, g_wspec, B, workspace, DLWP_FNO_ROUTE_FUSED_TAIL);
+    a.first = 1; a.gslab = slab_skip; a.gslab_accumulate = slab_skip_accumulate; a.lift = &t;
+    const int rc = dlwp_fno_block_bwd_run(p, &a, static_cast<hipStream_t>(stream_));
+    DLWP_REQUIRE(rc != DLWP_E_UNSUPPORTED, DLWP_E_UNSUPPORTED,
+                 "fno_block_lift_bwd_slab: needs 64-wide rows, a narrow 2-D plan of at most 48 channels, Cin <= 32 and "
+                 "FNO_FUSE_LIFT_BWD != 0 (use dlwp_fno_block_bwd_slab + dlwp_pwmlp_bwd_slab)");
+    return rc;
+}
+
+// Test entry points.  dlwp_fno_block_proj_fwd: one FNO block (rows DFT, per-mode stage) whose `spatial` stage is the fused launch:
+// pre, xhat as dlwp_fno_block_fwd; frame [B, Cout1, H, W] = projection(pre) (+ res); and, with window != NULL,
 // h0_next [B, C, H, W] = lifting(window [B, Cin2, H, W] with channel next_ch[o] >= 0 taken from frame channel o, in LDS) and its
 // rows DFT x1_next [B][H][m2c][C] complex.  DLWP_E_UNSUPPORTED, nothing launched, where the trainer keeps the two launches.
 // dlwp_pwmlp_proj_lift_fwd: the second of those two launches (pwmlp_fwd_chain_kernel, or pwmlp_fwd_kernel without a window) on
@@ -1813,23 +1885,18 @@ extern "C" int dlwp_fno_block_proj_fwd(const dlwp_fno_plan* p, const float* x, i
     DLWP_REQUIRE(p && x && wspec && wskip && pre && xhat && pw1 && pb1 && pw2 && pb2 && frame && workspace && B > 0 &&
                      (!window || (lw1 && lb1 && lw2 && lb2 && h0_next && x1_next && next_ch)),
                  DLWP_E_INVALID, "fno_block_proj_fwd: NULL argument or B<=0");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    float2* x1 = static_cast<float2*>(workspace);
-    float2* y = reinterpret_cast<float2*>(static_cast<char*>(workspace) + align256(x1_elems(p, B) * sizeof(float2)));
     const long long HW = (long long)p->H * p->W;
-    dlwp_fno_spatial_args s{};
-    s.tin = x; s.act_tin = act_in; s.spec = y; s.wskip = wskip; s.bias = bias; s.out = pre; s.B = B;
     const dlwp_chan_dst fd{frame, Cout1 * HW, HW, nullptr, nullptr};
     const dlwp_chan_src rs{res, Cout1 * HW, HW, nullptr, nullptr};
     const dlwp_chan_src wsrc{window, Cin2 * HW, HW, nullptr, nullptr};
     const dlwp_chan_dst hd{h0_next, p->C * HW, HW, nullptr, nullptr};
-    ProjFwdLaunch q;
-    int rc = proj_fwd_prepare(q, p, &s, pw1, pb1, pw2, pb2, &fd, res ? &rs : nullptr, Ch1, Cout1, window ? &wsrc : nullptr, lw1, lb1,
-                              lw2, lb2, &hd, Cin2, Ch2, next_ch, reinterpret_cast<float2*>(x1_next));
-    if (rc) return rc;
-    if ((rc = dlwp_fno_rows_dft(p, x, act_in, 0, x1, B, stream))) return rc;
-    if ((rc = dlwp_fno_mix_fwd(p, x1, reinterpret_cast<const float2*>(wspec), reinterpret_cast<float2*>(xhat), y, B, stream))) return rc;
-    return proj_fwd_launch(q, p, B, stream);
+    dlwp_fno_proj_fwd_tail t{};
+    t.pw1 = pw1; t.pb1 = pb1; t.pw2 = pw2; t.pb2 = pb2; t.y1 = &fd; t.res1 = res ? &rs : nullptr; t.Ch1 = Ch1; t.Cout1 = Cout1;
+    t.x2v = window ? &wsrc : nullptr; t.lw1 = lw1; t.lb1 = lb1; t.lw2 = lw2; t.lb2 = lb2; t.y2 = &hd; t.Cin2 = Cin2; t.Ch2 = Ch2;
+    t.next_ch = next_ch; t.x1_next = reinterpret_cast<float2*>(x1_next);
+    dlwp_fno_block_fwd_args a = fwd_entry_args(p, x, act_in, wspec, wskip, bias, pre, xhat, B, workspace);
+    a.proj = &t; a.keep = 1; a.route = DLWP_FNO_ROUTE_FUSED_TAIL;
+    return dlwp_fno_block_fwd_run(p, &a, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int dlwp_pwmlp_proj_lift_fwd(const dlwp_fno_plan* p, const float* pre, const float* pw1, const float* pb1,

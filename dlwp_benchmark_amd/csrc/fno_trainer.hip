@@ -166,59 +166,39 @@ int enqueue_forward(dlwp_fno_trainer* tr, bool keep, hipStream_t s, bool fused =
         DLWP_HIP(hipMemcpy2DAsync(tr->out, tr->traj_out * sizeof(float), tr->x, tr->traj * sizeof(float),
                                   (size_t)(ctx - 1) * tr->frame * sizeof(float), c.B, hipMemcpyDeviceToDevice, s));
     }
-    bool lifted = false;             // the lifting MLP of call k has already run (chained behind call k - 1's projection)
+    int lifted = 0;                  // the lifting MLP of call k has already run (with call k - 1's projection)
     for (int k = 0; k < tr->ncalls; ++k) {
         const dlwp_fno_trainer::CallInfo& ci = tr->calls[k];
         const int kk = keep ? k : 0;  // evaluation reuses slot 0
         float* h0 = tr->h0 + kk * actB;
         float* pre = tr->pre + (long long)kk * NL * actB;
         float2* xhat = tr->xhat + (long long)kk * NL * xhatB;
+        float* oplane = tr->out + (long long)ci.out_slot * tr->frame;
+        const long long zlB = (long long)c.B * c.lifting * P, zpB = (long long)c.B * c.projection * HW;     // wide layers
+        // lifting MLP, and the first block's W-axis DFT into x1
         if (tr->wide) {
-            // channel-blocked kernels + channels-first GEMM MLPs (fno_wide.hip); same dataflow as below
+            // channels-first GEMM MLPs (fno_wide.hip) on a dense copy of the window
             // (3-D context form: the gather table holds D * ctx frame planes = the [D][ctx * HW] volume the lifting layer
             // reads as D channels of P = ctx * HW pixels; the projection runs on the LAST time slice only, fno.py:96)
-            const long long xinB = (long long)c.B * tr->Cin * HW, zlB = (long long)c.B * c.lifting * P,
-                            zpB = (long long)c.B * c.projection * HW;
-            float* xin = tr->xin + kk * xinB;
+            float* xin = tr->xin + kk * (long long)c.B * tr->Cin * HW;
             if ((rc = dlwp_gather_channels(tr->src_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin, xin,
                                            c.B, tr->Cin, HW, s))) return rc;
             if ((rc = dlwp_cfmlp_fwd(xin, (long long)tr->Cin * HW, w.lw1, w.lb1, w.lw2, w.lb2, h0, tr->act, nullptr, 0,
                                      tr->zl + kk * zlB, tr->al + kk * zlB, c.B, LCin, c.lifting, C, P, s))) return rc;
             if ((rc = dlwp_fno_rows_dft(tr->plan, h0, 0, 0, tr->x1, c.B, s))) return rc;
-            for (int l = 0; l < NL; ++l) {
-                if ((rc = dlwp_fno_mix_fwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)),
-                                           xhat + l * xhatB, tr->spec, c.B, s))) return rc;
-                dlwp_fno_spatial_args a{};
-                a.tin = l == 0 ? h0 : pre + (l - 1) * actB;
-                a.act_tin = l > 0;
-                a.spec = tr->spec; a.wskip = w.skip(l); a.bias = w.bias(l);
-                a.out = pre + l * actB;
-                a.x1_out = l < NL - 1 ? tr->x1 : nullptr;
-                a.x1_act = 1;
-                a.B = c.B;
-                if ((rc = dlwp_fno_spatial(tr->plan, &a, s))) return rc;
-            }
-            if ((rc = dlwp_cfmlp_fwd(pre + (NL - 1) * actB + (P - HW), tr->act, w.pw1, w.pb1, w.pw2, w.pb2,
-                                     tr->out + (long long)ci.out_slot * tr->frame, tr->traj_out, ci.res, ci.res_bs,
-                                     tr->zp + kk * zpB, tr->ap + kk * zpB, c.B, C, c.projection, c.out_channels, HW, s, P))) return rc;
-            continue;
-        }
-        // lifting MLP with the first block's W-axis DFT in its epilogue where the shapes allow (one launch less per net
-        // call); otherwise the callee runs the separate rows kernel.  From the second call on it has normally already run,
-        // chained behind the previous call's projection (below).
-        if (!lifted) {
+        } else if (!lifted) {
+            // the DFT rides in the MLP's epilogue where the shapes allow (one launch less per net call); otherwise the callee
+            // runs the separate rows kernel.  From the second call on all this has normally run with the previous call's projection.
             dlwp_chan_src xs{nullptr, 0, 0, tr->src_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
             dlwp_chan_dst h0d{h0, tr->act, HW, nullptr, nullptr};
             if ((rc = dlwp_pwmlp_fwd_rows_ex(&xs, w.lw1, w.lb1, w.lw2, w.lb2, &h0d, nullptr, c.B, tr->Cin, c.lifting, C, HW,
                                              tr->plan, tr->x1, s))) return rc;
         }
-        lifted = false;
-        dlwp_chan_src ps{pre + (NL - 1) * actB, tr->act, HW, nullptr, nullptr};
-        float* oplane = tr->out + (long long)ci.out_slot * tr->frame;
+        // narrow layers: the projection runs with the last block, and with it the lifting of the next call where they chain
+        // (the frame(s) just produced go to the next window in LDS)
         dlwp_chan_dst od{oplane, tr->traj_out, HW, nullptr, nullptr};
         dlwp_chan_src rs{ci.res, ci.res_bs, HW, nullptr, nullptr};  // out = last frame + net (dlwp fno.py:103)
-        // projection of this call chained with the lifting of the next: the frame(s) just produced go to the next window in LDS
-        const bool chain = k + 1 < tr->ncalls && c.out_channels <= 8;
+        const bool chain = !tr->wide && k + 1 < tr->ncalls && c.out_channels <= 8;
         signed char next_ch[8];
         for (int o = 0; o < 8; ++o) next_ch[o] = -1;
         const size_t t1 = (size_t)(k + 1) * tr->Cin;
@@ -226,44 +206,28 @@ int enqueue_forward(dlwp_fno_trainer* tr, bool keep, hipStream_t s, bool fused =
             for (int o = 0; o < c.out_channels; ++o)
                 for (int ch = 0; ch < tr->Cin; ++ch)
                     if (tr->h_src[t1 + ch] == oplane + (long long)o * HW && tr->h_bs[t1 + ch] == tr->traj_out) next_ch[o] = (signed char)ch;
-        const int k1 = keep ? k + 1 : 0;
         dlwp_chan_src xs1{nullptr, 0, 0, tr->src_tab + (long long)(k + 1) * tr->Cin, tr->bstride_tab + (long long)(k + 1) * tr->Cin};
-        dlwp_chan_dst h0d1{tr->h0 + k1 * actB, tr->act, HW, nullptr, nullptr};
-        bool projected = false;          // the last block's `spatial` launch has run the projection (and the next lifting) too
+        dlwp_chan_dst h0d1{tr->h0 + (keep ? k + 1 : 0) * actB, tr->act, HW, nullptr, nullptr};
+        dlwp_fno_proj_fwd_tail t{};
+        t.pw1 = w.pw1; t.pb1 = w.pb1; t.pw2 = w.pw2; t.pb2 = w.pb2; t.y1 = &od; t.res1 = ci.res ? &rs : nullptr;
+        t.Ch1 = c.projection; t.Cout1 = c.out_channels;
+        t.x2v = chain ? &xs1 : nullptr; t.lw1 = w.lw1; t.lb1 = w.lb1; t.lw2 = w.lw2; t.lb2 = w.lb2; t.y2 = &h0d1;
+        t.Cin2 = tr->Cin; t.Ch2 = c.lifting; t.next_ch = next_ch; t.x1_next = tr->x1; t.lifted = &lifted;
         for (int l = 0; l < NL; ++l) {
-            if ((rc = dlwp_fno_mix_fwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)),
-                                       xhat + l * xhatB, tr->spec, c.B, s))) return rc;
-            dlwp_fno_spatial_args a{};
-            a.tin = l == 0 ? h0 : pre + (l - 1) * actB;
-            a.act_tin = l > 0;
-            a.spec = tr->spec; a.wskip = w.skip(l); a.bias = w.bias(l);
-            a.out = pre + l * actB;
+            dlwp_fno_block_fwd_args a{};
+            a.x = l == 0 ? h0 : pre + (l - 1) * actB;
+            a.act_in = l > 0;
+            a.wspec = reinterpret_cast<const float2*>(w.spec(l)); a.wskip = w.skip(l); a.bias = w.bias(l);
+            a.pre = pre + l * actB; a.xhat = xhat + l * xhatB;
+            a.x1 = tr->x1; a.spec = tr->spec;
             a.x1_out = l < NL - 1 ? tr->x1 : nullptr;
-            a.x1_act = 1;
-            a.B = c.B;
-            if (l == NL - 1 && keep) {
-                // training rollout (activations kept): the last block's `spatial`, the projection and, behind it, the next call's
-                // lifting MLP as one launch where the shapes allow; otherwise the launches below.  The evaluation path
-                // (keep == false) always keeps them: the fused launch was built for and measured on the training step, and
-                // pwmlp_fwd_chain_kernel stays the kernel an evaluation rollout is tested on
-                rc = dlwp_fno_spatial_proj_fwd(tr->plan, &a, w.pw1, w.pb1, w.pw2, w.pb2, &od, ci.res ? &rs : nullptr, c.projection,
-                                               c.out_channels, chain ? &xs1 : nullptr, w.lw1, w.lb1, w.lw2, w.lb2, &h0d1, tr->Cin,
-                                               c.lifting, next_ch, tr->x1, s);
-                if (rc == DLWP_OK) { projected = true; lifted = chain; break; }
-                if (rc != DLWP_E_UNSUPPORTED) return rc;
-            }
-            if ((rc = dlwp_fno_spatial(tr->plan, &a, s))) return rc;
+            a.proj = !tr->wide && l == NL - 1 ? &t : nullptr;
+            a.keep = keep; a.B = c.B;
+            if ((rc = dlwp_fno_block_fwd_run(tr->plan, &a, s))) return rc;
         }
-        if (projected) continue;
-        if (chain) {
-            rc = dlwp_pwmlp_fwd_chain_ex(&ps, w.pw1, w.pb1, w.pw2, w.pb2, &od, ci.res ? &rs : nullptr, C, c.projection, c.out_channels,
-                                         &xs1, w.lw1, w.lb1, w.lw2, w.lb2, &h0d1, tr->Cin, c.lifting, C, next_ch, c.B, HW,
-                                         tr->plan, tr->x1, s);
-            if (rc == DLWP_OK) { lifted = true; continue; }
-            if (rc != DLWP_E_UNSUPPORTED) return rc;
-        }
-        if ((rc = dlwp_pwmlp_fwd_ex(&ps, w.pw1, w.pb1, w.pw2, w.pb2, &od, ci.res ? &rs : nullptr, c.B, C, c.projection,
-                                    c.out_channels, HW, s))) return rc;
+        if (tr->wide && (rc = dlwp_cfmlp_fwd(pre + (NL - 1) * actB + (P - HW), tr->act, w.pw1, w.pb1, w.pw2, w.pb2, oplane,
+                                              tr->traj_out, ci.res, ci.res_bs, tr->zp + kk * zpB, tr->ap + kk * zpB, c.B, C,
+                                              c.projection, c.out_channels, HW, s, P))) return rc;
     }
     return DLWP_OK;
 }
@@ -298,9 +262,11 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
         float* pre = tr->pre + (long long)k * NL * actB;
         float2* xhat = tr->xhat + (long long)k * NL * xhatB;
         float *gcur = tr->gA, *gnext = tr->gB;
+        const int later_call = k != tr->ncalls - 1;      // the slabs already hold the partials of the calls behind this one
+        const long long xinB = (long long)c.B * tr->Cin * HW, zlB = (long long)c.B * c.lifting * P,         // wide layers
+                        zpB = (long long)c.B * c.projection * HW, CP = (long long)c.out_channels * HW;
+        // projection backward into gcur, and its adjoint W-axis DFT into x1
         if (tr->wide) {
-            const long long xinB = (long long)c.B * tr->Cin * HW, zlB = (long long)c.B * c.lifting * P,
-                            zpB = (long long)c.B * c.projection * HW, CP = (long long)c.out_channels * HW;
             // upstream of the projection = accumulated closed-loop gradient + d MSE / d out[t]; identity path of the residual
             if ((rc = dlwp_proj_gy(tr->g_out + oofs, grad_out ? nullptr : tr->out + oofs, grad_out ? nullptr : tr->y + oofs,
                                    mse_scale, tr->gyb, ci.gres, tr->traj_out, ci.gres_bs, CP, c.B, s))) return rc;
@@ -310,89 +276,51 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
                                      tr->ap + k * zpB, gcur + (P - HW), tr->act, tr->gz, g.pw1, g.pb1, g.pw2, g.pb2, c.B, C,
                                      c.projection, c.out_channels, HW, s, P, P))) return rc;
             if ((rc = dlwp_fno_rows_dft(tr->plan, gcur, 0, 1, tr->x1, c.B, s))) return rc;
-            for (int l = NL - 1; l >= 0; --l) {
-                if ((rc = dlwp_fno_mix_bwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)),
-                                           xhat + l * xhatB, tr->spec, reinterpret_cast<float2*>(g.spec(l)), c.B, s))) return rc;
-                dlwp_fno_spatial_args a{};
-                a.tin = gcur; a.spec = tr->spec; a.wskip = w.skip(l); a.transpose_w = 1;
-                a.pprev = l == 0 ? h0 : pre + (l - 1) * actB;
-                a.act_prev = l > 0;
-                a.out = gnext;
-                a.x1_out = l > 0 ? tr->x1 : nullptr;
-                a.x1_adjoint = 1;
-                a.g_wskip = g.skip(l); a.g_bias = g.bias(l);
-                a.inverse_adjoint = 1;
-                a.B = c.B;
-                if ((rc = dlwp_fno_spatial(tr->plan, &a, s))) return rc;
-                float* tmp = gcur; gcur = gnext; gnext = tmp;
-            }
+        } else {
+            // upstream = accumulated closed-loop gradient + d MSE / d out[t]
+            dlwp_chan_src ps{pre + (NL - 1) * actB, tr->act, HW, nullptr, nullptr};
+            dlwp_chan_src gy{tr->g_out + oofs, tr->traj_out, HW, nullptr, nullptr};
+            dlwp_chan_src pred{tr->out + oofs, tr->traj_out, HW, nullptr, nullptr};
+            dlwp_chan_src targ{tr->y + oofs, tr->traj_out, HW, nullptr, nullptr};
+            dlwp_chan_dst gx{gcur, tr->act, HW, nullptr, nullptr};
+            dlwp_chan_dst gr{ci.gres, ci.gres_bs, HW, nullptr, nullptr};  // identity path of the residual
+            // the DFT of the finished gradient rows rides in the epilogue where the shapes allow (one launch less per net
+            // call); otherwise the callee runs the separate rows kernel
+            if ((rc = dlwp_pwmlp_bwd_rows_ex(&ps, w.pw1, w.pb1, w.pw2, &gy, grad_out ? nullptr : &pred,
+                                             grad_out ? nullptr : &targ, mse_scale, &gx, 0, ci.gres ? &gr : nullptr, g.pw1,
+                                             g.pb1, g.pw2, g.pb2, tr->slab_proj, later_call, c.B, C, c.projection,
+                                             c.out_channels, HW, tr->plan, tr->x1, s))) return rc;
+        }
+        // narrow layers: the lifting backward runs with block 0; input-channel gradients flow into the predictions that fed this step
+        dlwp_chan_src xs{nullptr, 0, 0, tr->src_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
+        dlwp_chan_dst gxd{nullptr, 0, 0, tr->gdst_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
+        dlwp_fno_lift_bwd_tail t{};
+        t.x = &xs; t.w1 = w.lw1; t.b1 = w.lb1; t.w2 = w.lw2; t.gx = &gxd; t.gx_accumulate = 1;
+        t.gw1 = g.lw1; t.gb1 = g.lb1; t.gw2 = g.lw2; t.gb2 = g.lb2;
+        t.slab = tr->slab_lift; t.slab_accumulate = later_call; t.Cin = tr->Cin; t.Ch = c.lifting;
+        for (int l = NL - 1; l >= 0; --l) {
+            dlwp_fno_block_bwd_args a{};
+            a.g_pre = gcur;
+            a.x = l == 0 ? h0 : pre + (l - 1) * actB;
+            a.act_in = l > 0; a.first = l == 0;
+            a.wspec = reinterpret_cast<const float2*>(w.spec(l)); a.wskip = w.skip(l); a.xhat = xhat + l * xhatB;
+            a.g_x = gnext; a.g_wspec = reinterpret_cast<float2*>(g.spec(l));
+            if (tr->wide) { a.g_wskip = g.skip(l); a.g_bias = g.bias(l); }      // the GEMMs accumulate straight into the gradient buffer
+            else { a.gslab = tr->slab_skip + (long long)l * c.B * c.H * dlwp_fno_gslab_stride(C); a.gslab_accumulate = later_call; }
+            a.x1 = tr->x1; a.spec = tr->spec;
+            a.x1_out = l > 0 ? tr->x1 : nullptr;
+            a.lift = !tr->wide && l == 0 ? &t : nullptr;
+            a.B = c.B;
+            if ((rc = dlwp_fno_block_bwd_run(tr->plan, &a, s))) return rc;
+            float* tmp = gcur; gcur = gnext; gnext = tmp;
+        }
+        if (tr->wide) {
             if ((rc = dlwp_cfmlp_bwd(tr->xin + k * xinB, (long long)tr->Cin * HW, w.lw1, w.lw2, gcur, tr->act, tr->zl + k * zlB,
                                      tr->al + k * zlB, tr->gxin, (long long)tr->Cin * HW, tr->gz, g.lw1, g.lb1, g.lw2, g.lb2, c.B,
                                      LCin, c.lifting, C, P, s))) return rc;
             if ((rc = dlwp_scatter_add_channels(tr->gdst_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin,
                                                 tr->gxin, c.B, tr->Cin, HW, s))) return rc;
-            continue;
         }
-        // projection backward; upstream = accumulated closed-loop gradient + d MSE / d out[t]
-        dlwp_chan_src ps{pre + (NL - 1) * actB, tr->act, HW, nullptr, nullptr};
-        dlwp_chan_src gy{tr->g_out + oofs, tr->traj_out, HW, nullptr, nullptr};
-        dlwp_chan_src pred{tr->out + oofs, tr->traj_out, HW, nullptr, nullptr};
-        dlwp_chan_src targ{tr->y + oofs, tr->traj_out, HW, nullptr, nullptr};
-        dlwp_chan_dst gx{gcur, tr->act, HW, nullptr, nullptr};
-        dlwp_chan_dst gr{ci.gres, ci.gres_bs, HW, nullptr, nullptr};  // identity path of the residual
-        // the adjoint W-axis DFT of the finished gradient rows rides in the epilogue where the shapes allow (one launch
-        // less per net call); otherwise the callee runs the separate rows kernel
-        if ((rc = dlwp_pwmlp_bwd_rows_ex(&ps, w.pw1, w.pb1, w.pw2, &gy, grad_out ? nullptr : &pred,
-                                         grad_out ? nullptr : &targ, mse_scale, &gx, 0, ci.gres ? &gr : nullptr, g.pw1,
-                                         g.pb1, g.pw2, g.pb2, tr->slab_proj, k != tr->ncalls - 1, c.B, C, c.projection,
-                                         c.out_channels, HW, tr->plan, tr->x1, s))) return rc;
-        // lifting backward; input-channel gradients flow into the predictions that fed this step
-        dlwp_chan_src xs{nullptr, 0, 0, tr->src_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
-        dlwp_chan_dst gxd{nullptr, 0, 0, tr->gdst_tab + (long long)k * tr->Cin, tr->bstride_tab + (long long)k * tr->Cin};
-        bool lift_done = false;
-        for (int l = NL - 1; l >= 0; --l) {
-            dlwp_fno_spatial_args a{};
-            a.tin = gcur; a.spec = tr->spec; a.wskip = w.skip(l); a.transpose_w = 1;
-            a.pprev = l == 0 ? h0 : pre + (l - 1) * actB;
-            a.act_prev = l > 0;
-            a.out = gnext;
-            a.x1_out = l > 0 ? tr->x1 : nullptr;
-            a.x1_adjoint = 1;
-            a.gslab = tr->slab_skip + (long long)l * c.B * c.H * dlwp_fno_gslab_stride(C);
-            a.gslab_accumulate = k != tr->ncalls - 1;
-            a.inverse_adjoint = 1;
-            a.B = c.B;
-            // The skip-weight / bias gradient partials of the block need only gcur and pprev, which are complete here: where the
-            // shapes allow, extra workgroups of the per-mode launch (most CUs idle through it) form them into the slab and the
-            // `spatial` launch behind it runs its chain alone.  Block 0 takes this form together with its fused launch; where
-            // that one is refused it keeps the two-role `spatial` launch.
-            rc = (l > 0 || dlwp_fno_spatial_lift_bwd_fuses(tr->plan, tr->Cin, c.lifting))
-                     ? dlwp_fno_mix_bwd_skipgrad(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)), xhat + l * xhatB,
-                                                 tr->spec, reinterpret_cast<float2*>(g.spec(l)), a.tin, a.pprev, a.act_prev, a.gslab,
-                                                 a.gslab_accumulate, c.B, s)
-                     : DLWP_E_UNSUPPORTED;
-            if (rc == DLWP_OK) a.gslab = nullptr;
-            else if (rc != DLWP_E_UNSUPPORTED) return rc;
-            else if ((rc = dlwp_fno_mix_bwd(tr->plan, tr->x1, reinterpret_cast<const float2*>(w.spec(l)), xhat + l * xhatB, tr->spec,
-                                            reinterpret_cast<float2*>(g.spec(l)), c.B, s))) return rc;
-            if (l == 0) {
-                // block 0's `spatial` and the lifting backward as one launch where the shapes allow: the gradient of h0 stays in
-                // LDS (gnext is not written); otherwise the two launches below
-                dlwp_fno_spatial_args f = a;
-                f.out = nullptr;
-                rc = dlwp_fno_spatial_lift_bwd(tr->plan, &f, &xs, w.lw1, w.lb1, w.lw2, &gxd, 1, tr->slab_lift,
-                                               k != tr->ncalls - 1, tr->Cin, c.lifting, s);
-                if (rc == DLWP_OK) { lift_done = true; break; }
-                if (rc != DLWP_E_UNSUPPORTED) return rc;
-            }
-            if ((rc = dlwp_fno_spatial(tr->plan, &a, s))) return rc;
-            float* tmp = gcur; gcur = gnext; gnext = tmp;
-        }
-        if (lift_done) continue;
-        dlwp_chan_src gh0{gcur, tr->act, HW, nullptr, nullptr};
-        if ((rc = dlwp_pwmlp_bwd_ex(&xs, w.lw1, w.lb1, w.lw2, &gh0, nullptr, nullptr, 0.f, &gxd, 1, nullptr, g.lw1, g.lb1,
-                                    g.lw2, g.lb2, tr->slab_lift, k != tr->ncalls - 1, c.B, tr->Cin, c.lifting, C,
-                                    HW, s))) return rc;
     }
     if (tr->wide) return DLWP_OK;       // the GEMMs accumulated straight into the gradient buffer
     // fold the per-workgroup partial slabs of all net calls into the gradient buffer: one launch when the job table holds

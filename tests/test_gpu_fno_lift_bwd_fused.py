@@ -2,7 +2,9 @@
 lifting output stays in LDS between the two bodies instead of going through a [B, C, H, W] tensor.
 
 1. dlwp_fno_block_lift_bwd_slab against the two-launch sequence of the same build -- dlwp_fno_block_bwd_slab (act_in = 0) then
-   dlwp_pwmlp_bwd_slab on its g_x -- as the rollout trainer runs them: a plain-store call, an accumulating call, the folds.
+   dlwp_pwmlp_bwd_slab on its g_x -- as the rollout trainer runs them: a plain-store call, an accumulating call, the folds; with
+   the knob FNO_SKIP_WGRAD_IN_MIX at 1 (the trainer's default block-0 route: hosting per-mode launch, phase 1 without role B)
+   and at 0 (plain per-mode launch, role B).
    Both sequences run the same phase text on the same workgroup with the same slabs, so every output is compared bit for bit;
    each is also held to a float64 reference (autograd on the oracle's block and MLP in double) under the 5e-4 of
    tests/test_gpu_fno.py.  Shapes: one channel tile with a ragged hidden width; the headline's channels on a quarter-height
@@ -95,6 +97,9 @@ NAMES = ("gx", "gw1", "gb1", "gw2", "gb2", "gk", "gb", "gwspec")
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_entry_point_against_two_launches(L, cuda, case):
+    """Both values of FNO_SKIP_WGRAD_IN_MIX: the entry takes the per-mode form the trainer takes for block 0.  On (the default), the
+    launch that hosts the skip-gradient workgroups, followed by the phase-1 form without role B; off, the plain per-mode launch and
+    role B.  Every output of either is bit for bit the two launches'."""
     B, Cc, H, n_modes, Cin, Ch = case
     lib = L.load()
     m1, m2c = n_modes[0], n_modes[1] // 2 + 1
@@ -137,27 +142,42 @@ def test_entry_point_against_two_launches(L, cuda, case):
             torch.cuda.synchronize()
             return dict(gx=gx, gw1=g["w1"], gb1=g["b1"], gw2=g["w2"], gb2=g["b2"], gk=g["wskip"], gb=g["bias"], gwspec=gwspec), tail, g_h0
 
-        with L.kernel_accounting() as acc:
-            got, tail, g_h0 = run(True)
-        names = {r["name"] for r in acc.rows}
+        fused = {}
+        try:
+            for knob in (1, 0):
+                L.set_tuning("FNO_SKIP_WGRAD_IN_MIX", knob)
+                with L.kernel_accounting() as acc:
+                    res = run(True)
+                fused[knob] = res + ({r["name"]: r["calls"] for r in acc.rows},)
+        finally:
+            L.set_tuning("FNO_SKIP_WGRAD_IN_MIX", None)
         two, tail2, g_h0_two = run(False)
     finally:
         lib.dlwp_fno_plan_destroy(plan)
 
     # float64: gx is the last call's (overwritten), the parameter gradients are the sum of both calls
     ref = {k: (ref_b[k] if k == "gx" else ref_a[k] + ref_b[k]) for k in NAMES}
-    err = {k: rel_err(got[k], ref[k]) for k in ref}
-    print({"case": case_id(case), "err": err, "kernels": sorted(n for n in names if n.startswith(("fno_spatial", "pwmlp_bwd")))})
     nib, ncb, nbn = (Cin + 15) // 16, (Cc + 15) // 16, (2 * m2c + 15) // 16
-    assert "fno_spatial_lift_bwd_kernel<%d, %d, %d>" % (ncb, nbn, nib) in names, names
-    assert not any(n.startswith(("fno_spatial_roles", "pwmlp_bwd")) for n in names), names
-    assert bool((tail == SENTINEL).all()) and bool((tail2 == SENTINEL).all()), "a kernel wrote past the end of gx"
-    assert bool((g_h0 == POISON).all()), "the fused launch wrote the gradient of the lifting output"
+    assert bool((tail2 == SENTINEL).all()), "a kernel wrote past the end of gx"
     assert not bool((g_h0_two == POISON).any())
-    for k in NAMES:
-        assert torch.equal(got[k].view(torch.int32), two[k].view(torch.int32)), "not bit for bit the two launches: " + k
-    for k, e in err.items():
-        assert e <= GRAD_TOL, (k, e)
+    for knob, (got, tail, g_h0, calls) in fused.items():
+        names = set(calls)
+        err = {k: rel_err(got[k], ref[k]) for k in ref}
+        print({"case": case_id(case), "knob": knob, "err": err,
+               "kernels": sorted(n for n in names if n.startswith(("fno_mix", "fno_spatial", "pwmlp_bwd")))})
+        assert "fno_spatial_lift_bwd_kernel<%d, %d, %d>" % (ncb, nbn, nib) in names, names
+        assert not any(n.startswith(("fno_spatial_roles", "pwmlp_bwd")) for n in names), names
+        # Which per-mode launch ran.  The hosting launch has an accounting row; the plain fno_mix_bwd launch has none, so that it
+        # ran in both calls shows in gwspec, which only a per-mode launch accumulates: it is held to the sum of the two calls below.
+        host = "fno_mix_bwd_skipgrad_kernel<true, %d>" % ncb
+        mix = {n: c for n, c in calls.items() if n.startswith("fno_mix_bwd")}
+        assert mix == ({host: 2} if knob else {}), (knob, mix)
+        assert bool((tail == SENTINEL).all()), "a kernel wrote past the end of gx"
+        assert bool((g_h0 == POISON).all()), "the fused launch wrote the gradient of the lifting output"
+        for k in NAMES:
+            assert torch.equal(got[k].view(torch.int32), two[k].view(torch.int32)), "not bit for bit the two launches: " + k
+        for k, e in err.items():
+            assert e <= GRAD_TOL, (knob, k, e)
 
 
 @pytest.mark.gpu
