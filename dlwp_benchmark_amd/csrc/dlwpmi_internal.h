@@ -215,6 +215,13 @@ int dlwp_fold_slabs(const dlwp_fold_job* jobs, int njobs, hipStream_t stream);
 int dlwp_rollout_prep(float* loss, float* g_out, long long n, float* out, const float* x, long long out_bs, long long x_bs,
                       long long row, int B, hipStream_t stream);
 
+// train_ops.hip -- dlwp_sqerr_sum whose result does not depend on the order in which the workgroups finish (no float atomics):
+// ws holds one partial per workgroup and an arrival counter, is zeroed once by its owner and serves one call at a time
+constexpr int DLWP_SQERR_MAX_WGS = 2048;
+constexpr int DLWP_SQERR_WS_FLOATS = DLWP_SQERR_MAX_WGS + 4;
+int dlwp_sqerr_sum_ordered(const float* a, const float* b, long long n, float scale, float* loss_out, float* ws,
+                           hipStream_t stream);
+
 // token_ops.hip -- the MFMA GEMM with the channels-first extensions of the wide FNO path (fno_wide.hip).
 // C_z[M][N] (+)= epilogue(op(A_z)[M][K] . op(B_z)[K][N]), z < nb, operand z at base + z * s? (0 = shared).  Batches that share
 // the output (sC == 0, nb > 1) and long-K products are combined with float atomics (C zeroed first unless accumulate).

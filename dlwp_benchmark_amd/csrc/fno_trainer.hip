@@ -34,6 +34,7 @@ struct dlwp_fno_trainer {
     float *out = nullptr, *loss = nullptr;
     // trainer-owned device memory
     float* g_out = nullptr;
+    float* loss_ws = nullptr;                // dlwp_sqerr_sum_ordered: per-workgroup partials + arrival counter
     float *h0 = nullptr, *pre = nullptr;     // [ncalls][B,C,H,W], [ncalls][NL][B,C,H,W]
     float2* xhat = nullptr;                  // [ncalls][NL][B,m1,m2c,C]
     float2 *x1 = nullptr, *spec = nullptr;   // work
@@ -251,7 +252,8 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
     } else {
         // fused nn.MSELoss(reduction="mean") against the trainer's target buffer
         if (!fused && (rc = dlwp_zero_f32(tr->loss, 1, s))) return rc;
-        if ((rc = dlwp_sqerr_sum(tr->out, tr->y, n, 1.0f / (float)n, tr->loss, s))) return rc;
+        // (summed in workgroup order: the loss a training log prints is the same in every run of the same data)
+        if ((rc = dlwp_sqerr_sum_ordered(tr->out, tr->y, n, 1.0f / (float)n, tr->loss, tr->loss_ws, s))) return rc;
         if (!fused && (rc = dlwp_zero_f32(tr->g_out, n, s))) return rc;
         mse_scale = 2.0f / (float)n;
     }
@@ -405,7 +407,7 @@ extern "C" int dlwp_fno_trainer_create(const dlwp_fno_cfg* cfg, dlwp_fno_trainer
             return rc;
         }
     }
-    if ((rc = dmalloc(&tr->g_out, n)) ||
+    if ((rc = dmalloc(&tr->g_out, n)) || (rc = dmalloc(&tr->loss_ws, (size_t)DLWP_SQERR_WS_FLOATS)) ||
         (rc = dmalloc(&tr->h0, actB * tr->ncalls)) || (rc = dmalloc(&tr->pre, actB * tr->ncalls * c.n_layers)) ||
         (rc = dmalloc(&tr->xhat, xhatB * tr->ncalls * c.n_layers)) ||
         (rc = dmalloc(&tr->x1, (size_t)c.B * eff_H(c) * c.m2c * c.hidden)) || (rc = dmalloc(&tr->spec, xhatB)) ||
@@ -419,6 +421,12 @@ extern "C" int dlwp_fno_trainer_create(const dlwp_fno_cfg* cfg, dlwp_fno_trainer
         (rc = dmalloc(&tr->gdst_tab, (size_t)tr->ncalls * tr->Cin)) || (rc = dmalloc(&tr->bstride_tab, (size_t)tr->ncalls * tr->Cin))) {
         dlwp_fno_trainer_destroy(tr);
         return rc;
+    }
+    const hipError_t e = hipMemset(tr->loss_ws, 0, DLWP_SQERR_WS_FLOATS * sizeof(float));      // the arrival counter starts at 0
+    if (e != hipSuccess) {
+        dlwp_set_error("fno_trainer_create: hipMemset -> %s", hipGetErrorString(e));
+        dlwp_fno_trainer_destroy(tr);
+        return DLWP_E_HIP;
     }
     *out = tr;
     return DLWP_OK;
@@ -521,7 +529,7 @@ extern "C" void dlwp_fno_trainer_destroy(dlwp_fno_trainer* tr) {
     if (tr->graph) (void)hipGraphDestroy(tr->graph);
     if (tr->cap_stream) (void)hipStreamDestroy(tr->cap_stream);
     dlwp_fno_plan_destroy(tr->plan);
-    void* bufs[] = {tr->slab_skip, tr->slab_lift, tr->slab_proj, tr->g_out, tr->h0, tr->pre, tr->xhat, tr->x1, tr->spec,
+    void* bufs[] = {tr->slab_skip, tr->slab_lift, tr->slab_proj, tr->g_out, tr->loss_ws, tr->h0, tr->pre, tr->xhat, tr->x1, tr->spec,
                     tr->gA, tr->gB, (void*)tr->src_tab, (void*)tr->gdst_tab, tr->bstride_tab, tr->xin, tr->zl, tr->al, tr->zp,
                     tr->ap, tr->gz, tr->gyb, tr->gxin};
     for (void* b : bufs)

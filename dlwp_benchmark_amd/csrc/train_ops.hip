@@ -55,8 +55,42 @@ __device__ __forceinline__ void block_atomic_sum(float v, float* out) {
     if (threadIdx.x == 0) atomic_add_f32(out, part[0] + part[1] + part[2] + part[3]);
 }
 
+// block-wide sum -> out += the sum over ALL workgroups in workgroup order, whatever order they finish in: every workgroup
+// leaves its partial in ws[blockIdx.x] and takes a ticket from the arrival counter ws[DLWP_SQERR_MAX_WGS]; the one that draws
+// the last ticket adds the partials (lane t the partials t, t + 256, ..., then the fixed butterfly) and re-arms the counter.
+// Nobody waits for anybody.  Every shared word is an agent-scope atomic access: the partial is a write-through store that
+// its lane drains (vmcnt(0)) before it takes the ticket, so the ticket needs no release -- a release would write back the
+// XCD's whole dirty L2, 0.15 % of the headline step when every workgroup did it -- and the last workgroup's one acquire
+// fence drops its stale lines before it reads the partials.
+__device__ __forceinline__ void block_ordered_sum(float v, float* out, float* ws) {
+    __shared__ float part[4];
+    __shared__ int last;
+    unsigned* count = reinterpret_cast<unsigned*>(ws + DLWP_SQERR_MAX_WGS);
+    v = wave_sum(v);
+    if (lane_id() == 0) part[wave_id()] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(ws + blockIdx.x, part[0] + part[1] + part[2] + part[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        last = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;                                       // (workgroup-uniform)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    float s = 0.f;
+    for (unsigned i = threadIdx.x; i < gridDim.x; i += 256) s += __hip_atomic_load(ws + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s = wave_sum(s);
+    if (lane_id() == 0) part[wave_id()] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *out += part[0] + part[1] + part[2] + part[3];
+        __hip_atomic_store(count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void sqerr_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                    long long n, float scale, float* out) {
+                                                    long long n, float scale, float* out, float* ws) {
     float acc = 0.f;
     const long long n4 = n / 4;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -70,7 +104,8 @@ __global__ __launch_bounds__(256) void sqerr_kernel(const float* __restrict__ a,
         const float d = a[n4 * 4 + threadIdx.x] - b[n4 * 4 + threadIdx.x];
         acc += d * d;
     }
-    block_atomic_sum(acc * scale, out);
+    if constexpr (ORDERED) block_ordered_sum(acc * scale, out, ws);
+    else block_atomic_sum(acc * scale, out);
 }
 
 // loss += mean((a-b)^2), g = 2 (a-b) / n  (torch.nn.MSELoss forward + backward in one pass)
@@ -254,8 +289,20 @@ extern "C" int dlwp_sqerr_sum(const float* a, const float* b, long long n, float
                               void* stream) {
     DLWP_REQUIRE(a && b && loss_out && n >= 0, DLWP_E_INVALID, "sqerr_sum: NULL argument");
     if (n == 0) return DLWP_OK;
-    hipLaunchKernelGGL(sqerr_kernel, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, n,
-                       scale, loss_out);
+    hipLaunchKernelGGL(sqerr_kernel<false>, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, n,
+                       scale, loss_out, (float*)nullptr);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+// dlwp_sqerr_sum with a run-to-run reproducible result: the workgroups' partials are added in workgroup order (ws:
+// DLWP_SQERR_WS_FLOATS floats owned by the caller, zeroed once; one call at a time per ws)
+int dlwp_sqerr_sum_ordered(const float* a, const float* b, long long n, float scale, float* loss_out, float* ws,
+                           hipStream_t stream) {
+    DLWP_REQUIRE(a && b && loss_out && ws && n >= 0, DLWP_E_INVALID, "sqerr_sum_ordered: NULL argument");
+    if (n == 0) return DLWP_OK;
+    static_assert(DLWP_SQERR_MAX_WGS == 2048, "stream_grid() caps the grid at 2048 workgroups");
+    hipLaunchKernelGGL(sqerr_kernel<true>, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, stream, a, b, n, scale, loss_out, ws);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }

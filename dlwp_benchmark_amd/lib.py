@@ -40,6 +40,11 @@ class GraphWideOperand(C.Structure):
                 + [(n, C.c_void_p) for n in ("x", "vs", "vd", "src", "dst")] + [(n, C.c_int) for n in ("D0", "D1", "D2")])
 
 
+class WbChannel(C.Structure):
+    """dlwp_wb_channel (include/dlwpmi.h)"""
+    _fields_ = [("base", C.c_void_p), ("mean", C.c_float), ("std", C.c_float), ("normalize", C.c_int)]
+
+
 GRAPH_MAX_WIDTH, GRAPH_MAX_HIDDEN_LAYERS = 128, 3      # DLWP_GRAPH_MAX_WIDTH, DLWP_GRAPH_MAX_HIDDEN_LAYERS
 GRAPH_ROWS, GRAPH_EDGE, GRAPH_NODE = 0, 1, 2
 GRAPH_ACT = {"relu": 0, "silu": 1}      # DLWP_GRAPH_ACT_RELU, DLWP_GRAPH_ACT_SILU
@@ -267,6 +272,8 @@ SIGNATURES = {
     "dlwp_graph_wide_dgrad": (_I, [C.POINTER(GraphWideOperand)] + [_V] * 4 + [_I] + [_V] * 3 + [_I, _V]),
     "dlwp_graph_wide_gather_sum": (_I, [_V, _V, _V, _I, _V, _V, _I, _I, _I, _I, _V]),
     "dlwp_graph_wide_edge_gather": (_I, [_V] * 5 + [_I] * 4 + [_V]),
+    "dlwp_ns_batch": (_I, [_V, _I, _I, _L, _V, _I, _I, _F, C.c_ulonglong, _I, _V, _V, _V]),
+    "dlwp_wb_batch": (_I, [_V, _I, _I, _I, _V, _I, _I, _I, _I, _L, _F, C.c_ulonglong, _I, _V, _V, _V, _V, _V]),
     "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),
     "dlwp_debug_null_kernels": (_I, [_I, _I, _V]),
     "dlwp_debug_spin_kernels": (_I, [_I, _I, _I, _I, _I, _V]),

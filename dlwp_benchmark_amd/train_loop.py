@@ -164,10 +164,14 @@ def validation_mse(model, u_val, sequence_length, batch_size, teacher_forcing_st
 
 def train_ns(model, u_train, u_val, name="model", epochs=10, batch_size=4, sequence_length=21, learning_rate=1e-3,
              teacher_forcing_steps=10, val_teacher_forcing_steps=None, noise=0.0, clip_gradients=False, seed=1234,
-             out_dir="outputs", save_model=True, continue_training=False, verbose=False, log_scalars=True, stop_epoch=None):
+             out_dir="outputs", save_model=True, continue_training=False, verbose=False, log_scalars=True, stop_epoch=None,
+             device_data=False):
     """Train an nsbench FNO-family module (anything with make_optimizer / train_step) on trajectories u [N, T, D, H, W].
     Returns a list of per-epoch dicts(epoch, lr, train_mse, val_mse).  stop_epoch: leave after that many epochs of the
-    `epochs`-long schedule with a `_last` checkpoint written (a long run split over several processes: continue_training)."""
+    `epochs`-long schedule with a `_last` checkpoint written (a long run split over several processes: continue_training).
+    device_data: keep u_train / u_val on the device and assemble every batch there with one launch (device_data.py), written
+    into the model's io_buffers() where it has them; same samples and crops, and with noise == 0 the same bits, as the host
+    path; with noise > 0 the perturbation comes from the device path's own seeded stream."""
     device = next(model.parameters()).device
     rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
     world = torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1
@@ -187,15 +191,29 @@ def train_ns(model, u_train, u_val, name="model", epochs=10, batch_size=4, seque
             ddp.broadcast_parameters(buf, src=0)
     vtf = teacher_forcing_steps if val_teacher_forcing_steps is None else val_teacher_forcing_steps
     log = []
+    resident = None
+    if device_data:
+        from .device_data import DeviceTrajectories
+        resident = DeviceTrajectories(u_train, sequence_length, noise=noise, seed=seed, device=device)
+        u_val = torch.as_tensor(u_val).to(device)          # validation slices the resident tensor
     writer = ScalarLog(out_dir, name, enabled=log_scalars and save_model and rank == 0)
     for epoch in range(epoch0, epochs):
         opt.lr = cosine_lr(learning_rate, epoch, epochs)
         writer.add_scalar("Epoch", epoch, iteration)
         writer.add_scalar("Learning Rate", opt.lr, iteration)
         losses = []
-        for idx in ddp.shard_indices(u_train.shape[0], epoch, rank, world, batch_size, seed):
-            xs, ys = zip(*(ddp.ns_sample(u_train, int(i), epoch, sequence_length, noise, seed) for i in idx))
-            x, y = torch.stack(xs).to(device), torch.stack(ys).to(device)
+        if resident is not None:
+            batches = resident.epoch_table(epoch, rank, world, batch_size)      # [n_iters, B, 2] on the device, one copy
+        else:
+            batches = ddp.shard_indices(u_train.shape[0], epoch, rank, world, batch_size, seed)
+        for idx in batches:
+            if resident is not None:
+                out = (model.io_buffers(batch_size, sequence_length - 1, *u_train.shape[-2:], teacher_forcing_steps)
+                       if hasattr(model, "io_buffers") else None)
+                x, y = resident.batch(idx, epoch, out=out)
+            else:
+                xs, ys = zip(*(ddp.ns_sample(u_train, int(i), epoch, sequence_length, noise, seed) for i in idx))
+                x, y = torch.stack(xs).to(device), torch.stack(ys).to(device)
             loss = model.train_step(x, y, teacher_forcing_steps, optimizer=opt, grad_scale=1.0 / world, allreduce=reducer,
                                     clip_max_norm=opt.lr if clip_gradients else None)     # clip threshold = lr (:123-125)
             losses.append(loss.clone())   # the step returns its persistent loss buffer; clones stay on the device (no sync)
@@ -223,14 +241,19 @@ def train_ns(model, u_train, u_val, name="model", epochs=10, batch_size=4, seque
 
 
 @torch.no_grad()
-def validation_mse_dlwp(model, dataset, batch_size, device):
-    """dlwpbench/scripts/train.py:236-252: MSE over the concatenated outputs of every validation sample."""
+def validation_mse_dlwp(model, dataset, batch_size, device, resident=None):
+    """dlwpbench/scripts/train.py:236-252: MSE over the concatenated outputs of every validation sample.  resident: the
+    dataset's device_data.DeviceWeatherBench -- the batches are then assembled on the device."""
     from . import wbdata
     tot, cnt = 0.0, 0
     was_training = model.training
     model.eval()
     for i0 in range(0, len(dataset), batch_size):
-        c, p, g, t = wbdata.to_device_batch([dataset[i] for i in range(i0, min(i0 + batch_size, len(dataset)))], device)
+        items = range(i0, min(i0 + batch_size, len(dataset)))
+        if resident is not None:
+            c, p, g, t = resident.batch(list(items), getattr(dataset, "epoch", 0))
+        else:
+            c, p, g, t = wbdata.to_device_batch([dataset[i] for i in items], device)
         y_hat = model(constants=c, prescribed=p, prognostic=g)
         B, T, D, H, W = y_hat.shape
         m = error_moments(y_hat.reshape(B, T, D * H, W), t.reshape(B, T, D * H, W))
@@ -242,14 +265,17 @@ def validation_mse_dlwp(model, dataset, batch_size, device):
 
 def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch_size=4, learning_rate=1e-3,
                clip_gradients=False, gradient_accumulation_steps=1, seed=1234, out_dir="outputs", save_model=True,
-               use_graph=True, verbose=False, continue_training=False, log_scalars=True):
+               use_graph=True, verbose=False, continue_training=False, log_scalars=True, device_data=False):
     """The dlwpbench training script's epoch loop (src/dlwpbench/scripts/train.py:104-197) around the captured step of
     train_engine.GraphedTrainStep, for any dlwpbench module (forward(constants, prescribed, prognostic)): batches of
     `WeatherBenchDataset.__getitem__` tuples (wbdata.WeatherBenchArrays) from the seeded rank-sharded permutation, MSE,
     Adam with the cosine schedule stepped per epoch (:194), optional clipping at max_norm = current learning rate
     (:230-232), micro-batch gradient accumulation (:206-233), validation without gradients, the `_last` / `_best` checkpoint
     policy (:255-266).  One process per GPU; with
-    torch.distributed initialised the flat gradient is all-reduced once per step.  Returns per-epoch dicts."""
+    torch.distributed initialised the flat gradient is all-reduced once per step.  Returns per-epoch dicts.
+    device_data: upload both datasets once and assemble every batch on the device with one launch (device_data.py) instead of
+    `__getitem__` + collate + four copies; same items, and with noise == 0 the same bits; with noise > 0 the perturbation
+    comes from the device path's own seeded stream (the dataset then needs a seed)."""
     from . import wbdata
     from .train_engine import GraphedTrainStep
     # micro-batches as in the reference (:206-233): split_size = max(1, batch // steps); every micro-batch's mean loss is
@@ -272,6 +298,10 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
     def kwargs_of(c, p, g):
         return {k: v for k, v in (("constants", c), ("prescribed", p), ("prognostic", g)) if v is not None}
 
+    res_train = res_val = None
+    if device_data:
+        from .device_data import DeviceWeatherBench
+        res_train, res_val = DeviceWeatherBench(train_dataset, device), DeviceWeatherBench(val_dataset, device)
     writer = ScalarLog(out_dir, name, enabled=log_scalars and save_model and rank == 0)
     for epoch in range(epoch0, epochs):
         lr = cosine_lr(learning_rate, epoch, epochs)
@@ -280,8 +310,15 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
         losses = []
         if hasattr(train_dataset, "set_epoch"):
             train_dataset.set_epoch(epoch)
-        for idx in wbdata.shard_batches(train_dataset, epoch, rank, world, batch_size, seed):
-            c, p, g, t = wbdata.to_device_batch([train_dataset[int(i)] for i in idx], device)
+        if res_train is not None:
+            batches = res_train.epoch_table(epoch, rank, world, batch_size, seed)      # [n_iters, B] on the device, one copy
+        else:
+            batches = wbdata.shard_batches(train_dataset, epoch, rank, world, batch_size, seed)
+        for idx in batches:
+            if res_train is not None:
+                c, p, g, t = res_train.batch(idx, epoch)
+            else:
+                c, p, g, t = wbdata.to_device_batch([train_dataset[int(i)] for i in idx], device)
             sl = lambda v, i: None if v is None else v[i:i + micro]      # noqa: E731
             if step is None:
                 step = GraphedTrainStep(model, kwargs_of(sl(c, 0), sl(p, 0), sl(g, 0)), t[:micro], lr=lr, allreduce=reducer,
@@ -308,7 +345,7 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
             writer.add_scalar("MSE/training", losses[-1], iteration)
             iteration += 1
         train_mse = torch.stack(losses).mean().item() if losses else float("nan")
-        val_mse = validation_mse_dlwp(model, val_dataset, batch_size, device)
+        val_mse = validation_mse_dlwp(model, val_dataset, batch_size, device, resident=res_val)
         writer.add_scalar("MSE/validation", val_mse, iteration)
         writer.flush()
         if save_model and rank == 0 and step is not None:

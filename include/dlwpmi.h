@@ -1314,6 +1314,31 @@ int dlwp_graph_wide_gather_sum(const float* in, const int* ptr, const int* eid, 
 int dlwp_graph_wide_edge_gather(const float* in, const int* dst, const int* in_ptr, const float* add, float* out, int B, int N,
                                 int E, int C, void* stream);
 
+/* ---- training batches assembled on the device from resident datasets (csrc/batch_ops.hip, docs/kernels/data.md).        */
+/* One launch per batch on the caller's stream; pure data movement (no atomics, no LDS), so two calls give the same bits.  */
+/* A table row whose sample or window lies outside the resident data writes nothing for that row and reads nothing.        */
+/* noise > 0 adds noise * z with z from the library's own counter-based stream (Philox4x32-10, counter                     */
+/* (e >> 2, item, epoch, tag), key = the two halves of seed): the noise of a sample depends on (seed, epoch, item, element */
+/* e inside the sample) only, never on the batch.  noise == 0 copies (or normalises) exactly and draws nothing.            */
+#define DLWP_BATCH_TAG_NS 0x6e73u /* Philox counter word 3 of dlwp_ns_batch */
+#define DLWP_BATCH_TAG_WB 0x7762u /* ... of dlwp_wb_batch */
+/* u [N][T][F] (F = D H W floats per frame); table [B][2] int32 (sample i, crop start r);                                  */
+/* x [B][L-1][F] = u[i][r .. r+L-2] (+ noise z), y [B][L-1][F] = u[i][r+1 .. r+L-1]; every source frame is read once.      */
+int dlwp_ns_batch(const float* u, int N, int T, long long F, const int* table, int B, int L, float noise,
+                  unsigned long long seed, int epoch, float* x, float* y, void* stream);
+typedef struct {
+    const float* base; /* [n_time][P] series, or [P] for a constant */
+    float mean, std;
+    int normalize;     /* != 0: (a - mean) / std in fp32, correctly rounded */
+} dlwp_wb_channel;
+/* chan: DEVICE array of nC constants, then nP prescribed, then nG prognostic channels; items [B] int32, t0 = item * L.    */
+/* constants [B][1][nC][P]; prescribed [B][L][nP][P] from frames t0 .. t0+L-1; prognostic [B][L][nG][P] from the same      */
+/* frames (+ noise z); target [B][L-context][nG][P] from frames t0+1+context .. t0+L.  The outputs of a group without      */
+/* channels may be NULL and are not written.  An item is valid while 0 <= item and t0 + L + 1 <= n_time.                   */
+int dlwp_wb_batch(const dlwp_wb_channel* chan, int nC, int nP, int nG, const int* items, int B, int L, int context, int n_time,
+                  long long P, float noise, unsigned long long seed, int epoch, float* constants, float* prescribed,
+                  float* prognostic, float* target, void* stream);
+
 /* bench probe: ONE forward `spatial` launch of an inner FNO block as the rollout issues it     */
 /* (x = previous pre-activation, GELU on load; spec = [B][m1][m2c][C][2] mixed modes; fused      */
 /* W-axis DFT of gelu(pre) into x1_out [B][H][m2c][C][2]).                                       */
