@@ -83,6 +83,19 @@ class DeviceTrajectories:
         self.device = torch.device(device)
         self.u = u.to(self.device).contiguous()          # the one upload
 
+    @classmethod
+    def generate(cls, sequence_length, noise=0.0, seed=1234, device="cuda", **generate_data_kwargs):
+        """Trajectories generated on the device and wrapped where they lie: nsdata.generate_data(rng="philox", solver="kernels",
+        to_device=True, seed=seed, device=device, **generate_data_kwargs) -- no file, no host copy, no upload.  The one seed names
+        the dataset (Philox tag of dlwp_ns2d_grf) and keys the batch noise (tag of dlwp_ns_batch): two streams.  `.u` is the tensor
+        generate_data returned; train_ns(model, d.u[:k], d.u[k:], device_data=True) trains on it."""
+        from . import nsdata
+        for fixed in ("rng", "solver", "to_device", "seed", "device"):
+            if fixed in generate_data_kwargs:
+                raise ValueError(f"DeviceTrajectories.generate sets {fixed} itself")
+        data = nsdata.generate_data(rng="philox", solver="kernels", to_device=True, seed=seed, device=device, **generate_data_kwargs)
+        return cls(data["u"], sequence_length, noise=noise, seed=seed, device=data["u"].device)
+
     def upload(self, table):
         """A host table [..., 2] of (sample index, crop start) rows -> validated, int32, on the device (one copy)."""
         t = validate_ns_table(table, self.shape[0], self.shape[1], self.sequence_length)

@@ -274,6 +274,10 @@ SIGNATURES = {
     "dlwp_graph_wide_edge_gather": (_I, [_V] * 5 + [_I] * 4 + [_V]),
     "dlwp_ns_batch": (_I, [_V, _I, _I, _L, _V, _I, _I, _F, C.c_ulonglong, _I, _V, _V, _V]),
     "dlwp_wb_batch": (_I, [_V, _I, _I, _I, _V, _I, _I, _I, _I, _L, _F, C.c_ulonglong, _I, _V, _V, _V, _V, _V]),
+    "dlwp_ns2d_grf": (_I, [C.c_ulonglong, _L, _I, _I, _F, _F, _F, _V, _V]),
+    "dlwp_ns2d_spectral_terms": (_I, [_V, _V, _I, _I, _V]),
+    "dlwp_ns2d_advect": (_I, [_V, _V, _I, _I, _V]),
+    "dlwp_ns2d_cn_update": (_I, [_V, _V, _V, _I, _I, _I, _F, _F, _V]),
     "dlwp_fno_mix_fwd_probe":(_I, [_V, _V, _V, _V, _V, _I, _V]),
     "dlwp_debug_null_kernels": (_I, [_I, _I, _V]),
     "dlwp_debug_spin_kernels": (_I, [_I, _I, _I, _I, _I, _V]),

@@ -1339,6 +1339,30 @@ int dlwp_wb_batch(const dlwp_wb_channel* chan, int nC, int nP, int nG, const int
                   long long P, float noise, unsigned long long seed, int epoch, float* constants, float* prescribed,
                   float* prognostic, float* target, void* stream);
 
+/* ---- the Navier-Stokes data generator's point-wise kernels (csrc/ns_solver.hip, docs/kernels/data.md "Navier-Stokes    */
+/* generator"; reference: generate_ns_2d.py:27-130 and random_fields.py:8-64 as nsdata.py restates them).  Complex arrays    */
+/* are interleaved fp32 pairs, 8-byte aligned; the state is the half spectrum [B][n][n/2+1] of an n x n field, n even and   */
+/* >= 4.  Index a stands for the wavenumber a (a < n/2) or a - n, so the Nyquist row and column carry -n/2; k_x runs along   */
+/* the rows, k_y along the columns.  lap = 4 pi^2 (k_x^2 + k_y^2) with lap[0][0] = 1.  No tables, no atomics, one writer    */
+/* per output element: every launch gives the same bits, whatever the batch a sample travels in.                            */
+#define DLWP_NS2D_TAG_GRF 0x6772u /* Philox counter word 3 of dlwp_ns2d_grf */
+/* H [B][n][n/2+1]: half spectrum of the initial vorticity of the samples first_sample .. first_sample + B - 1.             */
+/*   c[a][b] = sqrt_eig[a][b] (z[2 (a n + b)] + i z[2 (a n + b) + 1]),                                                       */
+/*   sqrt_eig = n^2 sqrt(2) sigma (lap + tau^2)^(-alpha / 2), sqrt_eig[0][0] = 0 (here lap[0][0] = 0),                       */
+/*   z[e] the normal of element e of the sample under counter (e >> 2, sample, 0, DLWP_NS2D_TAG_GRF), key = seed;           */
+/*   H[a][b] = (c[a][b] + conj(c[(n - a) % n][(n - b) % n])) / 2, whose irfft2 (norm "backward") is Re(ifft2(c)).           */
+int dlwp_ns2d_grf(unsigned long long seed, long long first_sample, int B, int n, float alpha, float tau, float sigma, float* H,
+                  void* stream);
+/* out [B][4][n][n/2+1] = i k_y psi, -i k_x psi, i k_x w, i k_y w with psi = w_h / lap and each k times 2 pi: the spectra    */
+/* of the velocity components and the vorticity gradients, in the layout one channels-first dlwp_irfft2 reads.              */
+int dlwp_ns2d_spectral_terms(const float* w_h, float* out, int B, int n, void* stream);
+/* out [B][n][n] = q w_x + v w_y of fields [B][4][n][n] = (q, v, w_x, w_y).                                                  */
+int dlwp_ns2d_advect(const float* fields, float* out, int B, int n, void* stream);
+/* w_h <- (-dt D F_h + dt f_h + (1 - dt visc lap / 2) w_h) / (1 + dt visc lap / 2) in place, D = 1 where 3 |k_x| <= n and     */
+/* 3 |k_y| <= n, else 0 (the 2/3 rule).  f_h is [n][n/2+1], or [B][n][n/2+1] when f_batched != 0.                            */
+int dlwp_ns2d_cn_update(float* w_h, const float* F_h, const float* f_h, int f_batched, int B, int n, float dt, float visc,
+                        void* stream);
+
 /* bench probe: ONE forward `spatial` launch of an inner FNO block as the rollout issues it     */
 /* (x = previous pre-activation, GELU on load; spec = [B][m1][m2c][C][2] mixed modes; fused      */
 /* W-axis DFT of gelu(pre) into x1_out [B][H][m2c][C][2]).                                       */
