@@ -56,12 +56,17 @@ def ns_metrics(outputs, targets, teacher_forcing_steps):
 
 
 @torch.no_grad()
-def evaluate_ns(model, batches, teacher_forcing_steps):
-    """evaluate_model (:26-85) without the NetCDF detour: rollout every (x, y) batch, accumulate the moments on device."""
-    tot, shape = None, None
+def evaluate_ns(model, batches, teacher_forcing_steps, spectra=False):
+    """evaluate_model (:26-85) without the NetCDF detour: rollout every (x, y) batch, accumulate the moments on device.
+    spectra=True adds "spectra": `spectra.spectral_metrics` of the shell-binned spectra E(k) of outputs and targets
+    (`spectra.plane_spectra`) and the raw tables under "tables"."""
+    tot, shape, sparts = None, None, []
     for x, y in batches:
         y_hat = model(x, teacher_forcing_steps)
         B, T, D, H, W = y_hat.shape
+        if spectra:
+            from . import spectra as S
+            sparts.append({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in S.plane_spectra(y_hat, y).items()})
         m = error_moments(y_hat.reshape(B, T, D * H, W), y.reshape(B, T, D * H, W))
         tot = m if tot is None else tot + m
         shape = (shape[0] + B, T, D, H, W) if shape else (B, T, D, H, W)
@@ -72,6 +77,11 @@ def evaluate_ns(model, batches, teacher_forcing_steps):
         cnt = max(b - a, 0) * n
         out["rmse" + tag] = math.sqrt(m[0, a:b].sum().item() / cnt) if cnt else float("nan")
         out["frob" + tag] = (m[1, a:b] / n).sum().item()
+    if spectra:
+        from . import spectra as S
+        tables = S.concat_spectra(sparts)
+        out["spectra"] = S.spectral_metrics(tables)
+        out["spectra"]["tables"] = tables
     return out
 
 
@@ -339,7 +349,7 @@ def regular_latitudes(H):
 
 @torch.no_grad()
 def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, climatology=None, window_days=(334, 365), lats_deg=None,
-                  device=None):
+                  device=None, spectra=False, spectra_grid="midpoint"):
     """evaluate_model + compute_metrics (scripts/evaluate.py:112-234, 494-588) without the NetCDF detour, batch by batch, with nothing
     but the diagnostic tables leaving the device.
 
@@ -349,6 +359,9 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
               23-28) or "climatology" (needs `climatology`; the model is not called).
     remap     an hpx_remap.HEALPixRemap for the models on the HEALPix mesh: scored on its lat-lon grid.
     climatology [12, V, H, W] monthly maps in physical units (`monthly_climatology`): enables the ACC.
+    spectra   True: also the power per spherical-harmonic degree of outputs and targets (`spectra.sphere_spectra` on `spectra_grid`,
+              for HPX models on the remap's lat-lon grid): "spectra" holds `spectra.spectral_metrics` in physical units, over all lead
+              times and over the window, and the raw tables under "tables".
     Returns rmse [T, V] (acc [T, V]), rmse_global / rmse_trade_winds / rmse_south_westerlies / rmse_window [V], "window", "diag"."""
     if forecast not in ("model", "persistence", "climatology"):
         raise ValueError(f"forecast must be 'model', 'persistence' or 'climatology', not {forecast!r}")
@@ -359,7 +372,7 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
     from . import wbdata
     device = device if device is not None else (climatology.device if climatology is not None else next(model.parameters()).device)
     scale, shift = dataset_scale_shift(dataset)
-    parts, lats, window = [], None, None
+    parts, sparts, lats, window = [], [], None, None
     for i0 in range(0, len(dataset), int(batch_size)):
         items = list(range(i0, min(i0 + int(batch_size), len(dataset))))
         constants, prescribed, prognostic, target = wbdata.to_device_batch([dataset[i] for i in items], device)
@@ -380,8 +393,17 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
         d = rollout_diagnostics(out, target, scale=scale, shift=shift, lats_deg=lats, remap=remap, climatology=climatology,
                                 months=months, window=window)
         parts.append({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in d.items()})
+        if spectra:
+            from . import spectra as S
+            sp = S.sphere_spectra(out, target, grid=spectra_grid, remap=remap)
+            sparts.append({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in sp.items()})
     diag = concat_diagnostics(parts)
     res = diag_metrics(diag)
     res.update(physical_soundness(diag, lats, window[1] - window[0]))
     res["window"], res["diag"] = window, diag
+    if spectra:
+        from . import spectra as S
+        tables = S.concat_spectra(sparts)
+        res["spectra"] = S.spectral_metrics(tables, scale=scale, shift=shift, window=window if window[1] > window[0] else None)
+        res["spectra"]["tables"] = tables
     return res

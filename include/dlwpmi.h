@@ -653,6 +653,34 @@ int dlwp_rollout_diag(const float* out, long long out_bstride, long long out_tst
 /* n, no atomics; an empty group gives count 0 and a zero row.  G <= 64.                                                              */
 int dlwp_group_mean(const float* frames, const int* group, float* mean, int* count, long long N, long long P, int G,
                     void* stream);
+/* Power spectra of forecast and target per lead time (csrc/spectra.hip; the reference has none: tests/spectra_ref.py defines them).     */
+/* Sphere: out / target as dlwp_rollout_diag takes them ([Bc][Tc][V][H][W], or [Bc][Tc][V][12][n][n] with the hpx2ll table idx / w,   */
+/* analysed on the table's H x W grid; out with free element strides >= 0 or NULL: the targets alone, power[0] and cross are zero).   */
+/*   F  [2 M][W] : rows 2 m, 2 m + 1 = (2 pi / W) cos, -(2 pi / W) sin of 2 pi m n / W                                                  */
+/*   Wf [M][L][H]: orthonormal associated Legendre functions P~_l^m(cos theta_k) times the quadrature weight of row k                  */
+/*              (both built in float64 and rounded once by the caller: the kernel is grid-agnostic).  L <= H <= 256, M <= W / 2,       */
+/*              W <= 512 (the Nyquist order is left out).                                                                               */
+/*   power [2][Bc][T][V][L]: P_l = (1 / 4 pi) sum_m c_m |a_lm|^2 of out (0) and target (1), c_0 = 1, c_m = 2, in NORMALISED units       */
+/*   cross [Bc][T][V][L]   : (1 / 4 pi) sum_m c_m Re(a_lm^out conj a_lm^target)                                                         */
+/*   a00   [2][Bc][T][V]   : Re a_00 (a per-variable shift moves degree 0 only: the host applies it there)                              */
+/*   ws    : dlwp_sphere_spectra_ws_floats(Bc, Tc, V, H, W, L, M, n) floats (n = 0: lat-lon)                                            */
+/* All three are WRITTEN for the chunk's frames t_begin .. t_begin + Tc - 1 of T.  No atomics, one writer per address, a summation      */
+/* order that depends on (H, W, L, M, mesh) only: two runs, and time / batch chunks, give the same bits.  No a_lm and no lat-lon tensor */
+/* is written to memory.  Knobs: SPEC_MB / SPEC_RB (orders / rows per block), SPEC_HPX (0 auto, 1 LDS-staged planes, 2 direct).          */
+long long dlwp_sphere_spectra_ws_floats(int Bc, int Tc, int V, int H, int W, int L, int M, int n);
+int dlwp_sphere_spectra(const float* out, long long out_bstride, long long out_tstride, const float* target, const float* F,
+                        const float* Wf, const int* idx, const float* w, int n, int Bc, int Tc, int V, int H, int W, int L, int M,
+                        int t_begin, int T, float* power, float* cross, float* a00, float* ws, void* stream);
+/* Plane: the shell-binned spectrum of doubly periodic fields out / target [Bc][Tc][D][H][W] (out as above), through dlwp_rfft2           */
+/* (channels-first, norm "backward"; `plan` made for H x W is the caller's precondition) into ws and one binning pass.  Shell k is the   */
+/* CSR list rowptr [K + 1] / entry [nnz] (index into the half spectrum [H][W/2+1], 0 <= entry < H (W/2+1)) / weight [nnz] (c = 1 on the */
+/* self-conjugate columns, 2 otherwise), summed in list order:                                                                          */
+/*   power [2][Bc][T][D][K]: E(k) = sum c |u|^2 / (H W)^2;  cross [Bc][T][D][K]: sum c Re(u^out conj u^target) / (H W)^2                 */
+/*   ws    : dlwp_plane_spectra_ws_floats(Bc, Tc, D, H, W) floats (the half spectra of one chunk)                                        */
+long long dlwp_plane_spectra_ws_floats(int Bc, int Tc, int D, int H, int W);
+int dlwp_plane_spectra(const dlwp_fft_plan* plan, const float* out, long long out_bstride, long long out_tstride, const float* target,
+                       const int* rowptr, const int* entry, const float* weight, int K, int nnz, int Bc, int Tc, int D, int H, int W,
+                       int t_begin, int T, float* power, float* cross, float* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Token-level building blocks of the AFNO / Swin / Pangu blocks (nn.Linear, nn.LayerNorm, */
