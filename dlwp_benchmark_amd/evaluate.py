@@ -18,6 +18,10 @@ interpolation to lat-lon all happen inside the kernel) and leaves three small ta
 over a window of lead times -- from which `diag_metrics` (the dictionary of `dlwp_metrics`) and `physical_soundness` are finished on
 the host in float64.  `evaluate_dlwp` is the driver beside `evaluate_ns`; `persistence_forecast` and `forecast="climatology"` are
 the two baselines, `monthly_climatology` (dlwp_group_mean) the climatology itself.
+
+Ensembles (`ensemble=M` of both drivers, off by default): the initial state is perturbed into M seeded members, the members run
+through the model folded into the batch axis and are scored as a distribution -- CRPS, spread-skill ratio, rank histogram
+(dlwp_benchmark_amd/ensemble.py); every deterministic key is computed from member 0.
 """
 import math
 
@@ -55,14 +59,47 @@ def ns_metrics(outputs, targets, teacher_forcing_steps):
     return out
 
 
+def _ensemble_args(ensemble, sigma, seed):
+    """(M, sigma, seed) of the drivers' ensemble keywords, validated before the first batch"""
+    from . import ensemble as E
+    M = int(ensemble)
+    if not 2 <= M <= E.MAX_MEMBERS:
+        raise ValueError(f"ensemble = {M} members must lie in 2..{E.MAX_MEMBERS}")
+    sg = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    if not (np.isfinite(sg).all() and (sg >= 0).all()):
+        raise ValueError(f"ensemble_sigma {sg.tolist()} must be finite and not negative")
+    return M, (float(sg[0]) if sg.size == 1 else sg), E._check_seed(float(sg.max()), seed)
+
+
+def _host_tables(d):
+    return {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in d.items()}
+
+
 @torch.no_grad()
-def evaluate_ns(model, batches, teacher_forcing_steps, spectra=False):
+def evaluate_ns(model, batches, teacher_forcing_steps, spectra=False, ensemble=None, ensemble_sigma=0.0, ensemble_seed=None,
+                ensemble_control=True):
     """evaluate_model (:26-85) without the NetCDF detour: rollout every (x, y) batch, accumulate the moments on device.
     spectra=True adds "spectra": `spectra.spectral_metrics` of the shell-binned spectra E(k) of outputs and targets
-    (`spectra.plane_spectra`) and the raw tables under "tables"."""
-    tot, shape, sparts = None, None, []
+    (`spectra.plane_spectra`) and the raw tables under "tables".
+    ensemble=M adds "ensemble": the input x of every sample is perturbed into M members (`ensemble.perturb_members` with
+    `ensemble_sigma`, `ensemble_seed`, `ensemble_control`; the item is the running sample index over `batches`), the members run
+    through the model folded into the batch axis, and `ensemble.ensemble_metrics` of their rollouts is reported per lead time
+    (unweighted, no scale), the raw tables under "tables".  Every other key is computed from member 0."""
+    tot, shape, sparts, eparts, seen = None, None, [], [], 0
+    if ensemble is not None:
+        from . import ensemble as E
+        M, sigma, seed = _ensemble_args(ensemble, ensemble_sigma, ensemble_seed)
     for x, y in batches:
-        y_hat = model(x, teacher_forcing_steps)
+        if ensemble is not None:
+            Bx = x.shape[0]
+            xm = E.perturb_members(x, np.arange(seen, seen + Bx), M, sigma, seed, control=ensemble_control, variables=x.shape[-3])
+            seen += Bx
+            ym = model(xm.reshape(Bx * M, *x.shape[1:]), teacher_forcing_steps)
+            ym = ym.reshape(Bx, M, *ym.shape[1:])
+            eparts.append(_host_tables(E.ensemble_diagnostics(ym, y)))
+            y_hat = ym[:, 0]
+        else:
+            y_hat = model(x, teacher_forcing_steps)
         B, T, D, H, W = y_hat.shape
         if spectra:
             from . import spectra as S
@@ -82,6 +119,10 @@ def evaluate_ns(model, batches, teacher_forcing_steps, spectra=False):
         tables = S.concat_spectra(sparts)
         out["spectra"] = S.spectral_metrics(tables)
         out["spectra"]["tables"] = tables
+    if ensemble is not None:
+        tables = E.concat_ensemble(eparts)
+        out["ensemble"] = E.ensemble_metrics(tables)
+        out["ensemble"]["tables"] = tables
     return out
 
 
@@ -349,7 +390,8 @@ def regular_latitudes(H):
 
 @torch.no_grad()
 def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, climatology=None, window_days=(334, 365), lats_deg=None,
-                  device=None, spectra=False, spectra_grid="midpoint"):
+                  device=None, spectra=False, spectra_grid="midpoint", ensemble=None, ensemble_sigma=0.0, ensemble_seed=None,
+                  ensemble_control=True):
     """evaluate_model + compute_metrics (scripts/evaluate.py:112-234, 494-588) without the NetCDF detour, batch by batch, with nothing
     but the diagnostic tables leaving the device.
 
@@ -362,6 +404,12 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
     spectra   True: also the power per spherical-harmonic degree of outputs and targets (`spectra.sphere_spectra` on `spectra_grid`,
               for HPX models on the remap's lat-lon grid): "spectra" holds `spectra.spectral_metrics` in physical units, over all lead
               times and over the window, and the raw tables under "tables".
+    ensemble  M (2..64; forecast="model" only): `prognostic` of every sample is perturbed into M members (`ensemble.perturb_members`
+              with `ensemble_sigma` -- a scalar or one value per prognostic channel, normalised units --, `ensemble_seed` and
+              `ensemble_control`; the item is the dataset index, so a member does not depend on the batch size), the members run
+              through the model folded into the batch axis (B M samples, constants and prescribed repeated), and "ensemble" holds
+              `ensemble.ensemble_metrics` in physical units with the raw tables under "tables".  Every other key is computed from
+              member 0 (the unperturbed forecast under `ensemble_control`).
     Returns rmse [T, V] (acc [T, V]), rmse_global / rmse_trade_winds / rmse_south_westerlies / rmse_window [V], "window", "diag"."""
     if forecast not in ("model", "persistence", "climatology"):
         raise ValueError(f"forecast must be 'model', 'persistence' or 'climatology', not {forecast!r}")
@@ -369,17 +417,30 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
         raise ValueError("forecast='climatology' needs the climatology")
     if dataset.init_dates is None:
         raise ValueError("evaluate_dlwp iterates the dataset's init_dates branch: construct it with init_dates")
+    if ensemble is not None:
+        if forecast != "model":
+            raise ValueError(f"ensemble needs forecast='model': the {forecast} forecast has no members")
+        from . import ensemble as E
+        M, sigma, seed = _ensemble_args(ensemble, ensemble_sigma, ensemble_seed)
     from . import wbdata
     device = device if device is not None else (climatology.device if climatology is not None else next(model.parameters()).device)
     scale, shift = dataset_scale_shift(dataset)
-    parts, sparts, lats, window = [], [], None, None
+    parts, sparts, eparts, lats, window = [], [], [], None, None
     for i0 in range(0, len(dataset), int(batch_size)):
         items = list(range(i0, min(i0 + int(batch_size), len(dataset))))
         constants, prescribed, prognostic, target = wbdata.to_device_batch([dataset[i] for i in items], device)
         constants = None if constants is None or bool(constants.isnan().any()) else constants
         prescribed = None if prescribed is None or bool(prescribed.isnan().any()) else prescribed
         T = target.shape[1]
-        if forecast == "model":
+        members = None
+        if ensemble is not None:
+            B = prognostic.shape[0]
+            pm = E.perturb_members(prognostic, np.asarray(items), M, sigma, seed, control=ensemble_control, variables=prognostic.shape[2])
+            fold = lambda a: None if a is None else a.repeat_interleave(M, dim=0)      # noqa: E731
+            members = model(constants=fold(constants), prescribed=fold(prescribed), prognostic=pm.reshape(B * M, *prognostic.shape[1:]))
+            members = members.reshape(B, M, *members.shape[1:])
+            out = members[:, 0]
+        elif forecast == "model":
             out = model(constants=constants, prescribed=prescribed, prognostic=prognostic)
         elif forecast == "persistence":
             out = persistence_forecast(prognostic[:, 0], T)
@@ -393,6 +454,8 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
         d = rollout_diagnostics(out, target, scale=scale, shift=shift, lats_deg=lats, remap=remap, climatology=climatology,
                                 months=months, window=window)
         parts.append({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in d.items()})
+        if members is not None:
+            eparts.append(_host_tables(E.ensemble_diagnostics(members, target, lats_deg=lats, remap=remap)))
         if spectra:
             from . import spectra as S
             sp = S.sphere_spectra(out, target, grid=spectra_grid, remap=remap)
@@ -406,4 +469,8 @@ def evaluate_dlwp(model, dataset, batch_size, *, forecast="model", remap=None, c
         tables = S.concat_spectra(sparts)
         res["spectra"] = S.spectral_metrics(tables, scale=scale, shift=shift, window=window if window[1] > window[0] else None)
         res["spectra"]["tables"] = tables
+    if ensemble is not None:
+        tables = E.concat_ensemble(eparts)
+        res["ensemble"] = E.ensemble_metrics(tables, scale=scale)
+        res["ensemble"]["tables"] = tables
     return res

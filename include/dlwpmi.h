@@ -681,6 +681,33 @@ long long dlwp_plane_spectra_ws_floats(int Bc, int Tc, int D, int H, int W);
 int dlwp_plane_spectra(const dlwp_fft_plan* plan, const float* out, long long out_bstride, long long out_tstride, const float* target,
                        const int* rowptr, const int* entry, const float* weight, int K, int nnz, int Bc, int Tc, int D, int H, int W,
                        int t_begin, int T, float* power, float* cross, float* ws, void* stream);
+/* Seeded ensemble forecasts (csrc/ensemble.hip; the reference has none: tests/ens_ref.py defines them).                                */
+/* Perturbation: x [B][F] (one sample's input frames: F = frames x V planes of P floats), items [B] int32, sigma [V] in normalised      */
+/* units -> out [B][M][F], out[b][m][e] = x[b][e] + sigma[(e / P) % V] z with z from the stream of dlwp_ns_batch / dlwp_wb_batch,       */
+/* counter (e >> 2, items[b], m, DLWP_ENS_TAG), key = the two halves of seed: a member depends on (seed, item, member, element) only,   */
+/* never on B, on M or on the call.  control != 0: member 0 is a bit-exact copy and draws nothing.  One launch, pure data movement (no   */
+/* atomics, no LDS), x is read once.  1 <= M <= DLWP_ENS_MAX_MEMBERS, F a multiple of V P.                                               */
+#define DLWP_ENS_TAG 0x656eu /* Philox counter word 3 of dlwp_ens_perturb */
+#define DLWP_ENS_MAX_MEMBERS 64
+int dlwp_ens_perturb(const float* x, const int* items, const float* sigma, int B, long long F, long long P, int V, int M, int control,
+                     unsigned long long seed, float* out, void* stream);
+/* Scores of M members against the target in one read of both, per sample, lead time and variable (NORMALISED values: a shift cancels    */
+/* in every score, the host applies the scale).                                                                                          */
+/*   members  : frame (b, m, t) of variable v starts at members + b bstride + m mstride + t tstride + v H W (element strides >= 0; a     */
+/*              stride of 0 is read in place: an expanded view, the persistence forecast).  target dense [Bc][Tc][V][H][W].               */
+/*   row_weights [H] or NULL.                                                                                                            */
+/*   sums  [Bc][T][V][4]    : sum over pixels of w_h times (mean - y)^2 | sum_i (x_i - mean)^2 / (M - 1) | sum_i |x_i - y| / M |          */
+/*              sum_{i<j} |x_i - x_j| / (M (M - 1)); the fair CRPS is column 2 - column 3                                                 */
+/*   ranks [Bc][T][V][M + 1]: (int32) the unweighted count of pixels with #{i : x_i < y} = k; a tie counts as not below                  */
+/*   ws    : dlwp_ens_diag_ws_floats(Bc, M, Tc, V, H, W) floats (the pixel blocks' partial sums and counts)                              */
+/* Both are WRITTEN for the chunk's frames t_begin .. t_begin + Tc - 1 of T.  2 <= M <= DLWP_ENS_MAX_MEMBERS, H W <= 2^21 (721 x 1440   */
+/* fits).  Mean and variance in two passes over registers, relative to member 0 (no E[x^2] - mean^2); the pair term is the O(M^2) loop.  */
+/* No atomics, one writer per address, a summation order that depends on (H, W, M) only: two runs, and time / batch chunks, give the     */
+/* same bits.  Knob: ENS_BUCKET (0 auto, or 8 / 16 / 32 / 64 members held per thread).                                                    */
+long long dlwp_ens_diag_ws_floats(int Bc, int M, int Tc, int V, int H, int W);
+int dlwp_ens_diag(const float* members, long long bstride, long long mstride, long long tstride, const float* target,
+                  const float* row_weights, int Bc, int M, int Tc, int V, int H, int W, int t_begin, int T, float* sums, int* ranks,
+                  float* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Token-level building blocks of the AFNO / Swin / Pangu blocks (nn.Linear, nn.LayerNorm, */
