@@ -34,10 +34,15 @@
 // over the wave; the four waves in ascending order -> one partial per block in the workspace; ens_fold_kernel adds the blocks in
 // ascending order.  Ranks: per k and bin a wave ballot and its population count, added to a wave-uniform counter per bin (scalar
 // registers); waves and blocks are added as above (integers: exact in any order).
+//
+// ---- dlwp_crps_loss_fwd_bwd -----------------------------------------------------------------------------------------------------------
+// The CRPS of the members as a training loss, with its gradient from the same read (tests/crps_ref.py defines both): the
+// decomposition of dlwp_ens_diag, one partial per block, crps_fold_kernel adds them in a fixed order.  See crps_loss_kernel.
 #include "common.hip.h"
 #include "dlwpmi_internal.h"
 #include "batch_rng.hip.h"
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -230,6 +235,126 @@ int ens_blocks(int H, int W) {
     return (int)((hw + 256LL * ens_ppt(hw) - 1) / (256LL * ens_ppt(hw)));
 }
 
+// the member bucket of dlwp_ens_diag and dlwp_crps_loss_fwd_bwd: the smallest that holds M, or the one the knob forces
+int ens_bucket(const char* who, int M, int* bucket) {
+    const int forced = dlwp_tune_or("ENS_BUCKET", 0);
+    DLWP_REQUIRE(forced == 0 || forced == 8 || forced == 16 || forced == 32 || forced == 64, DLWP_E_INVALID,
+                 "%s: ENS_BUCKET %d is not 0 (auto), 8, 16, 32 or 64", who, forced);
+    DLWP_REQUIRE(forced == 0 || forced >= M, DLWP_E_UNSUPPORTED, "%s: ENS_BUCKET %d cannot hold M %d members", who, forced, M);
+    *bucket = forced ? forced : M <= 8 ? 8 : M <= 16 ? 16 : M <= 32 ? 32 : 64;
+    return DLWP_OK;
+}
+
+struct CrpsArgs {
+    const float *members, *target, *roww, *varw;
+    long long bs, ms, ts, gms;      // gms: the member stride of the dense gradient, Tc V H W
+    int M, Tc, V, W, hw, K, nblk;
+    float invM, cp;                 // the value: 1 / M and lambda / (M (M - 1))
+    double a1, a2;                  // the gradient: 1 / (N M) and lambda / (N M (M - 1))
+    float *grad, *part;             // part [B][Tc][V][nblk]: one weighted pixel sum per block
+};
+
+// One thread per pixel as ens_diag_kernel (same blocks, same K, same member bucket and guards).  For member i the loop over ALL j
+// counts c_i = #{j : x_j < x_i} - #{j : x_j > x_i}: it serves the pair term, sum_{i<j} |x_i - x_j| = sum_i (x_i - x_0) c_i (the c_i
+// add up to 0, so any shift of x is free and x_0 keeps the products small), and it IS the pair term's gradient.  The j loop runs
+// unguarded over chunks of eight held members; the members from M up to the chunk's end are NaN, which compares false both ways.
+// Member i's gradient is formed and stored inside the i loop and never held: lane t writes pixel block + 256 k + t, so a wave
+// writes 256 contiguous bytes per member.  Its bracket sgn(x_i - y) / M - lambda c_i / (M (M - 1)) is made of two integers; the
+// scaling by r_h c_v / N runs in double and is rounded to fp32 once (a handful of operations per member against the 4 M of the
+// count loop), so an element is within one fp32 rounding of the exact gradient.
+template <int MB, bool GRAD>
+__global__ __launch_bounds__(256) void crps_loss_kernel(const CrpsArgs a) {
+    __shared__ float red[4];
+    const int tc = blockIdx.x / a.nblk, blk = blockIdx.x - tc * a.nblk, v = blockIdx.y, b = blockIdx.z;
+    const int lane = lane_id(), wave = wave_id();
+    const long long f = ((long long)b * a.Tc + tc) * a.V + v;
+    const float* mp = a.members + b * a.bs + tc * a.ts + (long long)v * a.hw;
+    const float* tp = a.target + f * a.hw;
+    float* gp = GRAD ? a.grad + (((long long)b * a.M * a.Tc + tc) * a.V + v) * a.hw : nullptr;
+    const float cv = a.varw ? a.varw[v] : 1.f;
+    float acc = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+        const int p = (blk * a.K + k) * 256 + (int)threadIdx.x;
+        const bool ok = p < a.hw;
+        // opaque per round, as in ens_diag_kernel: the member offsets are formed with scalar adds, not hoisted out of the k loop
+        long long ms = a.ms, gms = a.gms;
+        int M = a.M;
+        asm volatile("" : "+s"(ms), "+s"(gms), "+s"(M));
+        float x[MB];
+        const float* q = mp + p;
+#pragma unroll
+        for (int i = 0; i < MB; ++i) {
+            x[i] = i < M ? (ok ? *q : 0.f) : __builtin_nanf("");
+            q += ms;
+        }
+        const float y = ok ? tp[p] : 0.f;
+        const float w = ok ? (a.roww ? a.roww[p / a.W] : 1.f) : 0.f;
+        const double wd = (double)w * (double)cv;      // exact
+        const float x0 = x[0];
+        float sa = 0.f, pair = 0.f;
+        float* gq = GRAD ? gp + p : nullptr;
+        auto member = [&](const float xi) {
+            int c = 0;
+#pragma unroll
+            for (int j0 = 0; j0 < MB; j0 += 8) {
+                if (j0 == 0 || j0 < M) {
+#pragma unroll
+                    for (int j = j0; j < j0 + 8; ++j) c += (x[j] < xi ? 1 : 0) - (x[j] > xi ? 1 : 0);
+                }
+            }
+            sa += fabsf(xi - y);
+            pair = fmaf(xi - x0, (float)c, pair);
+            if constexpr (GRAD) {
+                const int sg = (xi > y ? 1 : 0) - (xi < y ? 1 : 0);      // sgn(0) = 0
+                const float g = (float)(wd * fma(-a.a2, (double)c, (double)sg * a.a1));
+                if (ok) *gq = g;
+                gq += gms;
+            }
+        };
+        if constexpr (MB <= 32) {
+#pragma unroll
+            for (int i = 0; i < MB; ++i)
+                if (i < M) member(x[i]);
+        } else {
+            // 64 x 64 unrolled comparisons are more code than the instruction cache holds, and a rolled loop cannot index the held
+            // array: member i is read a second time (from the cache: the wave has just loaded the line) while x[] serves the j loop
+            const float* q2 = mp + p;
+#pragma unroll 1
+            for (int i = 0; i < M; ++i) {
+                member(ok ? *q2 : 0.f);
+                q2 += ms;
+            }
+        }
+        acc += (w * cv) * fmaf(-a.cp, pair, sa * a.invM);
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) a.part[f * a.nblk + blk] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// loss <- invN times the n block partials: thread t adds the partials t, t + 256, ... in ascending order, then the wave butterfly
+// and the four waves in ascending order (one workgroup: a fixed order for a given n)
+__global__ __launch_bounds__(256) void crps_fold_kernel(const float* __restrict__ part, long long n, float invN, float* loss) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (long long e = threadIdx.x; e < n; e += 256) s += part[e];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if (lane_id() == 0) red[wave_id()] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *loss = (((red[0] + red[1]) + red[2]) + red[3]) * invN;
+}
+
+template <bool GRAD>
+void crps_launch(int bucket, dim3 grid, hipStream_t stream, const CrpsArgs& a) {
+    if (bucket == 8) hipLaunchKernelGGL((crps_loss_kernel<8, GRAD>), grid, dim3(256), 0, stream, a);
+    else if (bucket == 16) hipLaunchKernelGGL((crps_loss_kernel<16, GRAD>), grid, dim3(256), 0, stream, a);
+    else if (bucket == 32) hipLaunchKernelGGL((crps_loss_kernel<32, GRAD>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((crps_loss_kernel<64, GRAD>), grid, dim3(256), 0, stream, a);
+}
+
 }  // namespace
 
 extern "C" int dlwp_ens_perturb(const float* x, const int* items, const float* sigma, int B, long long F, long long P, int V, int M,
@@ -278,11 +403,9 @@ extern "C" int dlwp_ens_diag(const float* members, long long bstride, long long 
                  "ens_diag: negative stride of members (batch %lld, member %lld, time %lld)", bstride, mstride, tstride);
     DLWP_REQUIRE(t_begin >= 0 && (long long)t_begin + Tc <= T, DLWP_E_INVALID, "ens_diag: chunk t_begin %d + Tc %d is outside the rollout T %d",
                  t_begin, Tc, T);
-    const int forced = dlwp_tune_or("ENS_BUCKET", 0);
-    DLWP_REQUIRE(forced == 0 || forced == 8 || forced == 16 || forced == 32 || forced == 64, DLWP_E_INVALID,
-                 "ens_diag: ENS_BUCKET %d is not 0 (auto), 8, 16, 32 or 64", forced);
-    DLWP_REQUIRE(forced == 0 || forced >= M, DLWP_E_UNSUPPORTED, "ens_diag: ENS_BUCKET %d cannot hold M %d members", forced, M);
-    const int bucket = forced ? forced : M <= 8 ? 8 : M <= 16 ? 16 : M <= 32 ? 32 : 64;
+    int bucket;
+    rc = ens_bucket("ens_diag", M, &bucket);
+    if (rc) return rc;
     EnsArgs a;
     a.members = members, a.target = target, a.roww = row_weights, a.bs = bstride, a.ms = mstride, a.ts = tstride;
     a.Bc = Bc, a.M = M, a.Tc = Tc, a.V = V, a.H = H, a.W = W, a.hw = H * W, a.K = ens_ppt(a.hw), a.nblk = ens_blocks(H, W);
@@ -304,6 +427,53 @@ extern "C" int dlwp_ens_diag(const float* members, long long bstride, long long 
     dlwp_prof_scope prof((hipStream_t)stream, 0.0, 4.0 * nf * (a.nblk + 1), "ens_diag_fold");
     hipLaunchKernelGGL(ens_fold_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ws, a.rpart, sums, ranks, nf, Tc,
                        V, M, a.nblk, t_begin, T);
+    DLWP_LAUNCH_CHECK();
+    return DLWP_OK;
+}
+
+extern "C" long long dlwp_crps_loss_ws_floats(int B, int M, int T, int V, int H, int W) {
+    const int rc = ens_check_shape("crps_loss_ws_floats", B, M, T, V, H, W);
+    if (rc) return rc;
+    return (long long)B * T * V * ens_blocks(H, W);      // one weighted pixel sum per block
+}
+
+extern "C" int dlwp_crps_loss_fwd_bwd(const float* members, long long bstride, long long mstride, long long tstride, const float* target,
+                                      const float* row_weights, const float* var_weights, int B, int M, int T, int V, int H, int W,
+                                      float pair_coeff, float* loss_out, float* grad, float* ws, void* stream) {
+    DLWP_REQUIRE(members, DLWP_E_INVALID, "crps_loss: members is NULL");
+    DLWP_REQUIRE(target, DLWP_E_INVALID, "crps_loss: target is NULL");
+    DLWP_REQUIRE(loss_out, DLWP_E_INVALID, "crps_loss: loss_out is NULL");
+    DLWP_REQUIRE(ws, DLWP_E_INVALID, "crps_loss: ws is NULL (dlwp_crps_loss_ws_floats gives its size)");
+    int rc = ens_check_shape("crps_loss", B, M, T, V, H, W);
+    if (rc) return rc;
+    DLWP_REQUIRE(bstride >= 0 && mstride >= 0 && tstride >= 0, DLWP_E_INVALID,
+                 "crps_loss: negative stride of members (batch %lld, member %lld, time %lld)", bstride, mstride, tstride);
+    DLWP_REQUIRE(std::isfinite(pair_coeff) && pair_coeff >= 0.f && pair_coeff <= 1.f, DLWP_E_INVALID,
+                 "crps_loss: pair_coeff %g must be finite and lie in [0, 1]", (double)pair_coeff);
+    int bucket;
+    rc = ens_bucket("crps_loss", M, &bucket);
+    if (rc) return rc;
+    CrpsArgs a;
+    a.members = members, a.target = target, a.roww = row_weights, a.varw = var_weights, a.bs = bstride, a.ms = mstride, a.ts = tstride;
+    a.M = M, a.Tc = T, a.V = V, a.W = W, a.hw = H * W, a.K = ens_ppt(a.hw), a.nblk = ens_blocks(H, W);
+    DLWP_REQUIRE((long long)T * a.nblk <= INT_MAX, DLWP_E_UNSUPPORTED, "crps_loss: T %d x %d pixel blocks are too many workgroups", T, a.nblk);
+    const long long fields = (long long)B * T * V;
+    const double N = (double)fields * a.hw;
+    a.gms = (long long)T * V * a.hw;
+    a.invM = 1.f / (float)M, a.cp = (float)((double)pair_coeff / ((double)M * (M - 1)));
+    a.a1 = 1.0 / (N * M), a.a2 = (double)pair_coeff / (N * M * (M - 1));
+    a.grad = grad, a.part = ws;
+    {
+        dlwp_prof_scope prof((hipStream_t)stream, 0.0, 4.0 * (double)fields * a.hw * (M + 1 + (grad ? M : 0)), "crps_loss_%s_m%d",
+                             grad ? "fwd_bwd" : "fwd", bucket);
+        const dim3 grid((unsigned)(T * a.nblk), V, B);
+        if (grad) crps_launch<true>(bucket, grid, (hipStream_t)stream, a);
+        else crps_launch<false>(bucket, grid, (hipStream_t)stream, a);
+        DLWP_LAUNCH_CHECK();
+    }
+    const long long n = fields * a.nblk;
+    dlwp_prof_scope prof((hipStream_t)stream, 0.0, 4.0 * (double)(n + 1), "crps_loss_fold");
+    hipLaunchKernelGGL(crps_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, n, (float)(1.0 / N), loss_out);
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }

@@ -8,7 +8,13 @@ variable): four weighted pixel sums -- squared error of the ensemble mean, ensem
 mean absolute difference of member pairs -- and the rank counts.  `ensemble_metrics` finishes on the host in float64: RMSE of the
 mean, spread, spread-skill ratio, CRPS (fair and ensemble estimator) and the rank histogram.  `evaluate.evaluate_dlwp` /
 `evaluate_ns` drive them with `ensemble=M`.
+
+`crps_loss` / `crps_loss_and_grad` / `CrpsLoss` are the CRPS of the members as a training loss (dlwp_crps_loss_fwd_bwd: value and
+gradient from one read of the members; the restatement tests/crps_ref.py defines them); `train_engine.GraphedTrainStep(loss=)` and
+`train_loop.train_dlwp(loss="crps")` train on it.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -27,6 +33,12 @@ def _check_seed(sigma_max, seed):
     return seed
 
 
+@functools.lru_cache(maxsize=16)
+def _device_floats(values, device):
+    """a small fp32 table (sigmas, weights) on the device, uploaded once per distinct content: a training step repeats its call"""
+    return torch.tensor(values, dtype=torch.float64).float().to(device)
+
+
 def _layout(x, variables):
     """(V, P): the variable count and the plane size of x [B, ..., V, H, W] or [B, ..., V, 12, n, n]"""
     s = tuple(x.shape)
@@ -43,7 +55,7 @@ def _layout(x, variables):
     raise ValueError(f"x {s} has no axis of {V} variables in front of its [H, W] or [12, n, n] planes")
 
 
-def perturb_members(x, items, members, sigma, seed, control=True, variables=None):
+def perturb_members(x, items, members, sigma, seed, control=True, variables=None, validate_items=True):
     """x [B, ..., V, H, W] or [B, ..., V, 12, n, n] (one sample's input frames per row, NORMALISED, on the GPU) -> [B, M, ...]:
     member m of sample b is x[b] + sigma_v z with z the standard normals of (seed, items[b], m, element).
 
@@ -53,7 +65,9 @@ def perturb_members(x, items, members, sigma, seed, control=True, variables=None
     seed      0 <= seed < 2^64; needed when any sigma > 0.
     control   True: member 0 is a bit-exact copy of x and draws nothing.
     variables the size of the variable axis when the trailing axes are ambiguous (default: [..., V, 12, n, n] when they fit, else
-              [..., V, H, W])."""
+              [..., V, H, W]).
+    validate_items  False: `items` is an int32 [B] tensor on x's device whose values the caller vouches for (a row of
+              `DeviceWeatherBench.epoch_table`); the kernel reads it in place -- no copy to the host, no synchronisation."""
     M = int(members)
     if not 1 <= M <= MAX_MEMBERS:
         raise ValueError(f"members = {M} must lie in 1..{MAX_MEMBERS}")
@@ -61,11 +75,14 @@ def perturb_members(x, items, members, sigma, seed, control=True, variables=None
         raise ValueError(f"x must be [B, ..., V, H, W] or [B, ..., V, 12, n, n], not {tuple(x.shape)}")
     B = x.shape[0]
     V, P = _layout(x, variables)
-    it = np.asarray(items.cpu() if torch.is_tensor(items) else items)
-    if it.shape != (B,) or not np.issubdtype(it.dtype, np.integer):
-        raise ValueError(f"items must be {B} integers, not {it.dtype} {it.shape}")
-    if B and (it.min() < 0 or it.max() >= 2 ** 31):
-        raise ValueError(f"items must lie in 0..2^31 - 1, found {int(it.min())}..{int(it.max())}")
+    if validate_items:
+        it = np.asarray(items.cpu() if torch.is_tensor(items) else items)
+        if it.shape != (B,) or not np.issubdtype(it.dtype, np.integer):
+            raise ValueError(f"items must be {B} integers, not {it.dtype} {it.shape}")
+        if B and (it.min() < 0 or it.max() >= 2 ** 31):
+            raise ValueError(f"items must lie in 0..2^31 - 1, found {int(it.min())}..{int(it.max())}")
+    elif not (torch.is_tensor(items) and items.dtype == torch.int32 and tuple(items.shape) == (B,) and items.device == x.device):
+        raise ValueError(f"validate_items=False takes an int32 [{B}] tensor on {x.device}")
     sg = np.asarray(sigma, dtype=np.float64).reshape(-1)
     if sg.size == 1:
         sg = np.repeat(sg, V)
@@ -81,8 +98,8 @@ def perturb_members(x, items, members, sigma, seed, control=True, variables=None
     xc = x.contiguous()
     F = xc.numel() // B
     out = torch.empty((B, M) + tuple(x.shape[1:]), device=x.device)
-    dit = torch.from_numpy(np.ascontiguousarray(it.astype(np.int32))).to(x.device)
-    dsg = torch.from_numpy(sg.astype(np.float32)).to(x.device)
+    dit = torch.from_numpy(np.ascontiguousarray(it.astype(np.int32))).to(x.device) if validate_items else items.contiguous()
+    dsg = _device_floats(tuple(sg.tolist()), x.device)
     L.check(L.load().dlwp_ens_perturb(L.ptr(xc), L.ptr(dit), L.ptr(dsg), B, F, P, V, M, int(bool(control)), seed, L.ptr(out), L.stream()))
     return out
 
@@ -191,3 +208,152 @@ def ensemble_metrics(diag, scale=None):
     return {"rmse_mean": rmse, "spread": spread, "spread_skill": float(np.sqrt((M + 1) / M)) * spread / rmse,
             "crps": sc * (tot[..., 2] - tot[..., 3]) / n, "crps_ens": sc * (tot[..., 2] - (M - 1) / M * tot[..., 3]) / n,
             "mae_members": sc * tot[..., 2] / n, "rank_hist": cnt.double() / n}
+
+
+# ---- the CRPS as a training loss (dlwp_crps_loss_fwd_bwd) ---------------------------------------------------------------------------
+def pair_coefficient(alpha, members):
+    """lambda = 1 - (1 - alpha) / M of the "almost fair" CRPS: alpha = 1 the fair estimator, alpha = 0 the ensemble estimator"""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:                              # (a NaN fails both comparisons)
+        raise ValueError(f"alpha = {alpha} must lie in [0, 1]")
+    return 1.0 - (1.0 - alpha) / int(members)
+
+
+def _crps_weights(plane, lats_deg, var_weights, V, device):
+    """(H, W, row weights [H] or None, variable weights [V] or None) for planes [H, W] or [12, n, n] (equal-area pixels: H = 12 n,
+    W = n, no row weights)"""
+    if len(plane) == 3:
+        if plane[0] != 12 or plane[1] != plane[2]:
+            raise ValueError(f"planes must be [H, W] or [12, n, n], not {list(plane)}")
+        if lats_deg is not None:
+            raise ValueError("lats_deg with HEALPix planes [12, n, n]: their pixels have equal area, there are no row weights")
+        H, W = 12 * plane[1], plane[2]
+    elif len(plane) == 2:
+        H, W = plane
+    else:
+        raise ValueError(f"planes must be [H, W] or [12, n, n], not {list(plane)}")
+    roww = varw = None
+    if lats_deg is not None:
+        lats = tuple(float(v) for v in np.asarray(lats_deg, dtype=np.float64).reshape(-1))
+        if len(lats) != H:
+            raise ValueError(f"lats_deg must have {H} entries, not {len(lats)}")
+        from .evaluate import lat_weights
+        roww = _device_floats(tuple(lat_weights(lats).tolist()), device)
+    if var_weights is not None:
+        vw = np.asarray(var_weights, dtype=np.float64).reshape(-1)
+        if vw.size != V:
+            raise ValueError(f"var_weights must have one entry per variable ({V}), not {vw.size}")
+        if not (np.isfinite(vw).all() and (vw >= 0).all()):
+            raise ValueError(f"var_weights {vw.tolist()} must be finite and not negative")
+        varw = _device_floats(tuple(vw.tolist()), device)
+    return int(H), int(W), roww, varw
+
+
+def _crps_launch(members, target, loss_out, want_grad, alpha, lats_deg, var_weights, held=None):
+    """(loss, gradient or None): the checks and the one call behind crps_loss and crps_loss_and_grad.  held: a dictionary in which the
+    caller keeps the weight tables alive (a captured step replays their addresses)"""
+    if target.dim() not in (5, 6) or members.dim() != target.dim() + 1:
+        raise ValueError(f"members must be [B, M, T, V, H, W] and target [B, T, V, H, W] (or planes [12, n, n]), not "
+                         f"{tuple(members.shape)} / {tuple(target.shape)}")
+    B, T, V = (int(n) for n in target.shape[:3])
+    M = int(members.shape[1])
+    plane = tuple(target.shape[3:])
+    if tuple(members.shape) != (B, M, T, V) + plane:
+        raise ValueError(f"members {tuple(members.shape)} and target {tuple(target.shape)} differ")
+    if not 2 <= M <= MAX_MEMBERS:
+        raise ValueError(f"M = {M} members must lie in 2..{MAX_MEMBERS}")
+    lam = pair_coefficient(alpha, M)
+    if members.dtype != torch.float32 or target.dtype != torch.float32:
+        raise L.DlwpError(f"crps_loss takes float32 tensors, not {members.dtype} / {target.dtype}")
+    if not target.is_cuda or not members.is_cuda:
+        raise L.DlwpError("libdlwpmi needs CUDA/HIP tensors (no CPU fallback)")
+    dev = target.device
+    if held is None or (dev, plane) not in held:
+        tables = _crps_weights(plane, lats_deg, var_weights, V, dev)
+        if held is not None:
+            held[(dev, plane)] = tables
+    else:
+        tables = held[(dev, plane)]
+    H, W, roww, varw = tables
+    m = members.detach()
+    dense = [int(np.prod(m.shape[k + 1:])) for k in range(3, m.dim())]
+    if list(m.stride()[3:]) != dense or min(m.stride()[:3]) < 0:
+        m = m.contiguous()
+    bs, ms, ts = m.stride()[:3]
+    if loss_out is None:
+        loss_out = torch.empty(1, device=dev)
+    elif loss_out.numel() != 1 or loss_out.dtype != torch.float32 or loss_out.device != dev:
+        raise L.DlwpError(f"loss_out must be one float32 on {dev}, not {loss_out.dtype} {tuple(loss_out.shape)} on {loss_out.device}")
+    grad = torch.empty(members.shape, device=dev) if want_grad else None
+    lib = L.load()
+    ws = L.workspace(lib.dlwp_crps_loss_ws_floats, B, M, T, V, H, W, device=dev)
+    L.check(lib.dlwp_crps_loss_fwd_bwd(m.data_ptr(), bs, ms, ts, L.ptr(target.detach().contiguous()), L.ptr(roww), L.ptr(varw), B, M, T, V,
+                                       H, W, lam, L.ptr(loss_out), L.ptr(grad), L.ptr(ws), L.stream()))
+    return loss_out.reshape(()), grad
+
+
+def crps_loss_and_grad(members, target, loss_out=None, *, alpha=1.0, lats_deg=None, var_weights=None):
+    """(the loss of `crps_loss`, its gradient with respect to members) from the one dlwp_crps_loss_fwd_bwd call, for a caller that
+    seeds the backward pass itself (train_engine.mse_loss_and_grad's counterpart).  loss_out: a one-element fp32 tensor that
+    receives the loss (written, not accumulated)."""
+    return _crps_launch(members, target, loss_out, True, alpha, lats_deg, var_weights)
+
+
+class _Crps(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, members, target, alpha, lats_deg, var_weights):
+        want = ctx.needs_input_grad[0]                       # False under no_grad: the loss alone (grad = NULL), as validation does
+        loss, g = _crps_launch(members, target, None, want, alpha, lats_deg, var_weights)
+        if want:
+            ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (g,) = ctx.saved_tensors
+        return g * gl, None, None, None, None
+
+
+def crps_loss(members, target, *, alpha=1.0, lats_deg=None, var_weights=None):
+    """The CRPS of M members against the target as one differentiable scalar (0-d), value and gradient from the same kernel:
+
+        loss = mean over [B, T, V, H, W] of r_h c_v ((1 / M) sum_i |x_i - y| - lambda / (M (M - 1)) sum_{i<j} |x_i - x_j|),
+        lambda = 1 - (1 - alpha) / M
+
+    members      [B, M, T, V, H, W] or [B, M, T, V, 12, n, n] fp32 on the GPU (HEALPix planes: equal-area pixels, scored as H = 12 n,
+                 W = n); batch, member and time strides are read in place, the trailing axes are made dense if they are not.
+    target       the same shape without M.
+    alpha        1: the fair CRPS (`ensemble_metrics`' "crps"); 0: the ensemble estimator ("crps_ens"); between: "almost fair".
+    lats_deg     latitudes of the H rows: the weights r = `evaluate.lat_weights`; not with HEALPix planes (ValueError).
+    var_weights  one weight c per variable.
+    The sub-gradient is torch's: sgn(0) = 0, members that tie contribute nothing to each other.  Where members needs no gradient
+    (torch.no_grad()) the kernel skips the gradient."""
+    return _Crps.apply(members, target, alpha, lats_deg, var_weights)
+
+
+class CrpsLoss:
+    """The loss object of `train_engine.GraphedTrainStep(..., loss=)`: the model's output [B M, T, V, ...] holds the M members of
+    each of the B samples next to each other (sample-major, the `repeat_interleave` order in which `evaluate_dlwp` folds the members
+    into the batch); the target has B rows."""
+
+    def __init__(self, members, alpha=1.0, lats_deg=None, var_weights=None):
+        self.members = int(members)
+        if not 2 <= self.members <= MAX_MEMBERS:
+            raise ValueError(f"members = {self.members} must lie in 2..{MAX_MEMBERS}")
+        pair_coefficient(alpha, self.members)
+        self.alpha, self.lats_deg, self.var_weights = float(alpha), lats_deg, var_weights
+        self._held = {}
+
+    def _view(self, out, target):
+        if out.dim() != target.dim() or out.shape[0] != target.shape[0] * self.members or out.shape[1:] != target.shape[1:]:
+            raise ValueError(f"output {tuple(out.shape)} is not {self.members} members of the target {tuple(target.shape)}")
+        return out.reshape(target.shape[0], self.members, *out.shape[1:])
+
+    def loss_and_grad(self, out, target, loss_out=None):
+        """(loss, d loss / d out in out's shape)"""
+        loss, g = _crps_launch(self._view(out, target), target, loss_out, True, self.alpha, self.lats_deg, self.var_weights, self._held)
+        return loss, g.reshape(out.shape)
+
+    def loss(self, out, target):
+        """the loss alone (validation)"""
+        return _crps_launch(self._view(out, target), target, None, False, self.alpha, self.lats_deg, self.var_weights, self._held)[0]

@@ -140,6 +140,8 @@ SIGNATURES = {
     "dlwp_ens_perturb": (_I, [_V, _V, _V, _I, _L, _L, _I, _I, _I, C.c_ulonglong, _V, _V]),
     "dlwp_ens_diag_ws_floats": (_L, [_I] * 6),
     "dlwp_ens_diag": (_I, [_V, _L, _L, _L, _V, _V] + [_I] * 8 + [_V] * 4),
+    "dlwp_crps_loss_ws_floats": (_L, [_I] * 6),
+    "dlwp_crps_loss_fwd_bwd": (_I, [_V, _L, _L, _L, _V, _V, _V] + [_I] * 6 + [_F] + [_V] * 4),
     "dlwp_gemm": (_I, [_V, _V, _V] + [_I] * 8 + [_V, _I, _V, _V, _I, _V, _V]),
     "dlwp_gemm_mixed": (_I, [_V, _V, _V] + [_I] * 8 + [_V, _I, _V, _V, _I, _V, _I, _V]),
     "dlwp_gemm_batched_mixed": (_I, [_V, _V, _V] + [_I] * 10 + [_L] * 6 + [_V, _L, _L, _I, _F, _V, _V, _L, _L, _I, _I, _I, _V]),

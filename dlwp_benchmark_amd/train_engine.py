@@ -134,11 +134,16 @@ class GraphedTrainStep:
     A reducer with `in_graph = True` (ddp.RcclComm: the C ABI's communicator enqueues ncclAllReduce on the caller's stream,
     which RCCL allows under stream capture) is captured INSIDE the one graph, between backward and the optimizer: a replay
     is then the whole data-parallel step.
+    `loss`: another criterion than the MSE, an object with `loss_and_grad(out, target, loss_out)` (ensemble.CrpsLoss: the inputs
+    then carry M members per row of `target`).
     """
 
     def __init__(self, model, inputs, target, lr=1e-3, clip_max_norm=None, allreduce=None, grad_scale=1.0,
-                 use_graph=True, call=None, graph_optimizer=True):
+                 use_graph=True, call=None, graph_optimizer=True, loss=None):
         self.model = model
+        # loss: None is the MSE of mse_loss_and_grad; otherwise an object whose loss_and_grad(out, target, loss_out) returns (loss,
+        # d loss / d out) and writes the loss into loss_out (ensemble.CrpsLoss: out then holds M members per target row)
+        self.loss_and_grad = mse_loss_and_grad if loss is None else loss.loss_and_grad
         self.flat, self.grad = flatten_parameters(model)
         self.opt = FusedAdam(self.flat, self.grad, lr=lr)
         self.inputs = {k: v.clone() for k, v in inputs.items()}
@@ -163,8 +168,8 @@ class GraphedTrainStep:
         prev, L.SHADOW_ACTIVE = L.SHADOW_ACTIVE, True
         try:
             out = self.call(self.model, self.inputs)
-            _, g = mse_loss_and_grad(out, self.target, self.loss)
-            torch.autograd.backward(out, g)           # = mse_loss(out, target).backward() without the seed launches
+            _, g = self.loss_and_grad(out, self.target, self.loss)
+            torch.autograd.backward(out, g)           # = loss(out, target).backward() without the seed launches
         finally:
             L.SHADOW_ACTIVE = prev
 

@@ -263,9 +263,59 @@ def validation_mse_dlwp(model, dataset, batch_size, device, resident=None):
     return tot / max(cnt, 1)
 
 
+def _crps_training_args(loss, ensemble, ensemble_sigma, ensemble_seed, crps_alpha):
+    """None for loss="mse", (M, sigma, seed, alpha) for loss="crps": train_dlwp's loss keywords, validated before the first batch"""
+    if loss not in ("mse", "crps"):
+        raise ValueError(f"loss = {loss!r} must be 'mse' or 'crps'")
+    if loss == "mse":
+        if ensemble is not None:
+            raise ValueError(f"ensemble = {ensemble} needs loss='crps': the MSE step has no member axis")
+        return None
+    if ensemble is None:
+        raise ValueError("loss='crps' needs ensemble = M members, 2 <= M <= 64")
+    from .ensemble import pair_coefficient
+    from .evaluate import _ensemble_args
+    M, sigma, seed = _ensemble_args(ensemble, ensemble_sigma, ensemble_seed)
+    pair_coefficient(crps_alpha, M)
+    return M, sigma, seed, float(crps_alpha)
+
+
+def _perturbed_inputs(c, p, g, items, M, sigma, seed):
+    """The inputs of B samples as B M rows, the members of a sample next to each other (the order `evaluate_dlwp` folds them in):
+    `prognostic` perturbed into M exchangeable members (no control member), constants and prescribed repeated.  items: the dataset
+    indices; an int32 tensor on the device is read in place."""
+    from . import ensemble as E
+    pm = E.perturb_members(g, items, M, sigma, seed, control=False, variables=g.shape[2],
+                           validate_items=not (torch.is_tensor(items) and items.is_cuda))
+    fold = lambda a: None if a is None else a.repeat_interleave(M, dim=0)      # noqa: E731
+    return fold(c), fold(p), pm.reshape(g.shape[0] * M, *g.shape[1:])
+
+
+@torch.no_grad()
+def validation_crps_dlwp(model, dataset, batch_size, device, criterion, sigma, seed, resident=None):
+    """The CRPS of `criterion` (an ensemble.CrpsLoss) over the validation samples, each perturbed into the criterion's members with
+    `seed` (the item is the dataset index) and scored by the forward-only kernel call; batches are weighted by their sample count."""
+    from . import wbdata
+    tot, cnt = torch.zeros((), device=device), 0
+    was_training = model.training
+    model.eval()
+    for i0 in range(0, len(dataset), batch_size):
+        items = list(range(i0, min(i0 + batch_size, len(dataset))))
+        if resident is not None:
+            c, p, g, t = resident.batch(items, getattr(dataset, "epoch", 0))
+        else:
+            c, p, g, t = wbdata.to_device_batch([dataset[i] for i in items], device)
+        c, p, g = _perturbed_inputs(c, p, g, items, criterion.members, sigma, seed)
+        tot += criterion.loss(model(constants=c, prescribed=p, prognostic=g), t) * len(items)
+        cnt += len(items)
+    model.train(was_training)
+    return tot.item() / max(cnt, 1)
+
+
 def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch_size=4, learning_rate=1e-3,
                clip_gradients=False, gradient_accumulation_steps=1, seed=1234, out_dir="outputs", save_model=True,
-               use_graph=True, verbose=False, continue_training=False, log_scalars=True, device_data=False):
+               use_graph=True, verbose=False, continue_training=False, log_scalars=True, device_data=False, loss="mse",
+               ensemble=None, ensemble_sigma=0.0, ensemble_seed=None, crps_alpha=1.0, loss_lat_weighted=False):
     """The dlwpbench training script's epoch loop (src/dlwpbench/scripts/train.py:104-197) around the captured step of
     train_engine.GraphedTrainStep, for any dlwpbench module (forward(constants, prescribed, prognostic)): batches of
     `WeatherBenchDataset.__getitem__` tuples (wbdata.WeatherBenchArrays) from the seeded rank-sharded permutation, MSE,
@@ -275,9 +325,19 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
     torch.distributed initialised the flat gradient is all-reduced once per step.  Returns per-epoch dicts.
     device_data: upload both datasets once and assemble every batch on the device with one launch (device_data.py) instead of
     `__getitem__` + collate + four copies; same items, and with noise == 0 the same bits; with noise > 0 the perturbation
-    comes from the device path's own seeded stream (the dataset then needs a seed)."""
+    comes from the device path's own seeded stream (the dataset then needs a seed).
+    loss="crps": train on the CRPS of perturbed members (ensemble.crps_loss; the reference has no such loss).  Every micro-batch's
+    `prognostic` is perturbed into `ensemble` = M exchangeable members (`ensemble.perturb_members`, control=False, the items are
+    the dataset indices, `ensemble_sigma` a scalar or one value per prognostic channel in normalised units, seed (ensemble_seed +
+    epoch) mod 2^64: fresh noise every epoch), constants and prescribed are repeated, the members run folded into the batch
+    (B M rows) and the step's loss is `ensemble.CrpsLoss(M, crps_alpha)` -- with cos(lat) row weights of the regular grid when
+    `loss_lat_weighted`.  The epoch dict carries "train_crps" in place of "train_mse", and next to "val_mse" -- still the MSE of the
+    unperturbed forecast, still what selects the `_best` checkpoint, so runs with different losses stay comparable -- "val_crps":
+    the validation samples perturbed with seed (ensemble_seed + 2^63) mod 2^64 and scored by the forward-only kernel call."""
     from . import wbdata
     from .train_engine import GraphedTrainStep
+    crps = _crps_training_args(loss, ensemble, ensemble_sigma, ensemble_seed, crps_alpha)
+    members, criterion = crps[0] if crps else 1, None      # the criterion is built with the first batch (it needs the grid)
     # micro-batches as in the reference (:206-233): split_size = max(1, batch // steps); every micro-batch's mean loss is
     # back-propagated un-scaled (the gradients are summed), the clip acts after every micro-backward, one Adam step per batch
     micro = max(1, batch_size // max(1, gradient_accumulation_steps))
@@ -319,11 +379,18 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
                 c, p, g, t = res_train.batch(idx, epoch)
             else:
                 c, p, g, t = wbdata.to_device_batch([train_dataset[int(i)] for i in idx], device)
-            sl = lambda v, i: None if v is None else v[i:i + micro]      # noqa: E731
+            if crps:
+                c, p, g = _perturbed_inputs(c, p, g, idx, members, crps[1], (crps[2] + epoch) % 2 ** 64)
+                if criterion is None:
+                    from .ensemble import CrpsLoss
+                    from .evaluate import regular_latitudes
+                    criterion = CrpsLoss(members, crps[3], lats_deg=regular_latitudes(t.shape[-2]) if loss_lat_weighted else None)
+            # micro-batch i: rows i .. i + micro of the target, and of the inputs their `members` rows each
+            sl = lambda v, i: None if v is None else v[i * members:(i + micro) * members]      # noqa: E731
             if step is None:
                 step = GraphedTrainStep(model, kwargs_of(sl(c, 0), sl(p, 0), sl(g, 0)), t[:micro], lr=lr, allreduce=reducer,
                                         grad_scale=1.0 / world, use_graph=use_graph, graph_optimizer=False,
-                                        clip_max_norm=lr if clip_gradients else None)
+                                        clip_max_norm=lr if clip_gradients else None, loss=criterion)
                 if resume is not None:
                     st = resume.get("optimizer_state_dict")
                     if not (isinstance(st, dict) and _load_optimizer_state(st, model, step.opt, ckpt_last)):
@@ -336,17 +403,22 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
             step.opt.lr = lr
             step.clip = lr if clip_gradients else None
             if micro == batch_size:
-                loss = step(kwargs_of(c, p, g), t)
+                step_loss = step(kwargs_of(c, p, g), t)
             else:
                 for i in range(0, batch_size, micro):
-                    loss = step.accumulate(kwargs_of(sl(c, i), sl(p, i), sl(g, i)), t[i:i + micro])
+                    step_loss = step.accumulate(kwargs_of(sl(c, i), sl(p, i), sl(g, i)), t[i:i + micro])
                 step.apply()
-            losses.append(loss.clone())
-            writer.add_scalar("MSE/training", losses[-1], iteration)
+            losses.append(step_loss.clone())
+            writer.add_scalar("CRPS/training" if crps else "MSE/training", losses[-1], iteration)
             iteration += 1
         train_mse = torch.stack(losses).mean().item() if losses else float("nan")
         val_mse = validation_mse_dlwp(model, val_dataset, batch_size, device, resident=res_val)
         writer.add_scalar("MSE/validation", val_mse, iteration)
+        entry = {"epoch": epoch, "lr": lr, "train_crps" if crps else "train_mse": train_mse, "val_mse": val_mse}
+        if criterion is not None:
+            entry["val_crps"] = validation_crps_dlwp(model, val_dataset, batch_size, device, criterion, crps[1],
+                                                     (crps[2] + 2 ** 63) % 2 ** 64, resident=res_val)
+            writer.add_scalar("CRPS/validation", entry["val_crps"], iteration)
         writer.flush()
         if save_model and rank == 0 and step is not None:
             sched = {"T_max": epochs, "last_epoch": epoch, "base_lrs": [learning_rate], "_last_lr": [lr]}
@@ -355,7 +427,7 @@ def train_dlwp(model, train_dataset, val_dataset, name="model", epochs=10, batch
             else:
                 best, dst = val_mse, ckpt_last.replace("last", "best")
             write_checkpoint(model, step.opt, sched, epoch, iteration, best, dst)
-        log.append({"epoch": epoch, "lr": lr, "train_mse": train_mse, "val_mse": val_mse})
+        log.append(entry)
         if verbose and rank == 0:
-            print(f"Epoch {str(epoch).zfill(3)}/{epochs}\tMSE train: {train_mse:.2E}\tMSE val: {val_mse:.2E}")
+            print(f"Epoch {str(epoch).zfill(3)}/{epochs}\t{'CRPS' if crps else 'MSE'} train: {train_mse:.2E}\tMSE val: {val_mse:.2E}")
     return log

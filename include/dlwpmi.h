@@ -708,6 +708,20 @@ long long dlwp_ens_diag_ws_floats(int Bc, int M, int Tc, int V, int H, int W);
 int dlwp_ens_diag(const float* members, long long bstride, long long mstride, long long tstride, const float* target,
                   const float* row_weights, int Bc, int M, int Tc, int V, int H, int W, int t_begin, int T, float* sums, int* ranks,
                   float* ws, void* stream);
+/* The CRPS of M members as a training loss, with its gradient from the same launch (csrc/ensemble.hip; tests/crps_ref.py defines it).  */
+/* Per pixel, with lambda = pair_coeff:  l = (1 / M) sum_i |x_i - y| - lambda / (M (M - 1)) sum_{i<j} |x_i - x_j|  (lambda = 1: the     */
+/* fair CRPS, columns 2 - 3 of dlwp_ens_diag; lambda = (M - 1) / M: the ensemble estimator), and                                         */
+/*   loss = (1 / N) sum_{b,t,v,h,w} r_h c_v l,  N = B T V H W;  row_weights [H] (r) and var_weights [V] (c) may be NULL (all ones)       */
+/*   grad[b][m][t][v][h][w] = (r_h c_v / N) (sgn(x_m - y) / M - lambda / (M (M - 1)) (#{j : x_j < x_m} - #{j : x_j > x_m})),             */
+/*   sgn(0) = 0 and a tie x_i == x_j contributes nothing (torch's sub-gradient of abs); dense, WRITTEN; NULL: the loss alone.            */
+/*   members as dlwp_ens_diag (element strides >= 0), target dense [B][T][V][H][W], loss_out one float, WRITTEN.                         */
+/*   ws    : dlwp_crps_loss_ws_floats(B, M, T, V, H, W) floats (one partial per pixel block)                                             */
+/* 2 <= M <= DLWP_ENS_MAX_MEMBERS, H W <= 2^21, 0 <= pair_coeff <= 1.  Two launches, no atomics, one writer per address, a summation     */
+/* order that depends on the shape only: two calls give the same bits of the loss and of the gradient.  Knob: ENS_BUCKET.                */
+long long dlwp_crps_loss_ws_floats(int B, int M, int T, int V, int H, int W);
+int dlwp_crps_loss_fwd_bwd(const float* members, long long bstride, long long mstride, long long tstride, const float* target,
+                           const float* row_weights, const float* var_weights, int B, int M, int T, int V, int H, int W, float pair_coeff,
+                           float* loss_out, float* grad, float* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Token-level building blocks of the AFNO / Swin / Pangu blocks (nn.Linear, nn.LayerNorm, */
