@@ -118,7 +118,7 @@ long long dlwp_fno_gslab_stride(int C);
 
 // ---- one block, sequenced: per-mode launch, then `spatial`, in the forms one decision function per direction picks.
 // Refusal protocol: the decision is taken in front of every launch, from the plan, the argument struct and the knobs FNO_SKIP_WGRAD_IN_MIX,
-// FNO_FUSE_LIFT_BWD and FNO_FUSE_PROJ_FWD (each read once per call).  With route AUTO a form the shapes or knobs do not take is
+// FNO_FUSE_LIFT_BWD, FNO_FUSE_PROJ_BWD and FNO_FUSE_PROJ_FWD (each read once per call).  With route AUTO a form the shapes or knobs do not take is
 // simply not chosen and the call runs the launches that remain.  A forced route that is not available gives DLWP_E_UNSUPPORTED
 // with the error string untouched and nothing launched.  The one refusal that shows later -- the projection chain's, while its
 // arguments are built -- is still in front of every launch: AUTO falls back to the separate launches, a forced route returns it.
@@ -131,12 +131,13 @@ enum dlwp_fno_route {
 enum dlwp_fno_spatial_form {
     DLWP_FNO_SPATIAL_FOUR_WAVE,   // fno_spatial_kernel (wide plans: the channel-blocked launches of fno_wide.hip)
     DLWP_FNO_SPATIAL_TWO_ROLE,    // bwd: fno_spatial_roles_kernel, the skip gradients on waves of their own
-    DLWP_FNO_SPATIAL_FUSED_TAIL   // bwd: fno_spatial_lift_bwd_kernel; fwd: fno_spatial_proj_fwd_kernel
+    DLWP_FNO_SPATIAL_FUSED_TAIL   // bwd: fno_spatial_lift_bwd_kernel / fno_spatial_lift_proj_bwd_kernel; fwd: fno_spatial_proj_fwd_kernel
 };
 struct dlwp_fno_forms {
     int rc;                       // DLWP_OK, or DLWP_E_UNSUPPORTED: the forced route is not available
     bool hosted;                  // bwd: fno_mix_bwd_skipgrad_kernel instead of fno_mix_bwd_kernel
     int spatial;                  // dlwp_fno_spatial_form
+    bool proj;                    // bwd, FUSED_TAIL: the previous net call's projection backward runs as the launch's third phase
 };
 // the lifting MLP's backward behind block 0: dlwp_pwmlp_bwd_ex's operands with gy = the block's g_x (which the fused launch
 // keeps in LDS and does not write); gw1 .. gb2 are read by the separate launch only
@@ -148,6 +149,20 @@ struct dlwp_fno_lift_bwd_tail {
     float *gw1, *gb1, *gw2, *gb2;
     float* slab;
     int slab_accumulate, Cin, Ch;
+};
+// the PREVIOUS net call's projection backward behind block 0's lifting backward (the next launch of the rollout's backward chain, on
+// the same row tiles): dlwp_pwmlp_bwd_rows_ex's operands in the form the NS rollout uses -- scalar output, upstream gradient = gy +
+// mse_scale * (pred - target), no residual path, dense overwritten gx with its adjoint rows DFT into x1_out, slab mode
+struct dlwp_fno_proj_bwd_tail {
+    const dlwp_chan_src* x;       // `pre` of the previous call's last block
+    const float *w1, *b1, *w2;
+    const dlwp_chan_src *gy, *pred, *target;
+    float mse_scale;
+    const dlwp_chan_dst* gx;
+    float2* x1_out;
+    float* slab;
+    int slab_accumulate, Ch, Cout;
+    int* taken;                   // out, nullable: the projection backward ran with this call (the caller skips its own launch)
 };
 // the projection MLP behind the last block (dlwp_pwmlp_fwd_ex's operands with x = the block's pre) and, with x2v != NULL, the next
 // net call's lifting MLP with its rows DFT chained behind it (dlwp_pwmlp_fwd_chain_ex's second half, Cout2 = plan->C)
@@ -194,6 +209,8 @@ struct dlwp_fno_block_bwd_args {
     int rows_dft;
     float2* x1_out;               // optional: adjoint rows DFT of g_x for the next block down
     const dlwp_fno_lift_bwd_tail* lift;   // block 0: the lifting backward runs with this call, fused or as a separate launch
+    const dlwp_fno_proj_bwd_tail* proj;   // block 0, nullable: the previous net call's projection backward, taken into the fused
+                                          // launch where the shapes allow (*taken); otherwise left to the caller
     int route, B;
 };
 dlwp_fno_forms dlwp_fno_fwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_fwd_args* a);

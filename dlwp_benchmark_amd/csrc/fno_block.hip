@@ -502,6 +502,55 @@ __global__ __launch_bounds__(512) void fno_spatial_lift_bwd_kernel(SpatialLiftDe
     DLWP_SPAN_END();
 }
 
+// The launch above with a THIRD phase: the scalar-output projection backward of the PREVIOUS net call (pwmlp_bwd_kernel<NCB, 0, 8>,
+// the next launch of the rollout's backward chain) on the same 64-pixel row under the same blockIdx.  Of this launch it needs only
+// its own row of the closed-loop gradient: the rows of g_out that phase 2 of this very workgroup has just accumulated through the
+// pointer table -- no other workgroup touches them.  Everything else it reads (`pre` of the previous call's last block, the
+// projection weights, prediction and target) was finished by earlier launches; what it writes (its row of the gradient of that
+// `pre`, its row of x1, its projection slab) has no reader in this launch except, where the gradient buffer is also this launch's
+// g_pre, the same workgroup's phase 1, long past.
+//   phases 1, 2: the text of fno_spatial_lift_bwd_kernel.
+//   phase 3: the whole text of pwmlp_bwd_body.inc.h once more, in the stand-alone form: gy staging (closed-loop gradient + MSE
+//            term), main loop, gx, adjoint rows DFT into x1.  Its LDS is carved from the start of smem, over the regions of
+//            phase 2, behind one workgroup barrier (PWMLP_BWD_BEHIND) that also orders this workgroup's g_out stores in front of
+//            their staging; each wave's first weight fragments and the DFT table are requested in front of that barrier (when
+//            phase 2 has finished: not in front of phases 1 and 2, and the x tile not at all ahead of its staging).
+// Same text, same row, same blockIdx: every output is bit for bit that of the two launches.
+struct SpatialLiftProjDev {
+    SpatialDev s;
+    BwdArgs m, q;
+};
+template <int NCB, int NBN, int NIBL, bool ROLE_B = true>
+__global__ __launch_bounds__(512) void fno_spatial_lift_proj_bwd_kernel(SpatialLiftProjDev f) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    {
+        constexpr int NIB = NIBL, NOB = NCB, NW = 8;
+        constexpr bool PWMLP_BWD_EARLY = true;      // instantiated for NCB <= 2 only
+        const BwdArgs& a = f.m;
+#define PWMLP_BWD_FUSED
+#define PWMLP_BWD_PART 1
+#include "pwmlp_bwd_body.inc.h"
+#undef PWMLP_BWD_PART
+        {
+            constexpr int MODE = 2;
+            const SpatialDev& a = f.s;
+#include "fno_spatial_roles_head.inc.h"
+        }
+#define PWMLP_BWD_PART 2
+#include "pwmlp_bwd_body.inc.h"
+#undef PWMLP_BWD_PART
+#undef PWMLP_BWD_FUSED
+    }
+    {
+        constexpr int NIB = NCB, NOB = 0, NW = 8;
+        const BwdArgs& a = f.q;
+#define PWMLP_BWD_BEHIND
+#include "pwmlp_bwd_body.inc.h"
+#undef PWMLP_BWD_BEHIND
+    }
+    DLWP_SPAN_END();
+}
+
 // The last block's forward `spatial` and the projection MLP (chained, as in pwmlp_fwd_chain_kernel, with the next net call's lifting
 // MLP and its rows DFT; NOB2 == 0: projection only) as ONE launch of 16 waves.  On 64-wide rows a `spatial` workgroup (one image row
 // (b, h)) and a pointwise-MLP workgroup (64 consecutive pixels of one sample) are the same pixels under the same blockIdx: the row
@@ -1567,15 +1616,34 @@ static size_t lift_bwd_fused_lds(const dlwp_fno_plan* p, int Cin) {
     return need <= CU_LDS_BYTES ? need : 0;       // need >= lds_roles: the two-role layout fits too
 }
 
+// The same launch with the previous net call's projection backward as its third phase (fno_spatial_lift_proj_bwd_kernel): LDS
+// bytes, or 0 where that projection backward keeps its own launch.  Taken where the stand-alone launch would be the scalar-output
+// kernel with the rows DFT in its epilogue (dlwp_pwmlp_bwd_rows_ex's own conditions: 64-wide rows, NP == 16, 16-byte access to
+// every view, a dense gx), at most two channel tiles (the instantiations that compile without scratch and without vector
+// spills), and all three phases inside the LDS of a CU.
+static size_t proj_bwd_fused_lds(const dlwp_fno_plan* p, int Cin, const dlwp_fno_proj_bwd_tail* q) {
+    const size_t lift = lift_bwd_fused_lds(p, Cin);
+    const int P = p->H * p->W;
+    if (!lift || !q || q->Cout != 1 || q->Ch < 1 || p->C_pad > 32 || !dlwp_pwmlp_rows_fusable(p, p->C, P)) return 0;
+    if (!q->x || !q->gy || !q->pred || !q->target || !q->gx || !q->gx->base || !q->x1_out || !q->slab) return 0;
+    if (!view_vec_ok(*q->x) || !view_vec_ok(*q->gy) || !view_vec_ok(*q->gx) || q->gx->bstride != (long long)p->C * P ||
+        q->gx->cstride != P) return 0;
+    const size_t phase3 = sizeof(float) * ((size_t)(1 + BWD_WAVES) * p->C_pad + 16) * LDP;
+    const size_t need = lift > phase3 ? lift : phase3;
+    return need <= CU_LDS_BYTES ? need : 0;
+}
+
 // `s`: the backward `spatial` arguments of block 0 (no activation in front of it, neither `out` nor a fused row DFT); t: the lifting
 // backward's operands, as for dlwp_pwmlp_bwd_ex with gy = the gradient `spatial` would have written.  Only where
 // dlwp_fno_bwd_decide() names the fused form.  s->gslab == NULL: the by-products of block 0 were formed by the per-mode launch
-// (mix_bwd_skipgrad_launch), and phase 1 runs the chain alone.
+// (mix_bwd_skipgrad_launch), and phase 1 runs the chain alone.  q != NULL (only where dlwp_fno_bwd_decide() says `proj`): the
+// previous net call's projection backward as the third phase, its argument block filled as dlwp_pwmlp_bwd_rows_ex fills it.
 static int spatial_lift_bwd_launch(const dlwp_fno_plan* p, const dlwp_fno_spatial_args* s, const dlwp_fno_lift_bwd_tail* t,
-                                   hipStream_t stream) {
+                                   const dlwp_fno_proj_bwd_tail* q, hipStream_t stream) {
     const int Cin = t->Cin, Ch = t->Ch;
-    const size_t lds = lift_bwd_fused_lds(p, Cin);
+    const size_t lds = q ? proj_bwd_fused_lds(p, Cin, q) : lift_bwd_fused_lds(p, Cin);
     const bool role_b = s->gslab != nullptr;
+    SpatialLiftProjDev fq{};
     SpatialLiftDev f{};
     f.s = make_spatial_dev(p, s);
     BwdArgs& a = f.m;
@@ -1592,9 +1660,27 @@ static int spatial_lift_bwd_launch(const dlwp_fno_plan* p, const dlwp_fno_spatia
     const int ncb = p->C_pad / 16, nbn = p->NP / 16, nib = a.Cin_pad / 16;
     const dim3 grid(s->B * p->H);
     const double pix = (double)s->B * a.P;
-    dlwp_prof_scope prof(stream, 2.0 * pix * (p->C * (2.0 * p->C + 2 * p->m2c) + Ch * (3.0 * Cin + 2.0 * p->C)),
-                         4.0 * pix * (2.0 * p->C + 2.0 * Cin),
-                         "fno_spatial_lift_bwd_kernel<%d, %d, %d>", ncb, nbn, nib);   // one accounting row for both forms of phase 1
+    double flops = 2.0 * pix * (p->C * (2.0 * p->C + 2 * p->m2c) + Ch * (3.0 * Cin + 2.0 * p->C));
+    double bytes = 4.0 * pix * (2.0 * p->C + 2.0 * Cin);
+    if (q) {
+        fq.s = f.s; fq.m = f.m;
+        BwdArgs& c = fq.q;
+        c.x = *q->x; c.w1 = q->w1; c.b1 = q->b1; c.w2 = q->w2;
+        c.gy = *q->gy; c.pred = *q->pred; c.target = *q->target; c.mse_scale = q->mse_scale;
+        c.gx = *q->gx; c.gx_accumulate = 0;
+        c.B = s->B; c.Cin = p->C; c.Ch = q->Ch; c.Cout = q->Cout; c.P = a.P;
+        c.tiles_per_sample = p->H;
+        c.Cin_pad = p->C_pad; c.Ch_pad = round_up(q->Ch, 16); c.Cout_pad = round_up(q->Cout, 16);
+        c.slab = q->slab; c.slab_stride = dlwp_pwmlp_slab_stride(p->C, q->Ch, q->Cout); c.slab_accumulate = q->slab_accumulate;
+        c.vec_w = aligned16(q->w1);
+        c.dCin = make_fastdiv(p->C); c.dCh = make_fastdiv(q->Ch);
+        c.vec_x = 1;                      // proj_bwd_fused_lds() has checked the views
+        c.x1_out = q->x1_out; c.FT = p->FT_adj; c.rows_H = p->H; c.m2c = p->m2c;
+        flops += 2.0 * pix * q->Ch * (3.0 * p->C + 2.0 * q->Cout);
+        bytes += 4.0 * pix * (2.0 * p->C + q->Cout);
+    }
+    // one accounting row for both forms of phase 1, with or without the third phase
+    dlwp_prof_scope prof(stream, flops, bytes, "fno_spatial_lift_bwd_kernel<%d, %d, %d>", ncb, nbn, nib);
     int rc;
 #define LAUNCH(N, M, I)                                                                                                 \
     if (role_b) {                                                                                                       \
@@ -1604,15 +1690,29 @@ static int spatial_lift_bwd_launch(const dlwp_fno_plan* p, const dlwp_fno_spatia
         if ((rc = set_lds(fno_spatial_lift_bwd_kernel<N, M, I, false>, lds, "fno_spatial_lift_bwd")) != DLWP_OK) return rc; \
         hipLaunchKernelGGL((fno_spatial_lift_bwd_kernel<N, M, I, false>), grid, dim3(512), lds, stream, f);             \
     }
+#define LAUNCH3(N, I)                                                                                                    \
+    if (role_b) {                                                                                                        \
+        if ((rc = set_lds(fno_spatial_lift_proj_bwd_kernel<N, 1, I>, lds, "fno_spatial_lift_proj_bwd")) != DLWP_OK) return rc; \
+        hipLaunchKernelGGL((fno_spatial_lift_proj_bwd_kernel<N, 1, I>), grid, dim3(512), lds, stream, fq);                \
+    } else {                                                                                                             \
+        if ((rc = set_lds(fno_spatial_lift_proj_bwd_kernel<N, 1, I, false>, lds, "fno_spatial_lift_proj_bwd")) != DLWP_OK) return rc; \
+        hipLaunchKernelGGL((fno_spatial_lift_proj_bwd_kernel<N, 1, I, false>), grid, dim3(512), lds, stream, fq);         \
+    }
 #define ROW(N, M)                                      \
     if (nib == 1) { LAUNCH(N, M, 1) } else { LAUNCH(N, M, 2) }
-    switch (ncb * 10 + nbn) {           // lift_bwd_fused_lds() has refused everything else
+    if (q) switch (ncb * 10 + nib) {    // proj_bwd_fused_lds() has refused everything else (NP == 16: nbn == 1)
+        case 11: LAUNCH3(1, 1) break;
+        case 21: LAUNCH3(2, 1) break; case 22: LAUNCH3(2, 2) break;
+        default: return DLWP_E_UNSUPPORTED;
+    }
+    else switch (ncb * 10 + nbn) {      // lift_bwd_fused_lds() has refused everything else
         case 11: LAUNCH(1, 1, 1) break; case 12: LAUNCH(1, 2, 1) break;
         case 21: ROW(2, 1) break; case 22: ROW(2, 2) break;
         case 31: ROW(3, 1) break; case 32: ROW(3, 2) break;
         default: return DLWP_E_UNSUPPORTED;
     }
 #undef ROW
+#undef LAUNCH3
 #undef LAUNCH
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
@@ -1674,14 +1774,15 @@ static int proj_fwd_launch(const ProjFwdLaunch& q, const dlwp_fno_plan* p, int B
     return DLWP_OK;
 }
 
-// ---- one block: which launch forms, and their sequence.  The only readers of the three FNO knobs.
+// ---- one block: which launch forms, and their sequence.  The only readers of the four FNO knobs.
 // (A narrow plan has 16 | W, one to four channel tiles and one or two frequency tiles -- plan_create_impl -- so every launcher
 // below has an instantiation for what these functions let through.)
 
 // Backward.  hosted: extra workgroups of the per-mode launch (most CUs idle through it) form the skip-weight / bias partials,
 // which need only g_pre and the block's input, into the slab, and `spatial` runs its chain alone -- wherever that `spatial` would
 // have taken the two-role kernel.  Block 0 takes this form only together with its fused lifting launch; where that one is
-// refused it keeps the two-role `spatial`.
+// refused it keeps the two-role `spatial`.  proj: the caller's next launch, the previous net call's projection backward, runs as
+// the third phase of that fused launch (FNO_FUSE_PROJ_BWD); never without it, so FNO_FUSE_LIFT_BWD = 0 switches both off.
 dlwp_fno_forms dlwp_fno_bwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args* a) {
     const bool skip_in_mix = dlwp_tune_or("FNO_SKIP_WGRAD_IN_MIX", 1) != 0, fuse_lift = dlwp_tune_or("FNO_FUSE_LIFT_BWD", 1) != 0;
     const bool slab = a->gslab != nullptr, fits = !dlwp_fno_is_wide(p) && two_role_fits(p);
@@ -1689,13 +1790,17 @@ dlwp_fno_forms dlwp_fno_bwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_
     const dlwp_fno_lift_bwd_tail* t = a->lift;
     const bool can_lift = t && slab && !a->g_wskip && !a->g_bias && !a->act_in && !a->x1_out && t->slab && t->Ch >= 1 &&
                           lift_bwd_fused_lds(p, t->Cin) != 0 && fuse_lift;
-    dlwp_fno_forms d{DLWP_OK, false, DLWP_FNO_SPATIAL_FOUR_WAVE};
+    const bool can_proj = a->proj && can_lift && dlwp_tune_or("FNO_FUSE_PROJ_BWD", 1) != 0 && proj_bwd_fused_lds(p, t->Cin, a->proj) != 0;
+    dlwp_fno_forms d{DLWP_OK, false, DLWP_FNO_SPATIAL_FOUR_WAVE, false};
     bool lift = false;
     switch (a->route) {
         case DLWP_FNO_ROUTE_PLAIN: break;
         case DLWP_FNO_ROUTE_HOSTED: d.hosted = true; if (!can_host) d.rc = DLWP_E_UNSUPPORTED; break;
-        case DLWP_FNO_ROUTE_FUSED_TAIL: lift = true; d.hosted = can_host; if (!can_lift) d.rc = DLWP_E_UNSUPPORTED; break;
-        default: lift = a->first && can_lift; d.hosted = can_host && (!a->first || lift); break;
+        case DLWP_FNO_ROUTE_FUSED_TAIL:         // with a projection tail: forced as well
+            lift = true; d.hosted = can_host; d.proj = a->proj != nullptr;
+            if (!can_lift || (a->proj && !can_proj)) d.rc = DLWP_E_UNSUPPORTED;
+            break;
+        default: lift = a->first && can_lift; d.hosted = can_host && (!a->first || lift); d.proj = lift && can_proj; break;
     }
     if (lift) d.spatial = DLWP_FNO_SPATIAL_FUSED_TAIL;
     else if (!d.hosted && (slab || a->g_wskip) && fits) d.spatial = DLWP_FNO_SPATIAL_TWO_ROLE;   // dlwp_fno_spatial's own choice
@@ -1713,7 +1818,7 @@ dlwp_fno_forms dlwp_fno_fwd_decide(const dlwp_fno_plan* p, const dlwp_fno_block_
     const bool can_fuse = t && a->keep && fuse_proj && !dlwp_fno_is_wide(p) && p->W == PT && p->C_pad <= 48 && !a->x1_out && t->y1 &&
                           t->Ch1 >= 1 && t->Cout1 >= 1 && t->Cout1 <= 8 &&
                           (!second || (p->C_pad <= 32 && p->NP == 16 && t->x1_next && t->y2 && t->Cin2 >= 1 && t->Cin2 <= 64 && t->Ch2 >= 1));
-    dlwp_fno_forms d{DLWP_OK, false, DLWP_FNO_SPATIAL_FOUR_WAVE};
+    dlwp_fno_forms d{DLWP_OK, false, DLWP_FNO_SPATIAL_FOUR_WAVE, false};
     const bool fused = a->route == DLWP_FNO_ROUTE_FUSED_TAIL || (a->route == DLWP_FNO_ROUTE_AUTO && can_fuse);
     if (fused) d.spatial = DLWP_FNO_SPATIAL_FUSED_TAIL;
     if (fused && !can_fuse) d.rc = DLWP_E_UNSUPPORTED;
@@ -1724,6 +1829,7 @@ int dlwp_fno_block_bwd_run(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args
     const dlwp_fno_forms d = dlwp_fno_bwd_decide(p, a);
     if (d.rc) return d.rc;
     const bool fused = d.spatial == DLWP_FNO_SPATIAL_FUSED_TAIL;
+    if (a->proj && a->proj->taken) *a->proj->taken = d.proj;
     int rc;
     if (a->rows_dft && (rc = dlwp_fno_rows_dft(p, a->g_pre, 0, 1, a->x1, a->B, stream))) return rc;
     rc = d.hosted ? mix_bwd_skipgrad_launch(p, a->x1, a->wspec, a->xhat, a->spec, a->g_wspec, a->g_pre, a->x, a->act_in, a->gslab,
@@ -1737,7 +1843,7 @@ int dlwp_fno_block_bwd_run(const dlwp_fno_plan* p, const dlwp_fno_block_bwd_args
     s.gslab_accumulate = a->gslab_accumulate;
     if (!d.hosted) { s.g_wskip = a->g_wskip; s.g_bias = a->g_bias; s.gslab = a->gslab; }
     const dlwp_fno_lift_bwd_tail* t = a->lift;
-    if (fused) return spatial_lift_bwd_launch(p, &s, t, stream);
+    if (fused) return spatial_lift_bwd_launch(p, &s, t, d.proj ? a->proj : nullptr, stream);
     if ((rc = dlwp_fno_spatial(p, &s, stream)) || !t) return rc;
     const int HW = p->H * p->W;
     const dlwp_chan_src gy{a->g_x, (long long)p->C * HW, HW, nullptr, nullptr};
@@ -1868,6 +1974,59 @@ extern "C" int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* p, const float*
                  "fno_block_lift_bwd_slab: needs 64-wide rows, a narrow 2-D plan of at most 48 channels, Cin <= 32 and "
                  "FNO_FUSE_LIFT_BWD != 0 (use dlwp_fno_block_bwd_slab + dlwp_pwmlp_bwd_slab)");
     return rc;
+}
+
+// dlwp_fno_block_lift_bwd_slab with the scalar-output projection backward of the previous net call as the launch's third phase,
+// forced.  px = that call's `pre` [B][C][H W]; gy = its closed-loop gradient plane, one [H W] plane per sample gy_bstride floats
+// apart (in the rollout: a plane of the tensor the lifting phase accumulates into through gx); pred, target [B][1][H W]; gcur
+// [B][C][H W] and x1_out [B][H][m2c][C] complex are overwritten.  DLWP_E_UNSUPPORTED, nothing launched, where the trainer keeps
+// the projection backward on its own launch.
+extern "C" int dlwp_fno_block_lift_proj_bwd_slab(const dlwp_fno_plan* p, const float* h0, const float* wspec, const float* wskip,
+                                                 const float* g_pre, const float* xhat, float* g_wspec, float* slab_skip,
+                                                 int slab_skip_accumulate, const float* x, const float* w1, const float* b1,
+                                                 const float* w2, float* gx, int gx_accumulate, float* slab_lift,
+                                                 int slab_lift_accumulate, int B, int Cin, int Ch, const float* px,
+                                                 const float* pw1, const float* pb1, const float* pw2, const float* gy,
+                                                 long long gy_bstride, const float* pred, const float* target, float mse_scale,
+                                                 const float* gres, float* gcur, float* x1_out, float* slab_proj,
+                                                 int slab_proj_accumulate, int PCh, int PCout, void* workspace, void* stream_) {
+    DLWP_REQUIRE(p && h0 && wspec && wskip && g_pre && xhat && g_wspec && slab_skip && x && w1 && b1 && w2 && slab_lift &&
+                     px && pw1 && pb1 && pw2 && gy && pred && target && gcur && x1_out && slab_proj && workspace && B > 0 &&
+                     Cin > 0 && Ch > 0 && PCh > 0 && PCout > 0,
+                 DLWP_E_INVALID, "fno_block_lift_proj_bwd_slab: NULL argument or non-positive dimension");
+    if (gres) return DLWP_E_UNSUPPORTED;            // a residual path's gradient: the stand-alone launch only
+    const long long P = (long long)p->H * p->W;
+    const dlwp_chan_src xs{x, (long long)Cin * P, P, nullptr, nullptr};
+    const dlwp_chan_dst gxd{gx, (long long)Cin * P, P, nullptr, nullptr};
+    dlwp_fno_lift_bwd_tail t{};
+    t.x = &xs; t.w1 = w1; t.b1 = b1; t.w2 = w2; t.gx = gx ? &gxd : nullptr; t.gx_accumulate = gx_accumulate;
+    t.slab = slab_lift; t.slab_accumulate = slab_lift_accumulate; t.Cin = Cin; t.Ch = Ch;
+    const dlwp_chan_src ps{px, p->C * P, P, nullptr, nullptr}, gys{gy, gy_bstride, P, nullptr, nullptr};
+    const dlwp_chan_src pr{pred, PCout * P, P, nullptr, nullptr}, tg{target, PCout * P, P, nullptr, nullptr};
+    const dlwp_chan_dst gc{gcur, p->C * P, P, nullptr, nullptr};
+    dlwp_fno_proj_bwd_tail q{};
+    q.x = &ps; q.w1 = pw1; q.b1 = pb1; q.w2 = pw2; q.gy = &gys; q.pred = &pr; q.target = &tg; q.mse_scale = mse_scale; q.gx = &gc;
+    q.x1_out = reinterpret_cast<float2*>(x1_out); q.slab = slab_proj; q.slab_accumulate = slab_proj_accumulate; q.Ch = PCh; q.Cout = PCout;
+    dlwp_fno_block_bwd_args a = bwd_entry_args(p, h0, 0, wspec, wskip, g_pre, xhat, nullptr, g_wspec, B, workspace, DLWP_FNO_ROUTE_FUSED_TAIL);
+    a.first = 1; a.gslab = slab_skip; a.gslab_accumulate = slab_skip_accumulate; a.lift = &t; a.proj = &q;
+    return dlwp_fno_block_bwd_run(p, &a, static_cast<hipStream_t>(stream_));
+}
+
+// the second of the two launches dlwp_fno_block_lift_proj_bwd_slab replaces, on the same tensors: the projection backward as the
+// rollout trainer issues it (dlwp_pwmlp_bwd_rows_ex in slab mode with the MSE term and the adjoint rows DFT)
+extern "C" int dlwp_pwmlp_proj_bwd_rows_slab(const dlwp_fno_plan* p, const float* px, const float* pw1, const float* pb1,
+                                             const float* pw2, const float* gy, long long gy_bstride, const float* pred,
+                                             const float* target, float mse_scale, float* gcur, float* x1_out, float* slab_proj,
+                                             int slab_proj_accumulate, int B, int PCh, int PCout, void* stream_) {
+    DLWP_REQUIRE(p && px && pw1 && pb1 && pw2 && gy && pred && target && gcur && x1_out && slab_proj && B > 0 && PCh > 0 && PCout > 0,
+                 DLWP_E_INVALID, "pwmlp_proj_bwd_rows_slab: NULL argument or non-positive dimension");
+    const long long P = (long long)p->H * p->W;
+    const dlwp_chan_src ps{px, p->C * P, P, nullptr, nullptr}, gys{gy, gy_bstride, P, nullptr, nullptr};
+    const dlwp_chan_src pr{pred, PCout * P, P, nullptr, nullptr}, tg{target, PCout * P, P, nullptr, nullptr};
+    const dlwp_chan_dst gc{gcur, p->C * P, P, nullptr, nullptr};
+    return dlwp_pwmlp_bwd_rows_ex(&ps, pw1, pb1, pw2, &gys, &pr, &tg, mse_scale, &gc, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  slab_proj, slab_proj_accumulate, B, p->C, PCh, PCout, (int)P, p, reinterpret_cast<float2*>(x1_out),
+                                  static_cast<hipStream_t>(stream_));
 }
 
 // Test entry points.  dlwp_fno_block_proj_fwd: one FNO block (rows DFT, per-mode stage) whose `spatial` stage is the fused launch:

@@ -257,6 +257,7 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
         if (!fused && (rc = dlwp_zero_f32(tr->g_out, n, s))) return rc;
         mse_scale = 2.0f / (float)n;
     }
+    int proj_taken = 0;              // the projection backward of call k has already run (with call k + 1's block-0 launch)
     for (int k = tr->ncalls - 1; k >= 0; --k) {
         const dlwp_fno_trainer::CallInfo& ci = tr->calls[k];
         const long long oofs = (long long)ci.out_slot * tr->frame;
@@ -278,7 +279,7 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
                                      tr->ap + k * zpB, gcur + (P - HW), tr->act, tr->gz, g.pw1, g.pb1, g.pw2, g.pb2, c.B, C,
                                      c.projection, c.out_channels, HW, s, P, P))) return rc;
             if ((rc = dlwp_fno_rows_dft(tr->plan, gcur, 0, 1, tr->x1, c.B, s))) return rc;
-        } else {
+        } else if (!proj_taken) {
             // upstream = accumulated closed-loop gradient + d MSE / d out[t]
             dlwp_chan_src ps{pre + (NL - 1) * actB, tr->act, HW, nullptr, nullptr};
             dlwp_chan_src gy{tr->g_out + oofs, tr->traj_out, HW, nullptr, nullptr};
@@ -300,6 +301,30 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
         t.x = &xs; t.w1 = w.lw1; t.b1 = w.lb1; t.w2 = w.lw2; t.gx = &gxd; t.gx_accumulate = 1;
         t.gw1 = g.lw1; t.gb1 = g.lb1; t.gw2 = g.lw2; t.gb2 = g.lb2;
         t.slab = tr->slab_lift; t.slab_accumulate = later_call; t.Cin = tr->Cin; t.Ch = c.lifting;
+        // The next launch of the chain, call k - 1's projection backward, works on the same row tiles as block 0's launch and
+        // needs from it only its own rows of g_out: it rides in that launch where the shapes allow (NS form: no residual path;
+        // fused MSE).  What the two share, row for row within one workgroup:
+        //   g_out  the lifting phase adds into slot (k - 1)'s rows, the projection phase reads them behind a workgroup barrier;
+        //   gA     the projection phase writes call k - 1's first gcur; block 0 read its g_pre -- gA when n_layers is odd, gB when
+        //          it is even -- in the launch's first phase, its own row only (the per-mode launch that read all of it is over);
+        //   x1     written by the projection phase, last read by block 0's per-mode launch; `spec` is not touched by it;
+        //   slabs  slab_proj of call k - 1 always accumulates (call ncalls - 1 never rides), slab_lift keeps call k's flag.
+        proj_taken = 0;
+        const bool ride = !tr->wide && k > 0 && !grad_out && c.form == DLWP_FNO_FORM_NS && !tr->calls[k > 0 ? k - 1 : 0].gres;
+        dlwp_chan_src ps1{}, gy1{}, pred1{}, targ1{};
+        dlwp_chan_dst gx1{};
+        dlwp_fno_proj_bwd_tail q{};
+        if (ride) {
+            const long long pofs = (long long)tr->calls[k - 1].out_slot * tr->frame;
+            ps1 = dlwp_chan_src{tr->pre + ((long long)(k - 1) * NL + NL - 1) * actB, tr->act, HW, nullptr, nullptr};
+            gy1 = dlwp_chan_src{tr->g_out + pofs, tr->traj_out, HW, nullptr, nullptr};
+            pred1 = dlwp_chan_src{tr->out + pofs, tr->traj_out, HW, nullptr, nullptr};
+            targ1 = dlwp_chan_src{tr->y + pofs, tr->traj_out, HW, nullptr, nullptr};
+            gx1 = dlwp_chan_dst{tr->gA, tr->act, HW, nullptr, nullptr};
+            q.x = &ps1; q.w1 = w.pw1; q.b1 = w.pb1; q.w2 = w.pw2; q.gy = &gy1; q.pred = &pred1; q.target = &targ1;
+            q.mse_scale = mse_scale; q.gx = &gx1; q.x1_out = tr->x1; q.slab = tr->slab_proj; q.slab_accumulate = 1;
+            q.Ch = c.projection; q.Cout = c.out_channels; q.taken = &proj_taken;
+        }
         for (int l = NL - 1; l >= 0; --l) {
             dlwp_fno_block_bwd_args a{};
             a.g_pre = gcur;
@@ -312,6 +337,7 @@ int enqueue_loss_backward(dlwp_fno_trainer* tr, const float* grad_out, hipStream
             a.x1 = tr->x1; a.spec = tr->spec;
             a.x1_out = l > 0 ? tr->x1 : nullptr;
             a.lift = !tr->wide && l == 0 ? &t : nullptr;
+            a.proj = ride && l == 0 ? &q : nullptr;
             a.B = c.B;
             if ((rc = dlwp_fno_block_bwd_run(tr->plan, &a, s))) return rc;
             float* tmp = gcur; gcur = gnext; gnext = tmp;

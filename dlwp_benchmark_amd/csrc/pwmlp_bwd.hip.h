@@ -1,6 +1,7 @@
 // What the pointwise-MLP backward body (pwmlp_bwd_body.inc.h) needs around it: tile constants, channel views, weight
 // fragments straight from global memory, the pixel-tile staging and the argument block.  Shared by pwmlp.hip and by the
-// fused FNO `spatial` + lifting backward launch of fno_block.hip.
+// fused FNO `spatial` + lifting backward launches of fno_block.hip (the second of which runs the body twice: the lifting backward
+// and the previous net call's projection backward).
 #pragma once
 #include "common.hip.h"
 #include "dlwpmi_internal.h"

@@ -7,6 +7,8 @@
 // depend on the upstream gradient -- the wave's first weight fragments and, there, the first unit of the input tile through the
 // pointer table -- have been requested, so their latency runs under the `spatial` phase (constant PWMLP_BWD_EARLY; false: they are
 // requested at the start of part 2).
+// PWMLP_BWD_BEHIND (without PWMLP_BWD_FUSED): the whole stand-alone text as the third phase of fno_spatial_lift_proj_bwd_kernel,
+// behind another body in the same launch; it adds the one workgroup barrier in front of the first LDS store.
 #if !defined(PWMLP_BWD_PART) || PWMLP_BWD_PART == 1
     constexpr bool SC = NOB == 0;
     constexpr int NB = SC ? 1 : NOB;         // 16-row output blocks of the slab layout and the operand arrays
@@ -77,6 +79,12 @@
 #ifndef PWMLP_BWD_FUSED
     float4 ftv = make_float4(0.f, 0.f, 0.f, 0.f);          // DFT table [16][PT] of the fused rows step
     if (a.x1_out && tid < 16 * (PT / 4)) ftv = reinterpret_cast<const float4*>(a.FT)[tid];
+#endif
+#ifdef PWMLP_BWD_BEHIND
+    // third phase of fno_spatial_lift_proj_bwd_kernel: the LDS below is the lifting phase's until here, and the upstream gradient
+    // rows staged below are the ones this workgroup has just accumulated in global memory.  The weight fragments and the table
+    // requested above depend on neither.
+    __syncthreads();
 #endif
 #ifndef PWMLP_BWD_FUSED
     stage_pixels(xs, a.x, b, a.Cin, a.Cin_pad, p0, a.P, a.vec_x != 0);

@@ -80,6 +80,7 @@ Knob g_knobs[] = {
     {"SPEC_HPX", "dlwp_sphere_spectra on HPX planes: 0 by plane size (default), 1 planes staged in LDS (refused when two planes do not fit), 2 gathered from global memory", 0, false},
     {"ENS_BUCKET", "dlwp_ens_diag, dlwp_crps_loss_fwd_bwd: members held in registers per thread, 8, 16, 32 or 64 (default 0: the smallest that holds M; one below M is refused)", 0, false},
     {"FNO_FUSE_LIFT_BWD","0: block 0's backward `spatial` and the lifting backward of the FNO rollout stay two launches (default 1: one launch, fno_spatial_lift_bwd_kernel, where the shapes allow)", 0, false},
+    {"FNO_FUSE_PROJ_BWD", "0: the projection backward of a net call of the FNO rollout stays its own launch (default 1: it runs as the third phase of the next launch up the chain, the following call's fused block-0 launch, fno_spatial_lift_proj_bwd_kernel, where the shapes allow; needs FNO_FUSE_LIFT_BWD)", 0, false},
     {"FNO_FUSE_PROJ_FWD", "0: the last block's forward `spatial` and the projection (+ next lifting) MLP of the FNO training rollout stay two launches (default 1: one launch, fno_spatial_proj_fwd_kernel, where the shapes allow)", 0, false},
     {"FNO_SKIP_WGRAD_IN_MIX", "0: the backward `spatial` launches of the FNO rollout form their skip-weight / bias gradients themselves (default 1: extra workgroups of the per-mode backward launch form them, fno_mix_bwd_skipgrad_kernel, and `spatial` runs its chain alone, where the shapes allow)", 0, false},
     {"CHAIN_ROT", "0: no rotation of the wave -> feature-tile assignment in the one-launch MLP chains (default 1)", 0, false},

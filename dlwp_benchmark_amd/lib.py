@@ -84,6 +84,9 @@ SIGNATURES = {
     "dlwp_fno_block_proj_fwd": (_I, [_V, _V, _I] + [_V] * 11 + [_I, _I] + [_V] * 7 + [_I, _I, C.c_char_p, _I, _V, _V]),
     "dlwp_pwmlp_proj_lift_fwd": (_I, [_V] * 8 + [_I, _I] + [_V] * 7 + [_I, _I, C.c_char_p, _I, _V]),
     "dlwp_fno_block_lift_bwd_slab": (_I, [_V] * 8 + [_I] + [_V] * 5 + [_I, _V, _I, _I, _I, _I, _V, _V]),
+    "dlwp_fno_block_lift_proj_bwd_slab": (_I, [_V] * 8 + [_I] + [_V] * 5 + [_I, _V, _I, _I, _I, _I] + [_V] * 5 + [_L, _V, _V, _F] +
+                                          [_V] * 4 + [_I, _I, _I, _V, _V]),
+    "dlwp_pwmlp_proj_bwd_rows_slab": (_I, [_V] * 6 + [_L, _V, _V, _F, _V, _V, _V, _I, _I, _I, _I, _V]),
     "dlwp_sqerr_sum": (_I, [_V, _V, _L, _F, _V, _V]),
     "dlwp_mse_fwd_bwd": (_I, [_V, _V, _L, _V, _V, _V]),
     "dlwp_error_moments": (_I, [_V, _V, _V, _V, _I, _I, _I, _I, _V, _V]),

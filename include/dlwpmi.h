@@ -169,6 +169,31 @@ int dlwp_fno_block_lift_bwd_slab(const dlwp_fno_plan* plan, const float* h0, con
                                  const float* w2, float* gx, int gx_accumulate, float* slab_lift,
                                  int slab_lift_accumulate, int B, int Cin, int Ch, void* workspace, void* stream);
 
+/* dlwp_fno_block_lift_bwd_slab with a third phase in the same launch: the scalar-output projection backward of the PREVIOUS net  */
+/* call of a rollout, which works on the same 64-pixel rows and needs from this launch only its own rows of the closed-loop       */
+/* gradient.  px [B][C][H W]: that call's last `pre`; pw1 [PCh][C], pb1 [PCh], pw2 [PCout][PCh]; gy: one [H W] plane per sample,  */
+/* gy_bstride floats apart -- in the rollout a plane of the tensor gx accumulates into (gx_accumulate != 0), read after this      */
+/* launch's own additions; pred, target [B][PCout][H W]: upstream = gy + mse_scale * (pred - target); gcur [B][C][H W] and        */
+/* x1_out [B][H][m2c][C] complex (its adjoint rows DFT) are overwritten; slab_proj: dlwp_pwmlp_slab_floats(B, C, PCh, PCout, H W). */
+/* Outputs bit for bit those of dlwp_fno_block_lift_bwd_slab followed by dlwp_pwmlp_proj_bwd_rows_slab.  DLWP_E_UNSUPPORTED,       */
+/* nothing launched, where the library keeps that launch: whatever dlwp_fno_block_lift_bwd_slab refuses, PCout != 1, gres != NULL */
+/* (a residual path), more than 32 channels, more than 8 kept column frequencies, or the knob FNO_FUSE_PROJ_BWD = 0.              */
+int dlwp_fno_block_lift_proj_bwd_slab(const dlwp_fno_plan* plan, const float* h0, const float* wspec, const float* wskip,
+                                      const float* g_pre, const float* xhat, float* g_wspec, float* slab_skip,
+                                      int slab_skip_accumulate, const float* x, const float* w1, const float* b1,
+                                      const float* w2, float* gx, int gx_accumulate, float* slab_lift,
+                                      int slab_lift_accumulate, int B, int Cin, int Ch, const float* px, const float* pw1,
+                                      const float* pb1, const float* pw2, const float* gy, long long gy_bstride,
+                                      const float* pred, const float* target, float mse_scale, const float* gres, float* gcur,
+                                      float* x1_out, float* slab_proj, int slab_proj_accumulate, int PCh, int PCout,
+                                      void* workspace, void* stream);
+/* The projection backward as the rollout trainer issues it on its own launch (slab mode, MSE term, adjoint rows DFT of the       */
+/* finished gradient rows where the shapes allow, else a separate rows launch): the reference of the entry point above.           */
+int dlwp_pwmlp_proj_bwd_rows_slab(const dlwp_fno_plan* plan, const float* px, const float* pw1, const float* pb1,
+                                  const float* pw2, const float* gy, long long gy_bstride, const float* pred,
+                                  const float* target, float mse_scale, float* gcur, float* x1_out, float* slab_proj,
+                                  int slab_proj_accumulate, int B, int PCh, int PCout, void* stream);
+
 /* The forward of the LAST block fused with the projection MLP on its result, as the training rollout runs it: rows DFT,         */
 /* per-mode stage, then ONE launch for `spatial` + projection (+ the next net call's lifting MLP with its rows DFT) -- the row  */
 /* `spatial` finishes in LDS is the projection's input tile; pre is written, not read back.  pre, xhat as dlwp_fno_block_fwd;   */
