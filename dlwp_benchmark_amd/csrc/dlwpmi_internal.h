@@ -279,15 +279,25 @@ int dlwp_cfmlp_bwd(const float* x, long long x_bs, const float* w1, const float*
                    const float* zpre, const float* act, float* gx, long long gx_bs, float* gz, float* gw1, float* gb1, float* gw2,
                    float* gb2, int B, int Cin, int Ch, int Cout, int P, hipStream_t stream, long long x_cs = 0, long long gx_cs = 0);
 
-// csrc/winattn_small.hip: the wave-per-(window, head) attention kernels for many short windows (<= 128 tokens, head_dim <= 32);
-// dlwp_window_attn_fwd / bwd route to them when dlwp_winattn_small_applies().
-bool dlwp_winattn_small_applies(int N, int d, long long pairs);
-int dlwp_winattn_small_fwd(const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
+// compute units of the current device (256 where it cannot be asked), read once
+inline int dlwp_cu_count() {
+    static const int ncu = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    return ncu;
+}
+
+// csrc/winattn_small.hip: the wave-per-(window, head) and LDS-staged attention kernels for many short windows (<= 128 tokens);
+// the window-layout entries of winattn.hip hand them the calls whose route (winattn_route.h) is not the tiled family.
+// r.io: qkv, out (and gout, gqkv) are bf16 arrays in the window layout.
+struct WaRoute;
+int dlwp_winattn_small_fwd(const WaRoute& r, const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
                            const int* labels, float* out, float* lse, int B_, int nW, int N, int TB, int ntypes, int heads, int d,
-                           float scale, int q_lo, int q_hi, void* stream, int io_bf16 = 0);
-// io_bf16: qkv, out (and gout, gqkv) are bf16 arrays in the window layout (dlwp_winattn_io_bf16_applies must hold)
-bool dlwp_winattn_io_bf16_applies(int N, int d, int TB, long long pairs);
-int dlwp_winattn_small_bwd(const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
+                           float scale, int q_lo, int q_hi, void* stream);
+int dlwp_winattn_small_bwd(const WaRoute& r, const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
                            const int* labels, const float* out, const float* lse, const float* gout, float* gqkv, float* gtable,
-                           int B_, int nW, int N, int TB, int ntypes, int heads, int d, float scale, int q_lo, int q_hi, void* stream,
-                           int io_bf16 = 0);
+                           int B_, int nW, int N, int TB, int ntypes, int heads, int d, float scale, int q_lo, int q_hi, void* stream);
+// the accounting name of the route's instantiation (any family of that file)
+int dlwp_winattn_small_name(const WaRoute& r, char* buf, int n);

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include "common.hip.h"
 #include "dlwpmi_internal.h"
+#include "winattn_route.h"
 
 namespace {
 
@@ -574,6 +575,15 @@ int wa_setup(WaDev& a, int B_, int nW, int N, int TB, int ntypes, int heads, int
     return DLWP_OK;
 }
 
+// the tiled family's dispatcher (winattn_route.h): the three kernel templates share one parameter space <NDB, NBUF, BF>
+template <class F>
+int tiled_inst(const WaRoute& r, F&& f) {
+    return wa_consts([&](auto NDB, auto NBUF, auto BF) {
+        return f(WA_INST(winattn_fwd_kernel, WA_C(NDB), WA_C(NBUF), WA_B(BF)), WA_INST(winattn_bwd_q_kernel, WA_C(NDB), WA_C(NBUF), WA_B(BF)),
+                 WA_INST(winattn_bwd_kv_kernel, WA_C(NDB), WA_C(NBUF), WA_B(BF)));
+    }, WaOneOf<1, 2, 3, 4>{r.ndb}, WaOneOf<1, 2>{r.n2}, WaBool{r.bf});
+}
+
 }  // namespace
 
 namespace {
@@ -624,34 +634,19 @@ extern "C" int dlwp_window_attn_fwd_qrange(const float* qkv, const float* bias_t
     a.table_t = packed_table;
     int rc = wa_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, "window_attn_fwd");
     if (rc) return rc;
-    if (dlwp_winattn_small_applies(N, d, (long long)B_ * heads) && !dlwp_tune_on("WINATTN_TILED"))
-        return dlwp_winattn_small_fwd(qkv, bias_table, packed_table, ia, ib, labels, out, lse, B_, nW, N, TB, ntypes, heads, d,
+    const WaRoute r = dlwp_winattn_route_fwd(WaCall{0, N, d, TB, (long long)B_ * heads, q_lo, q_hi});
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
+    if (r.family != WA_TILED)
+        return dlwp_winattn_small_fwd(r, qkv, bias_table, packed_table, ia, ib, labels, out, lse, B_, nW, N, TB, ntypes, heads, d,
                                       scale, q_lo, q_hi, stream);
     a.qkv = qkv; a.table = bias_table; a.ia = ia; a.ib = ib; a.labels = labels; a.out = out; a.lse = lse;
-    const int nbuf = N <= 128 ? 1 : 2;         // short windows: single-buffered tiles, more workgroups per CU
+    const int nbuf = r.n2;                     // short windows (N <= 128): single-buffered tiles, more workgroups per CU
     const size_t lds = sizeof(float) * ((size_t)(1 + nbuf) * 64 * (a.dp16 + 4) + (size_t)nbuf * a.dp16 * LDV + 256 + a.TB);
     const dim3 grid(B_ * heads * ((N + QT - 1) / QT)), block(256);
-    const bool bf = dlwp_get_gemm_precision() == 1;      // bf16 matrix arithmetic asked for: bf16 MFMA operands, fp32 everything else
-#define WA_FWD_B(NDB, NB, BFV)                                                                                                \
-    do {                                                                                                                  \
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(winattn_fwd_kernel<NDB, NB, BFV>), lds, "window_attn_fwd"))) return rc; \
-        dlwp_prof_scope prof((hipStream_t)stream, 2 * 2.0 * B_ * heads * (double)N * N * d, 4.0 * B_ * N * heads * d * 4 + 4.0 * B_ * heads * N, \
-                             "winattn_fwd_kernel<%d, %d, %s>", NDB, NB, BFV ? "true" : "false");                             \
-        hipLaunchKernelGGL((winattn_fwd_kernel<NDB, NB, BFV>), grid, block, lds, (hipStream_t)stream, a);               \
-    } while (0)
-#define WA_FWD(NDB)                                                                                                       \
-    do {                                                                                                                  \
-        if (bf) { if (nbuf == 1) WA_FWD_B(NDB, 1, true); else WA_FWD_B(NDB, 2, true); }                                   \
-        else { if (nbuf == 1) WA_FWD_B(NDB, 1, false); else WA_FWD_B(NDB, 2, false); }                                    \
-    } while (0)
-    switch (a.dp16 / 16) {
-        case 1: WA_FWD(1); break;
-        case 2: WA_FWD(2); break;
-        case 3: WA_FWD(3); break;
-        default: WA_FWD(4); break;
-    }
-#undef WA_FWD_B
-#undef WA_FWD
+    rc = tiled_inst(r, [&](auto fwd, auto, auto) {
+        return wa_launch(fwd, grid, block, lds, 2 * 2.0 * B_ * heads * (double)N * N * d, 4.0 * B_ * N * heads * d * 4 + 4.0 * B_ * heads * N, stream, a);
+    });
+    if (rc) return rc;
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
@@ -661,7 +656,7 @@ extern "C" int dlwp_window_attn_fwd_qrange(const float* qkv, const float* bias_t
 // the casts between them and the attention kernels disappear (Swin C4: eight cast launches over 20 - 80 MB each per step).  Where
 // dlwp_window_attn_io_bf16_supported() says so: windows of at most 64 tokens, head_dim % 4 == 0, bf16 matrix mode, the whole query range.
 extern "C" int dlwp_window_attn_io_bf16_supported(int N, int d, int TB, long long pairs) {
-    return dlwp_winattn_io_bf16_applies(N, d, TB, pairs) ? 1 : 0;
+    return dlwp_winattn_route_bwd(WaCall{WA_IO_BF16, N, d, TB, pairs, 0, N}).family != WA_NONE ? 1 : 0;
 }
 extern "C" int dlwp_window_attn_fwd_bf16(const void* qkv, const float* bias_table, const float* packed_table, const int* ia, const int* ib,
                                          const int* labels, void* out, float* lse, int B_, int nW, int N, int TB, int ntypes, int heads,
@@ -670,11 +665,11 @@ extern "C" int dlwp_window_attn_fwd_bf16(const void* qkv, const float* bias_tabl
     WaDev a{};
     int rc = wa_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, "window_attn_fwd_bf16");
     if (rc) return rc;
-    DLWP_REQUIRE(dlwp_winattn_io_bf16_applies(N, d, TB, (long long)B_ * heads), DLWP_E_UNSUPPORTED,
-                 "window_attn_fwd_bf16: needs windows of at most 64 tokens, head_dim %% 4 == 0 and the bf16 matrix mode (N %d, d %d)", N, d);
+    const WaRoute r = dlwp_winattn_route_fwd(WaCall{WA_IO_BF16, N, d, TB, (long long)B_ * heads, 0, N});
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
     DLWP_REQUIRE((uintptr_t)qkv % 8 == 0 && (uintptr_t)out % 8 == 0, DLWP_E_INVALID, "window_attn_fwd_bf16: 8-byte aligned tensors");
-    return dlwp_winattn_small_fwd(static_cast<const float*>(qkv), bias_table, packed_table, ia, ib, labels, static_cast<float*>(out), lse, B_, nW, N,
-                                  TB, ntypes, heads, d, scale, 0, N, stream, 1);
+    return dlwp_winattn_small_fwd(r, static_cast<const float*>(qkv), bias_table, packed_table, ia, ib, labels, static_cast<float*>(out), lse, B_, nW,
+                                  N, TB, ntypes, heads, d, scale, 0, N, stream);
 }
 extern "C" int dlwp_window_attn_bwd_bf16(const void* qkv, const float* bias_table, const float* packed_table, const int* ia, const int* ib,
                                          const int* labels, const void* out, const float* lse, const void* gout, void* gqkv,
@@ -686,9 +681,11 @@ extern "C" int dlwp_window_attn_bwd_bf16(const void* qkv, const float* bias_tabl
     if (rc) return rc;
     DLWP_REQUIRE((uintptr_t)qkv % 8 == 0 && (uintptr_t)out % 8 == 0 && (uintptr_t)gout % 8 == 0 && (uintptr_t)gqkv % 8 == 0, DLWP_E_INVALID,
                  "window_attn_bwd_bf16: 8-byte aligned tensors");
-    return dlwp_winattn_small_bwd(static_cast<const float*>(qkv), bias_table, packed_table, ia, ib, labels, static_cast<const float*>(out), lse,
+    const WaRoute r = dlwp_winattn_route_bwd(WaCall{WA_IO_BF16, N, d, TB, (long long)B_ * heads, 0, N});
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
+    return dlwp_winattn_small_bwd(r, static_cast<const float*>(qkv), bias_table, packed_table, ia, ib, labels, static_cast<const float*>(out), lse,
                                   static_cast<const float*>(gout), static_cast<float*>(gqkv), gbias_table, B_, nW, N, TB, ntypes, heads, d, scale,
-                                  0, N, stream, 1);
+                                  0, N, stream);
 }
 
 extern "C" int dlwp_window_attn_fwd(const float* qkv, const float* bias_table, const int* ia, const int* ib,
@@ -708,7 +705,8 @@ extern "C" int dlwp_window_attn_bwd_packed(const float* qkv, const float* bias_t
 
 // backward of dlwp_window_attn_fwd_qrange: `gout` rows outside [q_lo, q_hi) are taken as zero (they are: the caller crops those
 // tokens); the query gradient of those rows is written as zero, their key / value gradients are complete.  The tiled kernels
-// read every row of `out` / `lse` / `gout`: with them the forward must have been the tiled one too (same dispatch rule).
+// read every row of `out` / `lse` / `gout`: with them the forward must have been the tiled one too, which the routes guarantee
+// (small_family() in winattn_small.hip is the one question both directions ask).
 extern "C" int dlwp_window_attn_bwd_qrange(const float* qkv, const float* bias_table, const float* packed_table, const int* ia,
                                            const int* ib, const int* labels, const float* out, const float* lse,
                                            const float* gout, float* gqkv, float* gbias_table, float* dsum, float* slab, int B_,
@@ -721,55 +719,57 @@ extern "C" int dlwp_window_attn_bwd_qrange(const float* qkv, const float* bias_t
     a.table_t = packed_table;
     int rc = wa_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, "window_attn_bwd");
     if (rc) return rc;
-    if (dlwp_winattn_small_applies(N, d, (long long)B_ * heads) && !dlwp_tune_on("WINATTN_TILED"))
-        return dlwp_winattn_small_bwd(qkv, bias_table, packed_table, ia, ib, labels, out, lse, gout, gqkv, gbias_table, B_, nW, N,
+    const WaRoute r = dlwp_winattn_route_bwd(WaCall{0, N, d, TB, (long long)B_ * heads, q_lo, q_hi});
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
+    if (r.family != WA_TILED)
+        return dlwp_winattn_small_bwd(r, qkv, bias_table, packed_table, ia, ib, labels, out, lse, gout, gqkv, gbias_table, B_, nW, N,
                                       TB, ntypes, heads, d, scale, q_lo, q_hi, stream);
     a.qkv = qkv; a.table = bias_table; a.ia = ia; a.ib = ib; a.labels = labels; a.o = out; a.lse_in = lse; a.gout = gout; a.gqkv = gqkv;
     a.gtable = gbias_table; a.dsum = dsum; a.slab = slab;
-    const int LDT = a.dp16 + 4;
-    const int nbuf = N <= 128 ? 1 : 2;
+    const int LDT = a.dp16 + 4, nbuf = r.n2;
     const size_t lds_q = sizeof(float) * ((size_t)2 * nbuf * 64 * LDT + (size_t)nbuf * a.dp16 * LDV + 256 + 3 * (size_t)((a.TB + 1) & ~1));
     const size_t lds_kv = sizeof(float) * ((size_t)2 * nbuf * 64 * LDT + (size_t)2 * nbuf * a.dp16 * LDV + 512 + a.TB);
     const dim3 grid(B_ * heads * ((N + QT - 1) / QT)), block(256);
-    const bool bf = dlwp_get_gemm_precision() == 1;
-#define WA_BWD_B(NDB, NB, BFV)                                                                                                   \
-    do {                                                                                                                     \
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(winattn_bwd_q_kernel<NDB, NB, BFV>), lds_q, "window_attn_bwd"))) return rc;  \
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(winattn_bwd_kv_kernel<NDB, NB, BFV>), lds_kv, "window_attn_bwd"))) return rc; \
-        {   /* live accounting: the pair computes the five products of the backward once; q reads qkv, out, gout, writes gq */ \
-            dlwp_prof_scope prof((hipStream_t)stream, 2.5 * 2.0 * B_ * heads * (double)N * N * d, 4.0 * B_ * N * heads * d * 6,    \
-                                 "winattn_bwd_q_kernel<%d, %d, %s>", NDB, NB, BFV ? "true" : "false");                          \
-            hipLaunchKernelGGL((winattn_bwd_q_kernel<NDB, NB, BFV>), grid, block, lds_q, (hipStream_t)stream, a);          \
-        }                                                                                                                    \
-        {                                                                                                                    \
-            dlwp_prof_scope prof((hipStream_t)stream, 2.5 * 2.0 * B_ * heads * (double)N * N * d, 4.0 * B_ * N * heads * d * 6,    \
-                                 "winattn_bwd_kv_kernel<%d, %d, %s>", NDB, NB, BFV ? "true" : "false");                         \
-            hipLaunchKernelGGL((winattn_bwd_kv_kernel<NDB, NB, BFV>), grid, block, lds_kv, (hipStream_t)stream, a);        \
-        }                                                                                                                    \
-    } while (0)
-#define WA_BWD(NDB)                                                                                                          \
-    do {                                                                                                                     \
-        if (bf) { if (nbuf == 1) WA_BWD_B(NDB, 1, true); else WA_BWD_B(NDB, 2, true); }                                      \
-        else { if (nbuf == 1) WA_BWD_B(NDB, 1, false); else WA_BWD_B(NDB, 2, false); }                                       \
-    } while (0)
-    switch (a.dp16 / 16) {
-        case 1: WA_BWD(1); break;
-        case 2: WA_BWD(2); break;
-        case 3: WA_BWD(3); break;
-        default: WA_BWD(4); break;
-    }
-#undef WA_BWD_B
-#undef WA_BWD
+    // live accounting: the pair computes the five products of the backward once; q reads qkv, out, gout, writes gq
+    const double flops = 2.5 * 2.0 * B_ * heads * (double)N * N * d, bytes = 4.0 * B_ * N * heads * d * 6;
+    rc = tiled_inst(r, [&](auto, auto q, auto kv) {
+        if (int rc2 = wa_launch(q, grid, block, lds_q, flops, bytes, stream, a)) return rc2;
+        return wa_launch(kv, grid, block, lds_kv, flops, bytes, stream, a);
+    });
+    if (rc) return rc;
     if (slab) {
         const int nqt = (N + QT - 1) / QT, n_items = (B_ / ntypes) * nqt, chunks = (n_items + FOLD_CH - 1) / FOLD_CH;
         // live accounting: one add per slab partial; the slab is read once, every chunk adds its sums into the table
-        dlwp_prof_scope prof((hipStream_t)stream, (double)n_items * heads * ntypes * TB,
-                             4.0 * n_items * heads * ntypes * TB + 8.0 * chunks * TB * ntypes * heads, "winattn_fold_kernel");
-        hipLaunchKernelGGL(winattn_fold_kernel, dim3((TB + 255) / 256, heads * ntypes, (n_items + FOLD_CH - 1) / FOLD_CH),
-                           dim3(256), 0, (hipStream_t)stream, slab, gbias_table, TB, ntypes, heads, nqt, n_items);
+        rc = wa_launch(wa_inst(winattn_fold_kernel, wa_name("winattn_fold_kernel")), dim3((TB + 255) / 256, heads * ntypes, chunks), dim3(256), 0,
+                       (double)n_items * heads * ntypes * TB, 4.0 * n_items * heads * ntypes * TB + 8.0 * chunks * TB * ntypes * heads, stream,
+                       slab, gbias_table, TB, ntypes, heads, nqt, n_items);
+        if (rc) return rc;
     }
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
+}
+
+// debug entry: the accounting name(s) of the launch a call of that shape would make, ';'-separated (direction 0: forward, 1:
+// backward; layout: 0 fp32 arrays in the window layout, bit 0 token-layout entries, bit 1 with fill, bit 2 bf16 tensors), through
+// the routes and the name formatter the launches use.  Host state only: no device is touched.
+extern "C" int dlwp_window_attn_route_name(int direction, int layout, int N, int d, int TB, long long pairs, int q_lo, int q_hi, char* buf,
+                                           int n) {
+    DLWP_REQUIRE(buf && n > 0 && (direction == 0 || direction == 1) && layout >= 0 && layout < 8 && N > 0 && d > 0 && TB > 0 && pairs > 0,
+                 DLWP_E_INVALID, "window_attn_route_name: bad argument");
+    DLWP_REQUIRE(q_lo >= 0 && q_hi <= N && q_lo < q_hi, DLWP_E_INVALID, "window_attn_route_name: query range [%d, %d) outside [0, %d)", q_lo, q_hi, N);
+    const WaCall c{layout, N, d, TB, pairs, q_lo, q_hi};
+    const WaRoute r = direction ? dlwp_winattn_route_bwd(c) : dlwp_winattn_route_fwd(c);
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
+    if (r.family != WA_TILED) return dlwp_winattn_small_name(r, buf, n);
+    return tiled_inst(r, [&](auto fwd, auto q, auto kv) {
+        if (!direction) {
+            wa_format(fwd.name, buf, (size_t)n);
+        } else {
+            const int len = wa_format(q.name, buf, (size_t)n);
+            if (len + 1 < n) { buf[len] = ';'; wa_format(kv.name, buf + len + 1, (size_t)(n - len - 1)); }
+        }
+        return DLWP_OK;
+    });
 }
 
 extern "C" int dlwp_window_attn_bwd(const float* qkv, const float* bias_table, const int* ia, const int* ib,

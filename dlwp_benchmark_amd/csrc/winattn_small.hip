@@ -22,7 +22,9 @@
 //   dP^T = V dO^T,  dS^T = P^T (dP^T - D),  dQ^T += K^T dS^T ;   dP = dO V^T,  dS = P (dP - D),  dV^T += dO^T P,  dK^T += Q^T dS.
 // dBias partials are summed per workgroup in LDS (64-bit fixed point, see winattn.hip) and flushed with float atomics.
 //
-// Families in this file (dispatch: dlwp_winattn_small_fwd / _bwd and the token-layout entries at the end):
+// Families in this file.  Which one a call runs on, and on which instantiation, is decided by dlwp_winattn_route_fwd / _bwd below
+// (winattn_route.h: shape, layout, precision mode and the WINATTN_* knobs -> WaRoute; the tiled family of winattn.hip is one of
+// their answers); ws_launch turns a route into launch geometry and wa_launch launches it:
 //   winattn_small_fwd_kernel<NC, NDB, VEC, BF, TOK, IOBF>   forward, one wave per (window, head); TOK: operands in the token layout
 //                                                           through position maps; IOBF: bf16 token tensors
 //   winattn_small_bwd_kernel                                backward, register fragments (fp32 mode, or forced)
@@ -34,6 +36,7 @@
 #include <type_traits>
 #include "common.hip.h"
 #include "dlwpmi_internal.h"
+#include "winattn_route.h"
 
 namespace {
 
@@ -1321,26 +1324,17 @@ __global__ __launch_bounds__(64 * NW) void winattn_lds_bwd1p_kernel(WsDev a) {
 // with the same number of windows.  Round 6, Swin C4 in the step: stage 0 (5624 (window, head) pairs) 112.6 us at the 1536 workgroups of
 // rounds 3 - 5 (1.5 rounds, 3 or 4 windows each), 101 - 102 us at 960 - 1024; stage 1 (1520 pairs, head dim 48, three waves per SIMD) 64 us
 // at 1520 (one window each: the table staging and flush of a workgroup paid per window, a partial second round), 59 at 768.
-static int lds_groups(int M, int heads, int ntypes, int occ) {
-    const int env = dlwp_tune_or("WINATTN_WG_BWD", 0);
-    if (env) {
-        const long long g = ((long long)env + heads * ntypes - 1) / (heads * ntypes);
-        return g < 1 ? 1 : (g > M ? M : (int)g);
-    }
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    const long long pairs = (long long)M * heads * ntypes, slots = (long long)ncu * occ;
+static long long lds_groups(int M, int heads, int ntypes, int occ) {
+    const long long pairs = (long long)M * heads * ntypes, slots = (long long)dlwp_cu_count() * occ;
     const int per_wg = (int)((pairs + slots - 1) / slots);          // windows per workgroup
     return (M + per_wg - 1) / per_wg;
 }
-
-// the LDS-staged family takes the bf16 matrix mode with 16-byte loadable head slices
-static bool lds_family_applies(int N, int d) {
-    // head dims 33 .. 48: the two-pass backward only (windows of at most 64 tokens), see LDB48
-    return dlwp_get_gemm_precision() == 1 && d % 4 == 0 && (d <= 32 || (d <= 48 && N <= 64)) && N <= 128 && !dlwp_tune_on("WINATTN_NOLDS");
+// workgroups per (window type, head) of a kernel whose workgroups walk several windows: the knob's total count shared among the
+// (type, head) pairs, else the kernel's own figure `own`; at least one, at most one per window
+static int groups_of(const char* knob, long long own, int M, int heads, int ntypes) {
+    const int want = dlwp_tune_or(knob, 0);
+    const long long per = want ? ((long long)want + heads * ntypes - 1) / (heads * ntypes) : own;
+    return per < 1 ? 1 : (per > M ? M : (int)per);
 }
 
 int ws_setup(WsDev& a, int B_, int nW, int N, int TB, int ntypes, int heads, int d, float scale, int q_lo, int q_hi) {
@@ -1538,213 +1532,221 @@ __global__ __launch_bounds__(256) void winattn_lds_fwd_tok_kernel(WsDev a) {
     }
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------------ routes
+WaRoute wa_unsupported(const char* why, long long arg = 0) { return WaRoute{WA_NONE, 0, 0, false, false, false, false, why, arg}; }
+WaRoute wa_route(WaFamily family, int n2, int ndb, bool vec, bool bf, bool tok, bool io) { return WaRoute{family, n2, ndb, vec, bf, tok, io, nullptr, 0}; }
+const char* const WA_WIDE = "window attention: head_dim above 64 needs the GEMM form (dlwp_window_softmax_fwd/bwd) (N %d, d %d)";
 
-// Shapes this family takes: at most 128 tokens per window, head_dim <= 32, and enough (window, head) pairs that one wave per
-// pair fills the chip -- a single wave walks its pairs of 16 x 16 tiles serially (L1 / L2 latency per step, one prefetch deep),
-// so with few windows the tiled kernels of winattn.hip (a workgroup per 64 queries) finish sooner.  Measured
+// The rules.  Each WINATTN_* knob that decides a route and the precision mode are read in ONE of these functions, and the two
+// route functions below are the only callers.
+bool bf16_mode() { return dlwp_get_gemm_precision() == 1; }      // bf16 matrix arithmetic asked for: bf16 MFMA operands
+bool lds_off() { return dlwp_tune_on("WINATTN_NOLDS"); }
+// Shapes the wave-per-window family takes: at most 128 tokens per window, head_dim <= 32, and enough (window, head) pairs that one
+// wave per pair fills the chip -- a single wave walks its pairs of 16 x 16 tiles serially (L1 / L2 latency per step, one prefetch
+// deep), so with few windows the tiled kernels of winattn.hip (a workgroup per 64 queries) finish sooner.  Measured
 // (profiles/r02_winattn_probe.txt, forward / backward us, tiled -> this family):  1406 windows x 4 heads, N = 49, d = 24:
 // 86 / 264 -> 54 / 249;  703 x 6, N = 98, d = 32: 193 / 727 -> 149 / 643;  100 x 4, N = 49, d = 10: 8 / 26 -> 11 / 51.
+// Round 6: head dims up to 48 for windows of at most 64 tokens in the bf16 matrix mode (Swin C4 stage 1: 49 tokens, head dim 48, 1520 pairs at
+// batch 2: tiled kernels 36 + 106 us forward + backward per block, this family 12 + 31 us) -- from WINATTN_SMALL_MIN_PAIRS pairs (default 1024).
+bool wave_shape(int N, int d, long long pairs) {
+    if (N <= 128 && d <= 32 && pairs >= 2048) return true;
+    return dlwp_tune_or("WINATTN_D48", 1) != 0 && N <= 64 && d <= 48 && d % 4 == 0 && bf16_mode() && !lds_off() &&
+           pairs >= dlwp_tune_or("WINATTN_SMALL_MIN_PAIRS", 1024);
+}
+// FORWARD AND BACKWARD AGREE: both routes ask this one question, so a shape's two directions are either both tiled or both not.
+// They have to: the tiled backward reads every row of out / lse / gout, and only the tiled forward writes every row (the other
+// families skip the query chunks outside the caller's range).
+bool small_family(const WaCall& c) { return wave_shape(c.N, c.d, c.pairs) && !dlwp_tune_on("WINATTN_TILED"); }
+// the LDS-staged family takes the bf16 matrix mode with 16-byte loadable head slices
+// (head dims 33 .. 48: the two-pass backward only, windows of at most 64 tokens, see LDB48)
+bool lds_shape(int N, int d) { return bf16_mode() && d % 4 == 0 && (d <= 32 || (d <= 48 && N <= 64)) && N <= 128 && !lds_off(); }
+// the one-pass backward (round 4) wherever its LDS image fits and the table slice fits the staging area it is folded in.
+// Windows of at most 64 tokens (Swin's 49: four key chunks, the 4-wave instantiation) stay on the two-pass kernel unless asked for:
+// with ~4 windows per workgroup the per-workgroup fold of the dense image (2401 LDS float atomics onto 169 table slots) outweighs
+// the saved score evaluations -- Swin C4 step 6.74 ms one-pass vs 6.59 ms two-pass, same box, back to back.
+bool one_pass(int N, int d, int TB) {
+    const int nc = (N + 15) / 16;
+    if (d > 32) return false;
+    if (nc <= 4 && !dlwp_tune_on("WINATTN_BWD1P_SMALL")) return false;
+    return lds_shape(N, d) && lds2_bytes(16 * nc, TB) <= 160 * 1024 && (size_t)TB * 4 <= (size_t)4 * 16 * nc * LDB * 2 &&
+           !dlwp_tune_on("WINATTN_BWD2PASS");
+}
+
+}  // namespace
+
+WaRoute dlwp_winattn_route_bwd(const WaCall& c) {
+    const int N = c.N, d = c.d, nc = (N + 15) / 16, ndb2 = d <= 16 ? 1 : 2;
+    const bool io = (c.layout & WA_IO_BF16) != 0;
+    if (c.layout & WA_TOKENS) {          // gradients in the token layout: the one-pass kernel or nothing
+        if (!one_pass(N, d, c.TB))
+            return wa_unsupported("window_attn_bwd_tokens: needs the bf16 matrix mode, N <= 128, head_dim <= 32 and %% 4 == 0 (N %d, d %d, table %lld)", c.TB);
+        return wa_route(WA_LDS_BWD1P, nc > 4 ? 8 : 4, ndb2, true, true, true, io);
+    }
+    WaRoute r;                           // fp32 arrays in the window layout
+    if (d > 64) r = wa_unsupported(WA_WIDE);
+    else if (!small_family(c)) r = wa_route(WA_TILED, N <= 128 ? 1 : 2, (d + 15) / 16, false, bf16_mode(), false, false);
+    else if (one_pass(N, d, c.TB)) r = wa_route(WA_LDS_BWD1P, nc > 4 ? 8 : 4, ndb2, true, true, false, false);
+    else if (lds_shape(N, d)) r = wa_route(WA_LDS_BWD2, 0, d <= 32 ? ndb2 : 3, true, true, false, false);
+    else r = wa_route(WA_WAVE_BWD, 0, ndb2, d % 4 == 0, bf16_mode(), false, false);
+    if (!io) return r;
+    // bf16 tensors in the WINDOW layout (round 6: qkv, out, gout, gqkv all bf16 arrays; dlwp_window_attn_fwd_bf16 / _bwd_bf16): where
+    // fp32 arrays of the shape take the two-pass LDS-staged backward (which stages bf16 rows and writes the gradient as bf16; with it
+    // goes the wave-per-window forward on raw bf16 fragments) and the window has at most 64 tokens
+    if (r.family != WA_LDS_BWD2 || N > 64)
+        return wa_unsupported("window attention backward: bf16 tensors in the window layout need windows of at most 64 tokens in the bf16 matrix mode (N %d, d %d)");
+    r.io = true;
+    return r;
+}
+
+WaRoute dlwp_winattn_route_fwd(const WaCall& c) {
+    const int N = c.N, d = c.d, NC = N <= 64 ? 4 : 8, ndb2 = d <= 16 ? 1 : 2;
+    const bool io = (c.layout & WA_IO_BF16) != 0;
+    if (c.layout & WA_TOKENS) {          // operands and output in the token layout
+        if (!(d <= 32 && c.pairs >= 2048 && d % 4 == 0 && bf16_mode() && small_family(c)))
+            return wa_unsupported("window_attn_fwd_tokens: needs the bf16 matrix mode, N <= 128, head_dim <= 32 and %% 4 == 0, at least 2048 (window, head) pairs "
+                                  "(N %d, d %d, pairs %lld)", c.pairs);
+        // the LDS-staged forward by default: 43 vs 56 us per launch in the Pangu C4 step
+        if (dlwp_tune_or("WINATTN_FWD_LDS", 1)) return wa_route(WA_LDS_FWD_TOK, NC, ndb2, true, true, true, io);
+        return wa_route(WA_WAVE_FWD, NC, ndb2, true, true, true, io);
+    }
+    if (io) {                            // bf16 tensors in the window layout: wherever their backward exists
+        if (dlwp_winattn_route_bwd(c).family == WA_NONE)
+            return wa_unsupported("window_attn_fwd_bf16: needs windows of at most 64 tokens, head_dim %% 4 == 0 and the bf16 matrix mode (N %d, d %d)");
+        return wa_route(WA_WAVE_FWD, 4, (d + 15) / 16, true, true, false, true);
+    }
+    if (d > 64) return wa_unsupported(WA_WIDE);
+    if (!small_family(c)) return wa_route(WA_TILED, N <= 128 ? 1 : 2, (d + 15) / 16, false, bf16_mode(), false, false);
+    // head dims 33 .. 48 (bf16 matrix mode, windows of at most 64 tokens: wave_shape) have the one instantiation <4, 3, true, true>
+    if (d > 32) return wa_route(WA_WAVE_FWD, 4, 3, true, true, false, false);
+    return wa_route(WA_WAVE_FWD, NC, ndb2, d % 4 == 0, bf16_mode(), false, false);
+}
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ instantiations
+// One dispatch per kernel template: the route's integers become compile-time constants (wa_consts) and f receives the instantiation
+// with its accounting name (WA_INST).
+template <class F>
+int ws_inst(const WaRoute& r, F&& f) {
+    const WaOneOf<1, 2> ndb_12{r.ndb};
+    const WaOneOf<4, 8> n2_48{r.n2};
+    switch (r.family) {
+        case WA_WAVE_FWD:
+            return wa_consts([&](auto NC, auto NDB, auto VEC, auto BF, auto TOK, auto IO) {
+                constexpr int nc = WA_C(NC), ndb = WA_C(NDB);
+                constexpr bool vec = WA_B(VEC), bf = WA_B(BF), tok = WA_B(TOK), io = WA_B(IO);
+                // what the routes can reach, and no more: head dims above 32 are <4, 3, true, true, false, .>; the token layout and bf16
+                // tensors take vector loads of bf16 operands, and bf16 tensors in the window layout have at most 64 tokens
+                constexpr bool live = ndb == 3 ? (nc == 4 && vec && bf && !tok) : (tok || io) ? (vec && bf && (tok || nc == 4)) : true;
+                if constexpr (live) return f(WA_INST(winattn_small_fwd_kernel, nc, ndb, vec, bf, tok, io));
+                else return wa_not_built();
+            }, n2_48, WaOneOf<1, 2, 3>{r.ndb}, WaBool{r.vec}, WaBool{r.bf}, WaBool{r.tok}, WaBool{r.io});
+        case WA_WAVE_BWD:
+            return wa_consts([&](auto NDB, auto VEC, auto BF) { return f(WA_INST(winattn_small_bwd_kernel, WA_C(NDB), WA_B(VEC), WA_B(BF))); },
+                             ndb_12, WaBool{r.vec}, WaBool{r.bf});
+        case WA_LDS_BWD2:
+            return wa_consts([&](auto NDB) { return f(WA_INST(winattn_lds_bwd_kernel, WA_C(NDB))); }, WaOneOf<1, 2, 3>{r.ndb});
+        case WA_LDS_BWD1P:
+            return wa_consts([&](auto NDB, auto NW, auto IO) { return f(WA_INST(winattn_lds_bwd1p_kernel, WA_C(NDB), WA_C(NW), WA_B(IO))); },
+                             ndb_12, n2_48, WaBool{r.io});
+        case WA_LDS_FWD_TOK:
+            return wa_consts([&](auto NC, auto NDB, auto IO) { return f(WA_INST(winattn_lds_fwd_tok_kernel, WA_C(NC), WA_C(NDB), WA_B(IO))); },
+                             n2_48, ndb_12, WaBool{r.io});
+        default: return wa_not_built();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ launch
 // live accounting (prof.hip): products = 2 (forward: Q K^T, P V) or 5 (backward: the scores again, dP, dV, dQ, dK) over the
 // computed query chunks; bytes = the rows that exist in HBM read / written once (token layout: the unpartitioned tensors)
-static inline double ws_prof_flops(const WsDev& a, int products) {
+inline double ws_prof_flops(const WsDev& a, int products) {
     const double q = 16.0 * (a.qc_hi - a.qc_lo) < a.N ? 16.0 * (a.qc_hi - a.qc_lo) : a.N;
     return products * 2.0 * a.B_ * a.heads * q * a.N * a.d;
 }
-static inline double ws_prof_bytes(const WsDev& a, bool backward) {
+inline double ws_prof_bytes(const WsDev& a, bool backward) {
     const double rows = a.fill ? (double)(a.B_ / a.nW) * a.Ltok : (double)a.B_ * a.N;
     const double C = (double)a.heads * a.d, e = a.io_bf16 ? 2 : 4;      // io_bf16: qkv, out, gout, gqkv are all bf16 arrays
     // forward: qkv read, out + lse written; backward: qkv, out, gout, lse read, gqkv written
     return rows * C * e * (backward ? 3 + 1 + 1 + 3 : 3 + 1) + 4.0 * a.B_ * a.heads * a.N;
 }
-// Round 6: head dims up to 48 for windows of at most 64 tokens in the bf16 matrix mode (Swin C4 stage 1: 49 tokens, head dim 48, 1520 pairs at
-// batch 2: tiled kernels 36 + 106 us forward + backward per block, this family 12 + 31 us) -- from WINATTN_SMALL_MIN_PAIRS pairs (default 1024).
-bool dlwp_winattn_small_applies(int N, int d, long long pairs) {
-    if (N <= 128 && d <= 32 && pairs >= 2048) return true;
-    return dlwp_tune_or("WINATTN_D48", 1) != 0 && N <= 64 && d <= 48 && d % 4 == 0 && dlwp_get_gemm_precision() == 1 && !dlwp_tune_on("WINATTN_NOLDS") &&
-           pairs >= dlwp_tune_or("WINATTN_SMALL_MIN_PAIRS", 1024);
-}
-
-#define WS_DISPATCH(KERNEL, lds)                                                                                          \
-    do {                                                                                                                  \
-        const int nc = (N + 15) / 16, ndb = (d + 15) / 16;                                                                \
-        const bool vec = d % 4 == 0;                                                                                      \
-        const dim3 grid((unsigned)(heads * ntypes * a.groups)), block(256);                                               \
-        /* the accounting name carries the whole template argument list (the defaulted TOK = IOBF = false included) */     \
-        auto go = [&](auto knl, int NCv, int NDBv, bool V, bool B) -> int {                                               \
-            int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, #KERNEL);                                  \
-            if (rc2) return rc2;                                                                                          \
-            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), #KERNEL "<%d, %d, %s, %s, false, false>", \
-                                 NCv, NDBv, V ? "true" : "false", B ? "true" : "false");                                  \
-            hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);                                            \
-            return DLWP_OK;                                                                                               \
-        };                                                                                                                \
-        int rc3 = DLWP_OK;                                                                                                \
-        const bool bf = dlwp_get_gemm_precision() == 1;      /* bf16 matrix arithmetic asked for: bf16 MFMA operands */   \
-        if (bf && ndb == 3) {                       /* head dims 33 .. 48, windows of at most 64 tokens (small_applies) */  \
-            rc3 = go(KERNEL<4, 3, true, true>, 4, 3, true, true);                                                         \
-        } else if (bf) {                                                                                                  \
-            if (ndb == 1) {                                                                                               \
-                if (nc <= 4) rc3 = vec ? go(KERNEL<4, 1, true, true>, 4, 1, true, true) : go(KERNEL<4, 1, false, true>, 4, 1, false, true); \
-                else rc3 = vec ? go(KERNEL<8, 1, true, true>, 8, 1, true, true) : go(KERNEL<8, 1, false, true>, 8, 1, false, true); \
-            } else {                                                                                                      \
-                if (nc <= 4) rc3 = vec ? go(KERNEL<4, 2, true, true>, 4, 2, true, true) : go(KERNEL<4, 2, false, true>, 4, 2, false, true); \
-                else rc3 = vec ? go(KERNEL<8, 2, true, true>, 8, 2, true, true) : go(KERNEL<8, 2, false, true>, 8, 2, false, true); \
-            }                                                                                                             \
-        } else if (ndb == 1) {                                                                                            \
-            if (nc <= 4) rc3 = vec ? go(KERNEL<4, 1, true, false>, 4, 1, true, false) : go(KERNEL<4, 1, false, false>, 4, 1, false, false); \
-            else rc3 = vec ? go(KERNEL<8, 1, true, false>, 8, 1, true, false) : go(KERNEL<8, 1, false, false>, 8, 1, false, false); \
-        } else {                                                                                                          \
-            if (nc <= 4) rc3 = vec ? go(KERNEL<4, 2, true, false>, 4, 2, true, false) : go(KERNEL<4, 2, false, false>, 4, 2, false, false); \
-            else rc3 = vec ? go(KERNEL<8, 2, true, false>, 8, 2, true, false) : go(KERNEL<8, 2, false, false>, 8, 2, false, false); \
-        }                                                                                                                 \
-        if (rc3) return rc3;                                                                                              \
-    } while (0)
-
-int dlwp_winattn_small_fwd(const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
-                           const int* labels, float* out, float* lse, int B_, int nW, int N, int TB, int ntypes, int heads, int d,
-                           float scale, int q_lo, int q_hi, void* stream, int io_bf16) {
-    WsDev a{};
-    ws_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, q_lo, q_hi);
-    a.qkv = qkv; a.table = table; a.table_t = packed; a.ia = ia; a.ib = ib; a.labels = labels; a.out = out; a.lse = lse;
-    a.io_bf16 = io_bf16 != 0;
-    const size_t lds = sizeof(float) * (size_t)TB;
-    if (io_bf16) {
-        const int ndb = (d + 15) / 16;
-        const dim3 grid((unsigned)(heads * ntypes * a.groups)), block(256);
-        auto go = [&](auto knl) -> int {
-            int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, "winattn_small_fwd_kernel");
-            if (rc2) return rc2;
-            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_small_fwd_kernel<4, %d, true, true, false, true>", ndb);
-            hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);
-            return DLWP_OK;
-        };
-        const int rc3 = ndb == 1 ? go(winattn_small_fwd_kernel<4, 1, true, true, false, true>)
-                      : ndb == 2 ? go(winattn_small_fwd_kernel<4, 2, true, true, false, true>) : go(winattn_small_fwd_kernel<4, 3, true, true, false, true>);
-        if (rc3) return rc3;
-        DLWP_LAUNCH_CHECK();
-        return DLWP_OK;
+// the launch geometry of the route's family (workgroups per (type, head), threads, LDS bytes), then the launch
+int ws_launch(const WaRoute& r, WsDev& a, void* stream) {
+    const int nc = (a.N + 15) / 16, NR = 16 * nc, TB = a.TB, heads = a.heads, ntypes = a.ntypes;
+    const bool backward = r.family != WA_WAVE_FWD && r.family != WA_LDS_FWD_TOK;
+    size_t lds = 0;
+    int threads = 256;
+    a.io_bf16 = r.io;
+    switch (r.family) {
+        case WA_WAVE_FWD:          // four windows per workgroup (ws_setup); token layout: + the waves' map rows and the fill
+            lds = r.tok ? sizeof(float) * (size_t)((TB + 3) & ~3) + sizeof(int) * 4 * 256 + sizeof(float) * 96 : sizeof(float) * (size_t)TB;
+            break;
+        case WA_WAVE_BWD:
+            lds = sizeof(float) * (3 * (size_t)((TB + 1) & ~1) + 4 * 128);
+            break;
+        case WA_LDS_FWD_TOK: {
+            // one round of four-wave workgroups, two per CU (Pangu C4 step: 228 workgroups 10.97 ms, 456: 10.58, 912: 10.64, 1824: 10.72)
+            lds = (size_t)3 * NR * LDB * 2 + (size_t)4 * NR * 4 + (size_t)((TB + 3) & ~3) * 4 + 96 * 4;
+            const int per_cu = std::max(1, std::min(2, (int)((size_t)150 * 1024 / lds)));
+            a.groups = groups_of("WINATTN_WG_FWD", (long long)dlwp_cu_count() * per_cu / (heads * ntypes), a.M, heads, ntypes);
+            break;
+        }
+        case WA_LDS_BWD2:
+            lds = lds_bytes(NR, TB, true, r.ndb <= 2 ? LDB : LDB48);
+            a.groups = groups_of("WINATTN_WG_BWD", lds_groups(a.M, heads, ntypes, r.ndb <= 2 ? 4 : 3), a.M, heads, ntypes);
+            break;
+        case WA_LDS_BWD1P:
+            DLWP_REQUIRE((long long)(a.dst_map ? a.Ltok : a.N) * 3 * heads * a.d < (1LL << 31), DLWP_E_UNSUPPORTED,
+                         "window attention backward: a sample's qkv tensor must stay below 2^31 elements (32-bit row offsets)");
+            lds = lds2_bytes(NR, TB);
+            threads = 64 * r.n2;
+            a.dbg = dlwp_tune_or("WINATTN_DBG", 0);
+            // one round of workgroups: a workgroup's table staging, dense-image fold and flush cost ~36 k cycles (stamps), a window
+            // ~12 k, so the windows of a (type, head) are split over as many workgroups as fit on the chip at once and no more
+            // (Pangu C4 layer 1, 114 pairs x 37 windows: 228 workgroups 177 us, 456: 202, 798: 252)
+            a.groups = groups_of("WINATTN_WG_BWD", dlwp_cu_count() * (r.n2 == 8 ? 1 : 2) / (heads * ntypes), a.M, heads, ntypes);
+            break;
+        default: return wa_not_built();
     }
-    WS_DISPATCH(winattn_small_fwd_kernel, lds);
-    DLWP_LAUNCH_CHECK();
-    return DLWP_OK;
-}
-
-// the one-pass kernel (round 4) wherever its LDS image fits and the table slice fits the staging area it is folded in
-// Windows of at most 64 tokens (Swin's 49: four key chunks, the 4-wave instantiation) stay on the two-pass kernel unless asked for:
-// with ~4 windows per workgroup the per-workgroup fold of the dense image (2401 LDS float atomics onto 169 table slots) outweighs
-// the saved score evaluations -- Swin C4 step 6.74 ms one-pass vs 6.59 ms two-pass, same box, back to back.
-static bool one_pass_applies(int N, int d, int TB) {
-    const int nc = (N + 15) / 16;
-    if (d > 32) return false;
-    if (nc <= 4 && !dlwp_tune_on("WINATTN_BWD1P_SMALL")) return false;
-    return lds_family_applies(N, d) && lds2_bytes(16 * nc, TB) <= 160 * 1024 && (size_t)TB * 4 <= (size_t)4 * 16 * nc * LDB * 2;
-}
-// bf16 tensors in the WINDOW layout (round 6: qkv, out, gout, gqkv all bf16 arrays; dlwp_window_attn_fwd_bf16 / _bwd_bf16): windows of at
-// most 64 tokens in the bf16 matrix mode -- the wave-per-window forward with raw bf16 fragments and the two-pass LDS-staged backward
-bool dlwp_winattn_io_bf16_applies(int N, int d, int TB, long long pairs) {
-    return N <= 64 && d % 4 == 0 && dlwp_get_gemm_precision() == 1 && dlwp_winattn_small_applies(N, d, pairs) && lds_family_applies(N, d) &&
-           !(one_pass_applies(N, d, TB) && !dlwp_tune_on("WINATTN_BWD2PASS")) && !dlwp_tune_on("WINATTN_TILED");
-}
-
-static int one_pass_launch(WsDev& a, void* stream) {
-    const int nc = (a.N + 15) / 16, nw1 = nc > 4 ? 8 : 4, heads = a.heads, ntypes = a.ntypes, d = a.d;
-    DLWP_REQUIRE((long long)(a.dst_map ? a.Ltok : a.N) * 3 * heads * d < (1LL << 31), DLWP_E_UNSUPPORTED,
-                 "window attention backward: a sample's qkv tensor must stay below 2^31 elements (32-bit row offsets)");
-    const size_t lb1 = lds2_bytes(16 * nc, a.TB);
-    const int want = dlwp_tune_or("WINATTN_WG_BWD", 0);
-    a.dbg = dlwp_tune_or("WINATTN_DBG", 0);
-    // one round of workgroups: a workgroup's table staging, dense-image fold and flush cost ~36 k cycles (stamps), a window
-    // ~12 k, so the windows of a (type, head) are split over as many workgroups as fit on the chip at once and no more
-    // (Pangu C4 layer 1, 114 pairs x 37 windows: 228 workgroups 177 us, 456: 202, 798: 252)
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    const int slots = ncu * (nw1 == 8 ? 1 : 2);
-    const long long per = want ? ((long long)want + heads * ntypes - 1) / (heads * ntypes) : slots / (heads * ntypes);
-    a.groups = per < 1 ? 1 : (per > a.M ? a.M : (int)per);
     const dim3 grid((unsigned)(heads * ntypes * a.groups));
-    auto go1 = [&](auto knl, int nt) -> int {
-        int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lb1, "winattn_lds_bwd1p");
-        if (rc2) return rc2;
-        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 5), ws_prof_bytes(a, true), "winattn_lds_bwd1p_kernel<%d, %d, %s>",
-                             d <= 16 ? 1 : 2, nw1, a.io_bf16 ? "true" : "false");
-        hipLaunchKernelGGL(knl, grid, dim3(nt), lb1, (hipStream_t)stream, a);
-        return DLWP_OK;
-    };
-    int rc1;
-    if (a.io_bf16) {
-        if (nw1 == 8) rc1 = d <= 16 ? go1(winattn_lds_bwd1p_kernel<1, 8, true>, 512) : go1(winattn_lds_bwd1p_kernel<2, 8, true>, 512);
-        else rc1 = d <= 16 ? go1(winattn_lds_bwd1p_kernel<1, 4, true>, 256) : go1(winattn_lds_bwd1p_kernel<2, 4, true>, 256);
-    } else {
-        if (nw1 == 8) rc1 = d <= 16 ? go1(winattn_lds_bwd1p_kernel<1, 8>, 512) : go1(winattn_lds_bwd1p_kernel<2, 8>, 512);
-        else rc1 = d <= 16 ? go1(winattn_lds_bwd1p_kernel<1, 4>, 256) : go1(winattn_lds_bwd1p_kernel<2, 4>, 256);
-    }
-    if (rc1) return rc1;
-    DLWP_LAUNCH_CHECK();
-    return DLWP_OK;
-}
-
-int dlwp_winattn_small_bwd(const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
-                           const int* labels, const float* out, const float* lse, const float* gout, float* gqkv, float* gtable,
-                           int B_, int nW, int N, int TB, int ntypes, int heads, int d, float scale, int q_lo, int q_hi, void* stream, int io_bf16) {
-    WsDev a{};
-    ws_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, q_lo, q_hi);
-    a.qkv = qkv; a.table = table; a.table_t = packed; a.ia = ia; a.ib = ib; a.labels = labels; a.o = out; a.lse_in = lse;
-    a.gout = gout; a.gqkv = gqkv; a.gtable = gtable;
-    a.io_bf16 = io_bf16 != 0;
-    DLWP_REQUIRE(!io_bf16 || dlwp_winattn_io_bf16_applies(N, d, TB, (long long)B_ * heads), DLWP_E_UNSUPPORTED,
-                 "window attention backward: bf16 tensors in the window layout need windows of at most 64 tokens in the bf16 matrix mode (N %d, d %d)", N, d);
-    if (lds_family_applies(N, d)) {
-        const int nc = (N + 15) / 16;
-        if (!io_bf16 && !dlwp_tune_on("WINATTN_BWD2PASS") && one_pass_applies(N, d, TB)) return one_pass_launch(a, stream);
-        const size_t lb = lds_bytes(16 * nc, TB, true, d <= 32 ? LDB : LDB48);
-        a.groups = lds_groups(a.M, heads, ntypes, d <= 32 ? 4 : 3);
-        const dim3 grid((unsigned)(heads * ntypes * a.groups)), block(256);
-        auto go = [&](auto knl) -> int {
-            int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lb, "winattn_lds_bwd");
-            if (rc2) return rc2;
-            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 5), ws_prof_bytes(a, true), "winattn_lds_bwd_kernel<%d>", d <= 16 ? 1 : d <= 32 ? 2 : 3);
-            hipLaunchKernelGGL(knl, grid, block, lb, (hipStream_t)stream, a);
-            return DLWP_OK;
-        };
-        const int rc3 = d <= 16 ? go(winattn_lds_bwd_kernel<1>) : d <= 32 ? go(winattn_lds_bwd_kernel<2>) : go(winattn_lds_bwd_kernel<3>);
-        if (rc3) return rc3;
-        DLWP_LAUNCH_CHECK();
-        return DLWP_OK;
-    }
-    const size_t lds = sizeof(float) * (3 * (size_t)((TB + 1) & ~1) + 4 * 128);
-    const bool vec = d % 4 == 0;
-    const dim3 grid((unsigned)(heads * ntypes * a.groups)), block(256);
-    auto go = [&](auto knl) -> int {
-        int rc = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, "winattn_small_bwd");
-        if (rc) return rc;
-        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 5), ws_prof_bytes(a, true), "winattn_small_bwd_kernel<%d, %s, %s>", d <= 16 ? 1 : 2,
-                             vec ? "true" : "false", dlwp_get_gemm_precision() == 1 ? "true" : "false");
-        hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);
-        return DLWP_OK;
-    };
-    int rc;
-    if (dlwp_get_gemm_precision() == 1) {
-        if (d <= 16) rc = vec ? go(winattn_small_bwd_kernel<1, true, true>) : go(winattn_small_bwd_kernel<1, false, true>);
-        else rc = vec ? go(winattn_small_bwd_kernel<2, true, true>) : go(winattn_small_bwd_kernel<2, false, true>);
-    } else {
-        if (d <= 16) rc = vec ? go(winattn_small_bwd_kernel<1, true, false>) : go(winattn_small_bwd_kernel<1, false, false>);
-        else rc = vec ? go(winattn_small_bwd_kernel<2, true, false>) : go(winattn_small_bwd_kernel<2, false, false>);
-    }
+    const int rc = ws_inst(r, [&](const WaInst<WsDev>& k) {
+        return wa_launch(k, grid, dim3(threads), lds, ws_prof_flops(a, backward ? 5 : 2), ws_prof_bytes(a, backward), stream, a);
+    });
     if (rc) return rc;
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
 
+}  // namespace
+
+int dlwp_winattn_small_name(const WaRoute& r, char* buf, int n) {
+    return ws_inst(r, [&](const WaInst<WsDev>& k) { wa_format(k.name, buf, (size_t)n); return DLWP_OK; });
+}
+
+int dlwp_winattn_small_fwd(const WaRoute& r, const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
+                           const int* labels, float* out, float* lse, int B_, int nW, int N, int TB, int ntypes, int heads, int d,
+                           float scale, int q_lo, int q_hi, void* stream) {
+    WsDev a{};
+    ws_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, q_lo, q_hi);
+    a.qkv = qkv; a.table = table; a.table_t = packed; a.ia = ia; a.ib = ib; a.labels = labels; a.out = out; a.lse = lse;
+    return ws_launch(r, a, stream);
+}
+
+int dlwp_winattn_small_bwd(const WaRoute& r, const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,
+                           const int* labels, const float* out, const float* lse, const float* gout, float* gqkv, float* gtable,
+                           int B_, int nW, int N, int TB, int ntypes, int heads, int d, float scale, int q_lo, int q_hi, void* stream) {
+    WsDev a{};
+    ws_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, q_lo, q_hi);
+    a.qkv = qkv; a.table = table; a.table_t = packed; a.ia = ia; a.ib = ib; a.labels = labels; a.o = out; a.lse_in = lse;
+    a.gout = gout; a.gqkv = gqkv; a.gtable = gtable;
+    return ws_launch(r, a, stream);
+}
+
 // ---- token-layout entries (include/dlwpmi.h: dlwp_window_attn_fwd_tokens / dlwp_window_attn_bwd_tokens)
 extern "C" int dlwp_window_attn_bwd_tokens_supported(int N, int d, int TB) {
-    return one_pass_applies(N, d, TB) && !dlwp_tune_on("WINATTN_BWD2PASS") ? 1 : 0;
+    return dlwp_winattn_route_bwd(WaCall{WA_TOKENS, N, d, TB, 0, 0, N}).family != WA_NONE ? 1 : 0;
 }
 extern "C" int dlwp_window_attn_fwd_tokens_supported(int N, int d, long long pairs) {
-    return d <= 32 && pairs >= 2048 && dlwp_winattn_small_applies(N, d, pairs) && d % 4 == 0 && dlwp_get_gemm_precision() == 1 && !dlwp_tune_on("WINATTN_TILED") ? 1 : 0;
+    return dlwp_winattn_route_fwd(WaCall{WA_TOKENS | WA_FILL, N, d, 0, pairs, 0, N}).family != WA_NONE ? 1 : 0;
 }
 static int tokens_check(const char* who, int B_, int nW, int N, int Ltok, int TB, int ntypes, int heads, int d, int q_lo, int q_hi) {
     DLWP_REQUIRE(B_ > 0 && nW > 0 && B_ % nW == 0 && N > 0 && Ltok > 0 && heads > 0 && d > 0 && ntypes > 0 && TB > 0, DLWP_E_INVALID,
@@ -1761,70 +1763,15 @@ extern "C" int dlwp_window_attn_fwd_tokens(const float* qkv_tokens, const float*
                  "window_attn_fwd_tokens: NULL argument");
     int rc = tokens_check("window_attn_fwd_tokens", B_, nW, N, Ltok, TB, ntypes, heads, d, q_lo, q_hi);
     if (rc) return rc;
-    DLWP_REQUIRE(dlwp_window_attn_fwd_tokens_supported(N, d, (long long)B_ * heads), DLWP_E_UNSUPPORTED,
-                 "window_attn_fwd_tokens: needs the bf16 matrix mode, N <= 128, head_dim <= 32 and %% 4 == 0, at least 2048 (window, head) pairs "
-                 "(N %d, d %d, pairs %lld)", N, d, (long long)B_ * heads);
+    const WaRoute r = dlwp_winattn_route_fwd(WaCall{WA_TOKENS | WA_FILL | (io_bf16 ? WA_IO_BF16 : 0), N, d, TB, (long long)B_ * heads, q_lo, q_hi});
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
+    DLWP_REQUIRE((long long)Ltok * 3 * heads * d < (1LL << 31), DLWP_E_UNSUPPORTED,
+                 "window_attn_fwd_tokens: a sample's qkv tensor must stay below 2^31 elements (32-bit row offsets)");
     WsDev a{};
     ws_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, q_lo, q_hi);
     a.qkv = qkv_tokens; a.fill = fill; a.table = bias_table; a.table_t = packed_table; a.ia = ia; a.ib = ib; a.labels = labels;
-    a.src_map = src_map; a.dst_map = dst_map; a.out = out_tokens; a.lse = lse; a.Ltok = Ltok; a.io_bf16 = io_bf16 != 0;
-    const int nc = (N + 15) / 16;
-    DLWP_REQUIRE((long long)Ltok * 3 * heads * d < (1LL << 31), DLWP_E_UNSUPPORTED,
-                 "window_attn_fwd_tokens: a sample's qkv tensor must stay below 2^31 elements (32-bit row offsets)");
-    if (dlwp_tune_or("WINATTN_FWD_LDS", 1)) {
-        // the LDS-staged forward (winattn_lds_fwd_tok_kernel; default: 43 vs 56 us per launch in the Pangu C4 step): one round of
-        // four-wave workgroups, two per CU (Pangu C4 step: 228 workgroups 10.97 ms, 456: 10.58, 912: 10.64, 1824: 10.72)
-        const int NR = 16 * nc;
-        const size_t lb = (size_t)3 * NR * LDB * 2 + (size_t)4 * NR * 4 + (size_t)((TB + 3) & ~3) * 4 + 96 * 4;
-        static const int ncu = [] {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            return n > 0 ? n : 256;
-        }();
-        const int per_cu = std::max(1, std::min(2, (int)((size_t)150 * 1024 / lb)));
-        const int want = dlwp_tune_or("WINATTN_WG_FWD", 0);
-        const long long per = want ? ((long long)want + heads * ntypes - 1) / (heads * ntypes) : (long long)ncu * per_cu / (heads * ntypes);
-        a.groups = per < 1 ? 1 : (per > a.M ? a.M : (int)per);
-        const dim3 grid1((unsigned)(heads * ntypes * a.groups));
-        auto go1 = [&](auto knl) -> int {
-            int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lb, "winattn_lds_fwd_tok");
-            if (rc2) return rc2;
-            dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_lds_fwd_tok_kernel<%d, %d, %s>",
-                                 nc <= 4 ? 4 : 8, d <= 16 ? 1 : 2, io_bf16 ? "true" : "false");
-            hipLaunchKernelGGL(knl, grid1, dim3(256), lb, (hipStream_t)stream, a);
-            return DLWP_OK;
-        };
-        if (io_bf16) {
-            if (d <= 16) rc = nc <= 4 ? go1(winattn_lds_fwd_tok_kernel<4, 1, true>) : go1(winattn_lds_fwd_tok_kernel<8, 1, true>);
-            else rc = nc <= 4 ? go1(winattn_lds_fwd_tok_kernel<4, 2, true>) : go1(winattn_lds_fwd_tok_kernel<8, 2, true>);
-        } else {
-            if (d <= 16) rc = nc <= 4 ? go1(winattn_lds_fwd_tok_kernel<4, 1, false>) : go1(winattn_lds_fwd_tok_kernel<8, 1, false>);
-            else rc = nc <= 4 ? go1(winattn_lds_fwd_tok_kernel<4, 2, false>) : go1(winattn_lds_fwd_tok_kernel<8, 2, false>);
-        }
-        if (rc) return rc;
-        DLWP_LAUNCH_CHECK();
-        return DLWP_OK;
-    }
-    const size_t lds = sizeof(float) * (size_t)((TB + 3) & ~3) + sizeof(int) * 4 * 256 + sizeof(float) * 96;
-    const dim3 grid((unsigned)(heads * ntypes * a.groups)), block(256);
-    auto go = [&](auto knl) -> int {
-        int rc2 = dlwp_ensure_lds(reinterpret_cast<const void*>(knl), lds, "winattn_small_fwd_tokens");
-        if (rc2) return rc2;
-        dlwp_prof_scope prof((hipStream_t)stream, ws_prof_flops(a, 2), ws_prof_bytes(a, false), "winattn_small_fwd_kernel<%d, %d, true, true, true, %s>",
-                             nc <= 4 ? 4 : 8, d <= 16 ? 1 : 2, io_bf16 ? "true" : "false");
-        hipLaunchKernelGGL(knl, grid, block, lds, (hipStream_t)stream, a);
-        return DLWP_OK;
-    };
-    if (io_bf16) {
-        if (d <= 16) rc = nc <= 4 ? go(winattn_small_fwd_kernel<4, 1, true, true, true, true>) : go(winattn_small_fwd_kernel<8, 1, true, true, true, true>);
-        else rc = nc <= 4 ? go(winattn_small_fwd_kernel<4, 2, true, true, true, true>) : go(winattn_small_fwd_kernel<8, 2, true, true, true, true>);
-    } else {
-        if (d <= 16) rc = nc <= 4 ? go(winattn_small_fwd_kernel<4, 1, true, true, true>) : go(winattn_small_fwd_kernel<8, 1, true, true, true>);
-        else rc = nc <= 4 ? go(winattn_small_fwd_kernel<4, 2, true, true, true>) : go(winattn_small_fwd_kernel<8, 2, true, true, true>);
-    }
-    if (rc) return rc;
-    DLWP_LAUNCH_CHECK();
-    return DLWP_OK;
+    a.src_map = src_map; a.dst_map = dst_map; a.out = out_tokens; a.lse = lse; a.Ltok = Ltok;
+    return ws_launch(r, a, stream);
 }
 extern "C" int dlwp_window_attn_bwd_tokens(const float* qkv, const float* fill, const float* bias_table, const float* packed_table,
                                            const int* ia, const int* ib, const int* labels, const float* out, const float* lse,
@@ -1836,14 +1783,14 @@ extern "C" int dlwp_window_attn_bwd_tokens(const float* qkv, const float* fill, 
     DLWP_REQUIRE(!io_bf16 || fill, DLWP_E_INVALID, "window_attn_bwd_tokens: bf16 tensors need the token-layout operands (fill != NULL)");
     const int rc = tokens_check("window_attn_bwd_tokens", B_, nW, N, Ltok, TB, ntypes, heads, d, q_lo, q_hi);
     if (rc) return rc;
-    DLWP_REQUIRE(dlwp_window_attn_bwd_tokens_supported(N, d, TB), DLWP_E_UNSUPPORTED,
-                 "window_attn_bwd_tokens: needs the bf16 matrix mode, N <= 128, head_dim <= 32 and %% 4 == 0 (N %d, d %d, table %d)", N, d, TB);
+    const WaRoute r = dlwp_winattn_route_bwd(WaCall{WA_TOKENS | (fill ? WA_FILL : 0) | (io_bf16 ? WA_IO_BF16 : 0), N, d, TB, (long long)B_ * heads, q_lo, q_hi});
+    if (r.family == WA_NONE) return wa_refuse(r, N, d);
     WsDev a{};
     ws_setup(a, B_, nW, N, TB, ntypes, heads, d, scale, q_lo, q_hi);
     a.qkv = qkv; a.fill = fill; a.table = bias_table; a.table_t = packed_table; a.ia = ia; a.ib = ib; a.labels = labels; a.o = out;
     a.lse_in = lse; a.gout = gout_tokens; a.gqkv = gqkv_tokens; a.gtable = gbias_table;
-    a.src_map = src_map; a.dst_map = dst_map; a.gfill = gfill; a.Ltok = Ltok; a.io_bf16 = io_bf16 != 0;
-    return one_pass_launch(a, stream);
+    a.src_map = src_map; a.dst_map = dst_map; a.gfill = gfill; a.Ltok = Ltok;
+    return ws_launch(r, a, stream);
 }
 
 #ifdef DLWP_STAMPS

@@ -219,6 +219,7 @@ SIGNATURES = {
     "dlwp_window_attn_fwd_tokens_supported": (_I, [_I, _I, C.c_longlong]),
     "dlwp_window_attn_fwd_tokens": (_I, [_V] * 11 + [_I] * 8 + [_F, _I, _I, _I, _V]),
     "dlwp_window_attn_bwd_slab_floats": (_L, [_I] * 4),
+    "dlwp_window_attn_route_name": (_I, [_I] * 5 + [_L, _I, _I, C.c_char_p, _I]),
     "dlwp_window_softmax_fwd": (_I, [_V] * 5 + [_I] * 5 + [_F, _V]),
     "dlwp_window_softmax_bwd": (_I, [_V] * 5 + [_I] * 5 + [_F, _V]),
     "dlwp_fno_spatial_fwd_probe": (_I, [_V, _V, _V, _V, _V, _V, _V, _I, _V]),

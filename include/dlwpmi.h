@@ -411,6 +411,13 @@ int dlwp_window_attn_bwd_bf16(const void* qkv, const float* bias_table, const fl
                               const int* labels, const void* out, const float* lse, const void* gout, void* gqkv, float* gbias_table,
                               int B_, int nW, int N, int TB, int ntypes, int heads, int d, float scale, void* stream);
 long long dlwp_window_attn_bwd_slab_floats(int B_, int N, int heads, int TB);
+/* Debug: the accounting name(s), ';'-separated, of the attention kernel(s) a call of this shape would launch under the precision   */
+/* mode and tuning knobs in force (the slab fold and the table packing, which depend on the caller's buffers, are not listed), or  */
+/* DLWP_E_UNSUPPORTED with the refusal the entry would report.  direction: 0 forward, 1 backward.  layout: 0 = fp32 arrays in the  */
+/* window layout (_fwd / _bwd, _packed, _qrange); bit 0: the _tokens entries, bit 1: with fill != NULL, bit 2: bf16 tensors (alone: */
+/* _fwd_bf16 / _bwd_bf16).  pairs = B_ * heads.  Reads host state only: works without a device.                                     */
+int dlwp_window_attn_route_name(int direction, int layout, int N, int d, int TB, long long pairs, int q_lo, int q_hi, char* buf,
+                                int n);
 /* Backward of  reverse(crop) . attention . partition(pad with `fill`)  in ONE launch, for a block whose qkv projection ran */
 /* on the real tokens (EarthSpecificBlock.forward, src/dlwpbench/models/panguweather/panguweather.py:283-317: ZeroPad3d ->   */
 /* roll -> window_partition -> attention -> window_reverse -> roll -> crop3d; SwinTransformerBlock likewise).  The upstream   */

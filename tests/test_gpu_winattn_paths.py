@@ -905,16 +905,19 @@ def test_winattn_path(cuda, cid):
 
 
 # ------------------------------------------------------------------------------------------------ dispatch edges without a launch
+# (N, d, heads, B_) of the refused calls; the name's prefix says which entry, a *_fp32_mode suffix the precision mode
+UNSUPPORTED = {"fwd_bf16_n65": (65, 48, 1, 1100), "fwd_bf16_d36_fp32_mode": (49, 36, 1, 1100), "fwd_d65": (49, 65, 2, 40),
+               "fwd_tokens_pairs2047": (49, 16, 1, 2047), "bwd_tokens_d36": (98, 36, 2, 1100),
+               "fwd_tokens_fp32_mode": (49, 16, 2, 1100)}
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("what", ["fwd_bf16_n65", "fwd_bf16_d36_fp32_mode", "fwd_d65", "fwd_tokens_pairs2047", "bwd_tokens_d36",
-                                  "fwd_tokens_fp32_mode"])
+@pytest.mark.parametrize("what", list(UNSUPPORTED))
 def test_unsupported_launches_nothing(cuda, what):
     """shapes outside an entry's family: DLWP_E_UNSUPPORTED and no accounting row (nothing launched)"""
     from dlwp_benchmark_amd import lib as L
     lib = L.load()
-    N, d, H, B_ = {"fwd_bf16_n65": (65, 48, 1, 1100), "fwd_bf16_d36_fp32_mode": (49, 36, 1, 1100), "fwd_d65": (49, 65, 2, 40),
-                   "fwd_tokens_pairs2047": (49, 16, 1, 2047), "bwd_tokens_d36": (98, 36, 2, 1100),
-                   "fwd_tokens_fp32_mode": (49, 16, 2, 1100)}[what]
+    N, d, H, B_ = UNSUPPORTED[what]
     mode = "fp32" if what.endswith("fp32_mode") else "bf16"
     TB = 169
     buf = torch.zeros(B_ * N * 3 * H * d + 64, device=cuda)
