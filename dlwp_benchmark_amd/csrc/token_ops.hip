@@ -17,13 +17,13 @@
 // combined with float atomics into a zeroed C.
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
-#include "common.hip.h"
-#include "dlwpmi_internal.h"
+#include "gemm_route.h"
+#include "kernel_inst.h"
 
 namespace {
 
-constexpr int BK = 32;
 constexpr int LDK = BK + 4;    // [row][k] layout: 16-byte aligned rows
 // tile edge 64 * T (T = 1: 64 x 64 per workgroup, T = 2: 128 x 128 for the large products)
 template <int T> struct Tile {
@@ -58,7 +58,6 @@ struct GemmDev {
     int scale_rows = 1;
     int wide_epi = 0;          // gemm_p8_kernel: the register epilogue in 128-byte rows (p8_rows8; needs N % 8 == 0 and 16-byte aligned rows)
 };
-constexpr int DT_A = 1, DT_B = 2, DT_C = 4, DT_R = 8;
 
 // live accounting (prof.hip): algorithmic work of one product launch -- every operand read once, every output written once
 static inline double gemm_prof_flops(const GemmDev& a) { return 2.0 * a.M * a.N * (double)a.K * a.nbatch; }
@@ -85,14 +84,6 @@ static inline GemmProfTag gemm_prof_tag(const GemmDev& a) {
 // reference's bf16-autocast runs (BASELINE configs C3-C5); tensors in HBM stay fp32.  LDS tiles are [row][k] bf16.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-constexpr int BKB = 32;        // K-step of the bf16-operand mode.  A 64-deep step (fewer barriers, twice the bytes in flight
-                               // per workgroup) was measured: 136 instead of 104 registers drop the occupancy from 4 to 3
-                               // waves per SIMD and the net effect is -13 % ... +10 % depending on the shape (8192x512x256:
-                               // 14.1 -> 16.2 us, 8192x256x512: 15.1 -> 13.6 us), so the 32-deep step stays
-// K-step of a bf16-operand kernel: 64 only for the 128 x 128 weight-gradient product of two bf16 arrays (both operands
-// row-contiguous, K = tokens, split-K): 16200-deep 3072 x 768: 300 -> 410 TFLOP/s.  Everywhere else the doubled LDS image
-// halves the workgroups per CU and loses (16200 x 3072 x 768 forward: 479 -> 392; profiles/r02_gemm_bench.txt).
-constexpr int gemm_bf_kstep(int s16m, int T, bool akc, bool bkc) { return s16m == 3 && T == 2 && !akc && !bkc ? 64 : BKB; }
 
 // epilogue activations: 0 none, 1 GELU (erf), 2 ReLU, 3 soft-shrink(lambda); 4 is the backward form
 // v * GELU'(aux) with aux read through the `residual` view (the saved pre-activation): the product g W of a Linear layer
@@ -856,21 +847,6 @@ __global__ __launch_bounds__(256) void gemm_group_any_kernel(GemmGroupAny gg) {
     }
 }
 
-template <bool AKC, bool BKC, int VEC, int T, bool BF, int S16M = 0>
-int gemm_launch_t(const GemmDev& a, dim3 grid, hipStream_t s) {
-    constexpr int RW = Tile<T>::ROWS;
-    constexpr int KS = gemm_bf_kstep(S16M, T, AKC, BKC);
-    const size_t lds = BF ? sizeof(float) * 4 * ((RW * (KS + 8) > KS * (RW + 8) ? RW * (KS + 8) : KS * (RW + 8)) / 2)
-                          : sizeof(float) * 4 * Tile<T>::FLOATS;
-    int rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_kernel<AKC, BKC, VEC, T, BF, S16M>), lds, "gemm");
-    if (rc) return rc;
-    dlwp_prof_scope prof(s, gemm_prof_flops(a), gemm_prof_bytes(a), "gemm_kernel<%s, %s, %d, %d, %s, %d>%s", AKC ? "true" : "false",
-                         BKC ? "true" : "false", VEC, T, BF ? "true" : "false", S16M, gemm_prof_tag(a).s);
-    hipLaunchKernelGGL((gemm_kernel<AKC, BKC, VEC, T, BF, S16M>), grid, dim3(256), lds, s, a);
-    return DLWP_OK;
-}
-
-int g_gemm_bf16 = 0;    // dlwp_set_gemm_precision
 
 // ---- (round 3) both operands bf16 arrays, both k-contiguous ("NT": y = x W^T): 128 x 128 x 64 tiles staged by LDS-DMA.
 // The register-staged kernel above spends a K-step of 32 on 4 global loads + 4 ds_write_b128 + a barrier per 16 MFMAs and
@@ -891,7 +867,6 @@ int g_gemm_bf16 = 0;    // dlwp_set_gemm_precision
 // BKC = false ("NN": gx = g W with W [N][K] read as the [k][n] operand): the B tile is [64 k][128 n], chunk c of k-row kr stored at
 // chunk position c ^ (2 (kr & 3)); its MFMA fragments come through the hardware transpose read (ds_read_b64_tr_b16, as in
 // TileIO::frag_bf16): per 16-lane group four k-rows x 32 bytes, 32 different banks.
-constexpr int GT = 128, GK = 64;
 
 // GN = 96 (round 6): a 128 x 96 output tile.  Every feature width of the C4 models is a multiple of 96 (96 .. 1536) and several of their
 // products have just under one 128 x 128 tile per CU or pad a quarter of the last column tile (8192 x 384: 192 tiles -> 256 of 128 x 96;
@@ -1192,14 +1167,13 @@ __global__ __launch_bounds__(256) void gemm_slab_reduce_kernel(const float* __re
         for (int k = 0; k < 4; ++k) cp[k] = v[k];
     }
 }
-// the launch of both sliced weight-gradient kernels (C accumulates: the caller zeroed it for its own split-K when it does not);
-// accounting: one add per slice and element, every slice plane read once, C read and written once
-static void gemm_slab_reduce_launch(const float* slab, float* C, int M, int N, int ldc, int slices, hipStream_t s) {
+// the reduction launch of both sliced weight-gradient kernels; accounting: one add per slice and element, every slice plane read once,
+// C read and written once
+static int gemm_slab_reduce_launch(const float* slab, float* C, int M, int N, int ldc, int slices, hipStream_t s) {
     const long long units = (long long)M * (N / 4);
     const double mn = (double)M * N;
-    dlwp_prof_scope prof(s, mn * slices, 4.0 * mn * (slices + 2), "gemm_slab_reduce_kernel");
-    hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)std::min<long long>((units + 255) / 256, 2048)), dim3(256), 0, s,
-                       slab, C, M, N, ldc, slices, 1);
+    return ki_launch(ki_inst(gemm_slab_reduce_kernel, ki_name("gemm_slab_reduce_kernel")), dim3((unsigned)std::min<long long>((units + 255) / 256, 2048)),
+                     dim3(256), 0, mn * slices, 4.0 * mn * (slices + 2), s, slab, C, M, N, ldc, slices, 1);
 }
 
 // Scratch for the slices of the sliced weight-gradient kernel.  One slab per DEVICE, grow-only and never freed: a hipGraph captured
@@ -1229,64 +1203,6 @@ static float* tn_slab_for(hipStream_t s, size_t bytes) {
     return p;
 }
 
-// weight-gradient products the TN kernel takes: both operands bf16 arrays [k][row], fp32 output, no epilogue, one batch, the
-// caller already prepared for split-K (zeroed or accumulating output)
-static bool gemm_glds_tn_applies(const GemmDev& a) {
-    const bool off = dlwp_tune_on("GEMM_NOGLDS") || dlwp_tune_on("GEMM_NOGLDS_TN");
-    if (off || !g_gemm_bf16 || (a.dt & (DT_A | DT_B | DT_C | DT_R)) != (DT_A | DT_B)) return false;
-    if (a.M % 8 || a.N % 8 || a.lda % 8 || a.ldb % 8 || (uintptr_t)a.A % 16 || (uintptr_t)a.B % 16) return false;
-    if (a.nbatch != 1 || a.atomic_out || a.bias || a.residual || a.preact || a.act || a.act_b || a.bias_row) return false;
-    return a.M >= GT && a.N >= GT && a.K >= 1024 && a.splits > 1;
-}
-static int gemm_glds_tn_launch(const GemmDev& a_in, hipStream_t s) {
-    GemmDev a = a_in;
-    a.ntn = ceil_div(a.N, GT);
-    a.ntm = ceil_div(a.M, GT);
-    // K-step depth and slices from the sweep in profiles/r03_gemm_glds_tn.txt: the grid should fill the resident slots once (a second,
-    // partial round costs as much as a full one): 64 deep = 64 KB of LDS, two workgroups per CU; 32 deep = 32 KB and 160 VGPRs, three
-    // per CU, which pays once there are enough output tiles (FourCastNet's 3072 x 768: 120 us against 133)
-    const int kd_env = dlwp_tune("GEMM_GLDS_TN_KD");
-    const bool shallow = kd_env != DLWP_TUNE_UNSET ? kd_env == 32 : a.ntn * a.ntm >= 96;
-    const int kd = shallow ? 32 : 64;
-    const int wg_env = dlwp_tune("GEMM_GLDS_TN_WGS");
-    const int slots = wg_env != DLWP_TUNE_UNSET ? wg_env : (shallow ? 768 : 448);
-    // at least eight K-steps per slice: shorter slices only add partial tiles to combine (8192 tokens x 512 x 256, graph timing,
-    // tools/bench_gemm_graph.py: 32 slices 22.6 us, 16 slices 17.4 us)
-    int splits = std::max(1, std::min(slots / (a.ntn * a.ntm), a.K / (8 * kd)));
-    a.kchunk = ceil_div(ceil_div(a.K, splits), kd) * kd;
-    a.xcd_splitk = 0;
-    if (splits >= 8 && a.ntn * a.ntm < 64 && (dlwp_tune_or("GEMM_XCD_SPLITK", 1) & 2) != 0) {
-        // few tiles, many slices: a slice count that is a multiple of 8 keeps the tiles of a slice on one XCD (round 5)
-        for (int s8 = round_up(splits, 8); s8 >= 8 && s8 > splits / 2; s8 -= 8) {
-            const int kc = ceil_div(ceil_div(a.K, s8), kd) * kd;
-            if (ceil_div(a.K, kc) % 8 == 0) { a.kchunk = kc; a.xcd_splitk = 1; break; }
-        }
-    }
-    a.splits = std::max(2, ceil_div(a.K, a.kchunk));             // > 1: the atomic epilogue (the caller zeroed C for its own split)
-    const size_t lds = (size_t)2 * 2 * GT * kd * 2;
-    const dim3 grid(a.ntn * a.ntm, 1, ceil_div(a.K, a.kchunk));
-    const bool no_slab = dlwp_tune_on("GEMM_TN_ATOMIC");
-    // few output tiles cut into many slices (SFNO's 512 x 256: 8 tiles x 32) read more slab in the reduction than the atomics cost
-    const int slab_min_env = dlwp_tune("GEMM_TN_SLAB_MIN");
-    const int slab_min = slab_min_env != DLWP_TUNE_UNSET ? slab_min_env : 24;
-    a.slab = (no_slab || a.ntn * a.ntm < slab_min || a.N % 4 || a.ldc % 4 || (uintptr_t)a.C % 16) ? nullptr
-                                                                         : tn_slab_for(s, sizeof(float) * grid.z * (size_t)a.M * a.N);
-    int rc;
-    {
-    dlwp_prof_scope prof(s, gemm_prof_flops(a), gemm_prof_bytes(a), "gemm_glds_tn_kernel<%d>%s", kd, gemm_prof_tag(a).s);
-    if (shallow) {
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_glds_tn_kernel<32>), lds, "gemm_glds_tn"))) return rc;
-        hipLaunchKernelGGL(gemm_glds_tn_kernel<32>, grid, dim3(256), lds, s, a);
-    } else {
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_glds_tn_kernel<64>), lds, "gemm_glds_tn"))) return rc;
-        hipLaunchKernelGGL(gemm_glds_tn_kernel<64>, grid, dim3(256), lds, s, a);
-    }
-    }
-    // the caller zeroed C for its own split-K when it does not accumulate: adding to it is the same either way
-    if (a.slab) gemm_slab_reduce_launch(a.slab, a.C, a.M, a.N, a.ldc, (int)grid.z, s);
-    return DLWP_OK;
-}
-
 // ---- (round 3) 256 x 256 x 64 tiles, eight waves in two groups half a phase apart (the CDNA guide's "8-phase" schedule, built
 // here from its description): y = x W^T, both operands bf16 arrays with k contiguous.
 // A wave (wr = w >> 2, wc = w & 3) owns rows wr * 128 .. + 128, columns wc * 64 .. + 64 of the tile = four quadrants
@@ -1307,7 +1223,6 @@ static int gemm_glds_tn_launch(const GemmDev& a_in, hipStream_t s) {
 //        barrier that precedes group 0's first read of tile t + 1 (global 8 t + 8).
 // A DMA instruction moves 64 consecutive 16-byte chunks = 8 rows of a half-tile image (lane-linear LDS side), chunk c of local row
 // lr stored at position c ^ ((lr >> 1) & 7); each group loads half of every half-tile (two DMAs per thread).
-constexpr int P8T = 256;
 // the barrier as inline assembly with a memory clobber: the compiler must not move LDS reads across it (the s_barrier builtin alone
 // does not order memory accesses for the optimiser; a read hoisted above the barrier that follows the other group's vmcnt wait
 // would see a half-tile before its DMA has landed)
@@ -1545,65 +1460,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmDev a) {
     }
 }
 
-// shapes the LDS-DMA kernel takes: both operands bf16 arrays with k contiguous and 16-byte aligned rows, K a multiple of 64, one
-// plain product (no split-K / batches / row sums / row bias), the aligned epilogue, enough tiles to be worth 128 x 128
-// column-tile width of gemm_glds_kernel: 96 when N is a multiple of 96 and rounds x width (whole rounds of one workgroup per CU, work per
-// tile ~ its width) comes out lower than with 128-wide tiles; ties go to 128 when N is a multiple of 128.  GEMM_GLDS_N96: 0 never, 1 by
-// this rule (default), 2 wherever N % 96 == 0.  GEMM_GLDS_N96_TIE_K: ties go to 96 up to this K (default 192).
-static int gemm_glds_tile_n(const GemmDev& a) {
-    const int mode = dlwp_tune_or("GEMM_GLDS_N96", 1);
-    if (mode == 0 || a.N % 96 != 0) return GT;
-    if (mode == 2) return 96;
-    const long long ncu = 256, mt = ceil_div(a.M, GT);
-    const long long c128 = ceil_div(mt * ceil_div(a.N, GT), ncu) * 128, c96 = ceil_div(mt * (a.N / 96), ncu) * 96;
-    // ties: 96 where 128 would pad, and for short products (K <= 192: launch / epilogue bound, the finer tiles fill the last round better --
-    // Swin C4 443 -> 449 samples/s with every tie at 96, AFNO 721 53.6 -> 52.3 with its K = 768 products there too)
-    return c96 < c128 || (c96 == c128 && (a.N % GT != 0 || a.K <= dlwp_tune_or("GEMM_GLDS_N96_TIE_K", 192))) ? 96 : GT;
-}
-static bool gemm_glds_applies(const GemmDev& a, bool akc, bool bkc) {
-    const bool off = dlwp_tune_on("GEMM_NOGLDS");
-    if (off || !g_gemm_bf16 || !akc || (a.dt & (DT_A | DT_B)) != (DT_A | DT_B)) return false;
-    if (a.K % 32 || a.lda % 8 || a.ldb % 8 || (uintptr_t)a.A % 16 || (uintptr_t)a.B % 16) return false;
-    if (!bkc && a.N % 8) return false;
-    if (a.splits != 1 || a.nbatch != 1 || a.atomic_out || a.rowsum || a.bias_row || a.act_b || !a.vec_epi) return false;
-    const bool force = dlwp_tune_on("GEMM_GLDS_FORCE");          // measurement: skip the shape heuristic below
-    if (force) return a.M >= GT && a.N >= 64;
-    // at least one workgroup per CU: below that the 64 x 64 kernel's shorter prologue wins (measured, profiles/r03_gemm_bench.txt: Pangu
-    // 8192 x 192 x 768 104 vs 120 TFLOP/s, 2048 x 1536 x 384 77 vs 93; round 6, in the step: 128 tiles instead of 256 costs Pangu C4 1.3 %).
-    // K: rounds 3 - 5 asked for four 64-deep K-steps; with >= 256 tiles the kernel wins from K = 96 on (three 32-deep steps) -- back to back
-    // 32768 x 768 x 192 36.2 -> 26.1 us, 65536 x 384 x 96 28.8 -> 21.7 us (profiles/r06_gemm_vs_vendor.txt), in the step Swin C4 390.5 -> 396.5,
-    // Pangu C4 107.0 -> 107.9 samples/s (profiles/r06_gemm_glds_threshold_sweep.txt)
-    const int mink = dlwp_tune_or("GEMM_GLDS_MINK", 96), mintiles = dlwp_tune_or("GEMM_GLDS_MINTILES", 256);
-    return a.K >= mink && (long long)ceil_div(a.M, GT) * ceil_div(a.N, gemm_glds_tile_n(a)) >= mintiles;
-}
-static int gemm_glds_launch(const GemmDev& a_in, bool bkc, hipStream_t s) {
-    GemmDev a = a_in;
-    const int gn = gemm_glds_tile_n(a);
-    a.ntn = ceil_div(a.N, gn);
-    a.ntm = ceil_div(a.M, GT);
-    const int kd_env = dlwp_tune("GEMM_GLDS_KD");
-    // depth of a K-step (profiles/r03_gemm_glds_kd.txt): 32 deep leaves room for three or four workgroups per CU, which wins for
-    // y = x W^T up to K ~ 1000 (16200 x 3072 x 768: 122 -> 110 us) and for gx = g W with at least four column tiles (16200 x 768 x 3072:
-    // 122 -> 96 us, 8192^3: 841 -> 945 TFLOP/s); the deep, long products stay at 64 (8192^3 y: 1001 TFLOP/s against 828)
-    const bool shallow = a.K % GK != 0 || (kd_env != DLWP_TUNE_UNSET ? kd_env == 32 : (bkc ? a.K <= 1024 : a.N >= 512));
-    // 64 KB at KD = 64 (the epilogue's 64 x 132 fp32 half tile fits inside); 33 KB (that half tile) at KD = 32
-    const size_t lds = shallow ? sizeof(float) * 64 * (GT + 4) : (size_t)2 * 2 * GT * GK * 2;
-    int rc;
-#define GLDS_GO2(BKC_, KD_, GN_)                                                                                        \
-    do {                                                                                                                \
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_glds_kernel<BKC_, KD_, GN_>), lds, "gemm_glds"))) return rc; \
-        dlwp_prof_scope prof(s, gemm_prof_flops(a), gemm_prof_bytes(a), "gemm_glds_kernel<%s, %d, %d>%s", BKC_ ? "true" : "false", KD_, GN_,    \
-                             gemm_prof_tag(a).s);                                                                        \
-        hipLaunchKernelGGL((gemm_glds_kernel<BKC_, KD_, GN_>), dim3(a.ntn * a.ntm), dim3(256), lds, s, a);               \
-    } while (0)
-#define GLDS_GO(BKC_, KD_) do { if (gn == 96) GLDS_GO2(BKC_, KD_, 96); else GLDS_GO2(BKC_, KD_, 128); } while (0)
-    if (bkc) { if (shallow) GLDS_GO(true, 32); else GLDS_GO(true, 64); }
-    else     { if (shallow) GLDS_GO(false, 32); else GLDS_GO(false, 64); }
-#undef GLDS_GO2
-#undef GLDS_GO
-    return DLWP_OK;
-}
-
 
 // ---- the same schedule for weight gradients ("TN": gW = g^T x, both operands [k = tokens][row] bf16 arrays): the half-tile images
 // are [64 k][128 local columns] (chunk cm of k-row kr at position cm ^ 2 (kr & 3), as the 128^2 kernels' [k][n] tile), every fragment
@@ -1791,269 +1647,131 @@ __global__ __launch_bounds__(512) void gemm_p8_tn_kernel(GemmDev a) {
     }
 }
 
+// ---- the host side.  Every entry fills a GemmDev (the kernels' arguments) and a GemmCall (what the rules read); dlwp_gemm_route
+// (gemm_route.h) decides the family, the instantiation, the split-K plans, grid and LDS; gemm_run launches what it says.
 
-static int gemm_p8_launch(const GemmDev& a_in, bool bkc, hipStream_t s) {
-    GemmDev a = a_in;
-    a.ntn = ceil_div(a.N, P8T);
-    a.ntm = ceil_div(a.M, P8T);
-    const size_t lds = (size_t)2 * 4 * 128 * 64 * 2;          // 128 KB: two stages of four half-tile images (the epilogue's 64 x 260 fp32 tile fits inside)
-    int rc;
-    const bool direct = !dlwp_tune_on("GEMM_P8_STAGED");
-    {   // 128-byte-row register epilogue (round 6): every tensor the epilogue touches in whole, aligned 8-column pieces
-        auto al = [&](const void* p, bool bf) { return !p || (uintptr_t)p % (bf ? 16 : 32) == 0; };
-        a.wide_epi = dlwp_tune_or("GEMM_P8_WIDE", 1) != 0 && a.N % 8 == 0 && a.ldc % 8 == 0 && al(a.C, a.dt & DT_C) && al(a.preact, a.dt & DT_C) &&
-                     al(a.residual, a.dt & DT_R) && (!a.bias || a.bias_row || (uintptr_t)a.bias % 16 == 0);
+// the route's kernel instantiation with its accounting name, handed to f.  Combinations no route reaches are excluded with if constexpr,
+// so no further instantiation is built: VEC 1 / 2 on the 64 x 64 tile only, S16M with VEC 3 in the bf16 mode only, the wide register
+// epilogue on the direct kernel only
+template <class F> int gemm_inst(const GemmRoute& r, F&& f) {
+    switch (r.family) {
+        case GEMM_P8:
+            return ki_consts([&](auto d, auto b, auto w) {
+                if constexpr (!KI_B(d) && KI_B(w)) return ki_not_built();
+                else return f(KI_INST(gemm_p8_kernel, KI_B(d), KI_B(b), KI_B(w)));
+            }, KiBool{r.direct}, KiBool{r.bkc}, KiBool{r.wide});
+        case GEMM_GLDS:
+            return ki_consts([&](auto b, auto kd, auto gn) { return f(KI_INST(gemm_glds_kernel, KI_B(b), KI_C(kd), KI_C(gn))); },
+                             KiBool{r.bkc}, KiOneOf<32, 64>{r.kd}, KiOneOf<96, 128>{r.gn});
+        case GEMM_GLDS_TN: return ki_consts([&](auto kd) { return f(KI_INST(gemm_glds_tn_kernel, KI_C(kd))); }, KiOneOf<32, 64>{r.kd});
+        case GEMM_P8_TN: return f(ki_inst(gemm_p8_tn_kernel, ki_name("gemm_p8_tn_kernel")));
+        case GEMM_GENERIC:
+            return ki_consts([&](auto akc, auto bkc, auto vec, auto t, auto bf, auto m16) {
+                constexpr int VEC = KI_C(vec), T = KI_C(t), S16M = KI_C(m16);
+                if constexpr (((VEC == 1 || VEC == 2) && T == 2) || (S16M != 0 && !(KI_B(bf) && VEC == 3))) return ki_not_built();
+                else return f(KI_INST(gemm_kernel, KI_B(akc), KI_B(bkc), VEC, T, KI_B(bf), S16M));
+            }, KiBool{r.akc}, KiBool{r.bkc}, KiOneOf<0, 1, 2, 3>{r.vec}, KiOneOf<1, 2>{r.T}, KiBool{r.bf}, KiOneOf<0, 1, 2, 3>{r.s16m});
+        default: return ki_not_built();      // (a parked product leaves with its group)
     }
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-#define P8_GO(D_, B_, W_)                                                                                               \
-    do {                                                                                                                \
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_p8_kernel<D_, B_, W_>), lds, "gemm_p8"))) return rc; \
-        dlwp_prof_scope prof(s, gemm_prof_flops(a), gemm_prof_bytes(a), "gemm_p8_kernel<%s, %s, %s>%s", D_ ? "true" : "false", B_ ? "true" : "false", \
-                             W_ ? "true" : "false", gemm_prof_tag(a).s);                                                 \
-        hipLaunchKernelGGL((gemm_p8_kernel<D_, B_, W_>), dim3(std::min(a.ntn * a.ntm, ncu)), dim3(512), lds, s, a);     \
-    } while (0)
-    if (direct && a.wide_epi) { if (bkc) P8_GO(true, true, true); else P8_GO(true, false, true); }
-    else if (bkc) { if (direct) P8_GO(true, true, false); else P8_GO(false, true, false); }
-    else          { if (direct) P8_GO(true, false, false); else P8_GO(false, false, false); }
-#undef P8_GO
-    return DLWP_OK;
 }
-
-int g_gemm_tile256 = 0;    // dlwp_set_gemm_tile256: 0 by shape (below), 1 wherever the kernel applies, -1 never
-
-// weight gradients on the 256 x 256 two-group kernel.  Measured (profiles/r03_gemm_p8.txt): 4096^3 707 against 656 TFLOP/s for the
-// 128 x 128 sliced kernel, 8192^3 764 / 762, FourCastNet 3072 x 768 x 16200 639 / 689, 768 x 3072 x 16200 652 / 640 -- with every fragment
-// through two transposing reads the K loop does not reach the y = x W^T kernel's rate and the gain is within the noise: NOT taken by
-// shape, only when forced (dlwp_set_gemm_tile256(1) / DLWP_GEMM_P8: tests, measurements).  Needs the slab.
-static int gemm_p8_tn_launch(const GemmDev& a_in, hipStream_t s, bool* taken) {
-    *taken = false;
-    const bool off = dlwp_tune_on("GEMM_NOP8_TN");
-    if (off || g_gemm_tile256 < 0 || a_in.M < P8T || a_in.N < P8T || a_in.N % 4 || a_in.ldc % 4 || (uintptr_t)a_in.C % 16) return DLWP_OK;
-    GemmDev a = a_in;
-    a.ntn = ceil_div(a.N, P8T);
-    a.ntm = ceil_div(a.M, P8T);
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    const int tiles = a.ntn * a.ntm;
-    int splits = std::max(1, std::min(ncu / tiles, a.K / (16 * 64)));
-    a.kchunk = ceil_div(ceil_div(a.K, splits), 64) * 64;
-    splits = ceil_div(a.K, a.kchunk);
-    const bool force = dlwp_tune_on("GEMM_P8");
-    if (!force && g_gemm_tile256 <= 0) return DLWP_OK;
-    a.splits = splits;
-    a.slab = tn_slab_for(s, sizeof(float) * splits * (size_t)a.M * a.N);
-    if (!a.slab) return DLWP_OK;
-    const size_t lds = (size_t)2 * 4 * 128 * 64 * 2;
-    int rc;
-    if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_p8_tn_kernel), lds, "gemm_p8_tn"))) return rc;
-    {
-    dlwp_prof_scope prof(s, gemm_prof_flops(a), gemm_prof_bytes(a), "gemm_p8_tn_kernel%s", gemm_prof_tag(a).s);
-    hipLaunchKernelGGL(gemm_p8_tn_kernel, dim3(std::min(tiles * splits, ncu)), dim3(512), lds, s, a);
+// the two group kernels: the queue's (any layout) and dlwp_weight_grad_group's (both operands row-contiguous)
+constexpr auto gemm_group_any_inst = [](auto bf) { return KI_INST(gemm_group_any_kernel, KI_B(bf)); };
+constexpr auto gemm_wgrad_group_inst = [](auto bf) { return KI_INST(gemm_group_kernel, false, false, 3, 1, KI_B(bf), 0); };
+// n products as one grid (blockIdx.y picks the product); every member runs the 64 x 64 body with the 32-deep K-step
+template <class Group, class Inst> int gemm_group_launch(const Group& gg, int n, hipStream_t s, Inst inst) {
+    unsigned gx = 0, gz = 0;
+    double flops = 0, bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        gx = std::max(gx, (unsigned)(gg.g[i].ntn * gg.g[i].ntm));
+        gz = std::max(gz, (unsigned)(gg.g[i].nbatch * gg.g[i].splits));
+        flops += gemm_prof_flops(gg.g[i]);
+        bytes += gemm_prof_bytes(gg.g[i]);
     }
-    gemm_slab_reduce_launch(a.slab, a.C, a.M, a.N, a.ldc, splits, s);
-    *taken = true;
-    return DLWP_OK;
-}
-
-
-// the 256 x 256 kernel runs one workgroup per CU: nothing covers its prologue (two K-tiles of DMAs) and epilogue, so it needs a long K
-// to pay -- 8192^3: 1351 against 1017 TFLOP/s, 4096^3 1186 / 983, 16200 x 768 x 3072: 898 / 788, but 16200 x 3072 x 768: 686 / 693 and every
-// K <= 512 shape loses (profiles/r03_gemm_p8.txt): taken from K = 2048 with at least 128 tiles, or when forced
-static bool gemm_p8_applies(const GemmDev& a, bool akc, bool bkc) {
-    const bool env_on = dlwp_tune_on("GEMM_P8");
-    if (g_gemm_tile256 < 0 || !akc || a.K % 64 || a.M < P8T || a.N < P8T) return false;
-    const long long tiles = (long long)ceil_div(a.M, P8T) * ceil_div(a.N, P8T);
-    const int mink_env = dlwp_tune("GEMM_P8_MINK");
-    const int mink = mink_env != DLWP_TUNE_UNSET ? mink_env : 2048;
-    // one workgroup per CU: the last round should be at least 70 % full.  Round 5 asked for 80 % (16200 x 768 x 3072: 192 tiles = 75 % of one
-    // round, where the 128 x 128 LDS-DMA kernel was then 0.4 % of the C5 step faster); with the 128-byte-row epilogue (round 6) this kernel
-    // wins there: C5 720 x 1440 step 16.25 -> 16.08 ms, 721 x 1440 / Pangu / Swin unchanged (profiles/r06_gemm_p8_dispatch_sweep.txt)
-    const long long rounds = (tiles + 255) / 256;
-    const int fill_pct = dlwp_tune_or("GEMM_P8_FILL", 70);
-    const bool fills = tiles >= 128 && 100 * tiles >= (long long)fill_pct * rounds * 256;
-    return env_on || g_gemm_tile256 > 0 || (a.K >= mink && fills);
+    return ki_consts([&](auto bf) { return ki_launch(inst(bf), dim3(gx, n, gz), dim3(256), gemm_generic_lds(KI_B(bf), 1, BKB), flops, bytes, s, gg); },
+                     KiBool{g_gemm_bf16 != 0});
 }
 
 // ---- a queue of independent small products (dlwp_gemm_group_begin ... dlwp_gemm_group_end): while it is open, every product
-// that fits the generic 64 x 64 configuration and is small (latency-bound by itself) is parked instead of launched; _end launches
-// up to three parked products as ONE grid (gemm_group_any_kernel).  Everything else launches at once, as usual -- the products
-// inside a begin / end pair must not depend on each other.
+// that fits the generic 64 x 64 configuration and is small (latency-bound by itself) is parked instead of launched (the route says
+// which); _end launches up to three parked products as ONE grid (gemm_group_any_kernel).  Everything else launches at once, as usual --
+// the products inside a begin / end pair must not depend on each other.
 struct GemmQueue { bool open = false; int n = 0; GemmGroupAny gg; };
-static thread_local GemmQueue g_queue;      // per host thread: a backward pass on another autograd thread has its own (empty) queue
-static int gemm_queue_flush(hipStream_t s) {
+thread_local GemmQueue g_queue;      // per host thread: a backward pass on another autograd thread has its own (empty) queue
+int gemm_queue_flush(hipStream_t s) {
     GemmQueue& q = g_queue;
     if (q.n == 0) return DLWP_OK;
-    unsigned gx = 0, gz = 0;
-    for (int i = 0; i < q.n; ++i) {
-        gx = std::max(gx, (unsigned)(q.gg.g[i].ntn * q.gg.g[i].ntm));
-        gz = std::max(gz, (unsigned)(q.gg.g[i].nbatch * q.gg.g[i].splits));
-    }
-    const dim3 grid(gx, q.n, gz);
-    double flops = 0, bytes = 0;
-    for (int i = 0; i < q.n; ++i) {
-        flops += gemm_prof_flops(q.gg.g[i]);
-        bytes += gemm_prof_bytes(q.gg.g[i]);
-    }
-    int rc;
-    if (g_gemm_bf16) {
-        constexpr int KS = gemm_bf_kstep(0, 1, false, false);
-        const size_t lds = sizeof(float) * 4 * ((64 * (KS + 8) > KS * (64 + 8) ? 64 * (KS + 8) : KS * (64 + 8)) / 2);
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_group_any_kernel<true>), lds, "gemm_group_any"))) return rc;
-        dlwp_prof_scope prof(s, flops, bytes, "gemm_group_any_kernel<true>");
-        hipLaunchKernelGGL(gemm_group_any_kernel<true>, grid, dim3(256), lds, s, q.gg);
-    } else {
-        const size_t lds = sizeof(float) * 4 * Tile<1>::FLOATS;
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_group_any_kernel<false>), lds, "gemm_group_any"))) return rc;
-        dlwp_prof_scope prof(s, flops, bytes, "gemm_group_any_kernel<false>");
-        hipLaunchKernelGGL(gemm_group_any_kernel<false>, grid, dim3(256), lds, s, q.gg);
-    }
+    if (int rc = gemm_group_launch(q.gg, q.n, s, gemm_group_any_inst)) return rc;
     q.n = 0;
     return DLWP_OK;
 }
-// park a product if the queue is open and it qualifies; a full queue is flushed first
-static bool gemm_queue_take(const GemmDev& a_in, bool akc, bool bkc, int vec, int T, hipStream_t s, int* rc) {
-    *rc = DLWP_OK;
+// park a product; a full queue is flushed first
+int gemm_queue_park(const GemmDev& a, const GemmRoute& r, hipStream_t s) {
     GemmQueue& q = g_queue;
-    if (!q.open || vec != 3 || T != 1 || a_in.act_b) return false;
-    // small, latency-bound products only: at most 2.2 GFLOP (the SFNO block-tail products are 2.1; Pangu's 8192 x 384 x 1152 input
-    // gradient at 7.2 GFLOP belongs on its own kernel: parked, the C4 step went from 14.3 to 15.1 ms)
-    const double flop = 2.0 * a_in.M * a_in.N * (double)a_in.K * a_in.nbatch;
-    if (flop > 2.2e9 || a_in.K > 16384) return false;
-    if (q.n == 3 && (*rc = gemm_queue_flush(s))) return true;
-    GemmDev a = a_in;
-    a.ntn = ceil_div(a.N, 64);
-    a.ntm = ceil_div(a.M, 64);
+    if (q.n == 3)
+        if (int rc = gemm_queue_flush(s)) return rc;
     q.gg.g[q.n] = a;
-    q.gg.layout[q.n] = (akc ? 2 : 0) | (bkc ? 1 : 0);
-    {   // both operands bf16 arrays on the 16-byte path (the conditions gemm_launch uses for a single product)
-        auto ok16 = [&](const float* p, int ld, bool kc, int rows, long long s1, long long s2) {
-            return (uintptr_t)p % 16 == 0 && ld % 8 == 0 && (kc ? a.K % 8 == 0 && a.kchunk % 8 == 0 : rows % 8 == 0) &&
-                   (a.nbatch == 1 || (s1 % 8 == 0 && s2 % 8 == 0));
-        };
-        q.gg.s16m[q.n] = g_gemm_bf16 ? ((((a.dt & DT_A) && ok16(a.A, a.lda, akc, a.M, a.sA1, a.sA2)) ? 1 : 0) |
-                                        (((a.dt & DT_B) && ok16(a.B, a.ldb, bkc, a.N, a.sB1, a.sB2)) ? 2 : 0))
-                                     : 0;
-    }
+    q.gg.layout[q.n] = (r.akc ? 2 : 0) | (r.bkc ? 1 : 0);
+    q.gg.s16m[q.n] = r.s16m;
     ++q.n;
-    return true;
+    return DLWP_OK;
 }
 
-template <bool AKC, bool BKC>
-int gemm_launch(const GemmDev& a_in, int vec, int T, hipStream_t s) {
-    {
-        int qrc;
-        if (gemm_queue_take(a_in, AKC, BKC, vec, T, s, &qrc)) return qrc;
-    }
-    if (gemm_glds_applies(a_in, AKC, BKC) && gemm_p8_applies(a_in, AKC, BKC)) return gemm_p8_launch(a_in, BKC, s);
-    if (gemm_glds_applies(a_in, AKC, BKC)) return gemm_glds_launch(a_in, BKC, s);
-    if (!AKC && !BKC && gemm_glds_tn_applies(a_in)) {
-        bool taken = false;
-        if (int rc = gemm_p8_tn_launch(a_in, s, &taken)) return rc;
-        if (taken) return DLWP_OK;
-        return gemm_glds_tn_launch(a_in, s);
-    }
-    const int edge = 64 * T;
-    GemmDev a = a_in;
-    a.ntn = ceil_div(a.N, edge);
-    a.ntm = ceil_div(a.M, edge);
-    const dim3 grid(a.ntn * a.ntm, 1, a.nbatch * a.splits);
-    if (T == 2 && vec != 3) vec = 0;      // the 128-wide tile exists for fully aligned operands only
-    // bf16 arrays in memory (dlwp_gemm_mixed): whole groups of 8 along the contiguous dimension and 16-byte aligned -> the
-    // 16-byte path; otherwise TileIO::load widens them element-wise (correct, slower)
-    if (g_gemm_bf16 && vec == 3 && (a.dt & (DT_A | DT_B)) && !a.act_b) {
-        auto ok16 = [&](const float* p, int ld, bool kc, int rows, long long s1, long long s2) {
-            return (uintptr_t)p % 16 == 0 && ld % 8 == 0 && (kc ? a.K % 8 == 0 && a.kchunk % 8 == 0 : rows % 8 == 0) &&
-                   (a.nbatch == 1 || (s1 % 8 == 0 && s2 % 8 == 0));
-        };
-        const int m16 = (((a.dt & DT_A) && ok16(a.A, a.lda, AKC, a.M, a.sA1, a.sA2)) ? 1 : 0) |
-                        (((a.dt & DT_B) && ok16(a.B, a.ldb, BKC, a.N, a.sB1, a.sB2)) ? 2 : 0);
-#define GEMM_S16(TT)                                                                       \
-        switch (m16) {                                                                     \
-            case 1: return gemm_launch_t<AKC, BKC, 3, TT, true, 1>(a, grid, s);           \
-            case 2: return gemm_launch_t<AKC, BKC, 3, TT, true, 2>(a, grid, s);           \
-            case 3: return gemm_launch_t<AKC, BKC, 3, TT, true, 3>(a, grid, s);           \
-            default: break;                                                                \
-        }
-        if (T == 2) { GEMM_S16(2) } else { GEMM_S16(1) }
-#undef GEMM_S16
-    }
-#define GEMM_VEC_SWITCH(TT, BFV)                                                          \
-    switch (vec) {                                                                         \
-        case 3: return gemm_launch_t<AKC, BKC, 3, TT, BFV>(a, grid, s);                   \
-        case 2: if (TT == 1) return gemm_launch_t<AKC, BKC, 2, 1, BFV>(a, grid, s);       \
-                return gemm_launch_t<AKC, BKC, 0, TT, BFV>(a, grid, s);                   \
-        case 1: if (TT == 1) return gemm_launch_t<AKC, BKC, 1, 1, BFV>(a, grid, s);       \
-                return gemm_launch_t<AKC, BKC, 0, TT, BFV>(a, grid, s);                   \
-        default: return gemm_launch_t<AKC, BKC, 0, TT, BFV>(a, grid, s);                  \
-    }
-    if (g_gemm_bf16) {
-        if (T == 2) { GEMM_VEC_SWITCH(2, true) }
-        GEMM_VEC_SWITCH(1, true)
-    }
-    if (T == 2) { GEMM_VEC_SWITCH(2, false) }
-    GEMM_VEC_SWITCH(1, false)
-#undef GEMM_VEC_SWITCH
+GemmCall gemm_call_of(const GemmDev& a, int transA, int transB, GemmEntry entry, int per_product = 0) {
+    return GemmCall{a.M, a.N, a.K, a.lda, a.ldb, a.ldc, transA, transB, a.nbatch, a.sA1, a.sA2, a.sB1, a.sB2, a.sC1, a.sC2, a.sR1, a.sR2, a.sBi1, a.sBi2,
+                    a.dt, (uintptr_t)a.A, (uintptr_t)a.B, (uintptr_t)a.C, (uintptr_t)a.bias, (uintptr_t)a.preact, (uintptr_t)a.residual,
+                    a.act != 0, a.act_b != 0, a.bias_row != 0, a.rowsum != nullptr, a.row_scale != nullptr, a.accumulate != 0, a.atomic_out != 0,
+                    entry, per_product, g_queue.open, dlwp_cu_count(), false, false};
 }
-
-}  // namespace
-
-// Tile edge selection.  The 128 x 128 instantiation (T = 2) needs ~200 VGPRs and 74 KB of LDS, i.e. two waves per SIMD,
-// and measured 5-7 % SLOWER than 64 x 64 (T = 1: ~104 VGPRs, four waves per SIMD hide the LDS fragment reads behind the
-// other waves' MFMAs) on the SFNO (M = 512-32768, N = K = 256-512) and FourCastNet-scale (16200 x 3072 x 768) products,
-// so it is only used when DLWP_GEMM_TILE=128 asks for it (kept for re-measurement with bf16 operands).
-// With both operands stored as bf16 (16-byte loads, 4 staging registers per operand) the picture changes for deep products:
-// profiles/r02_gemm_bench.txt, 16200 x 3072 x 768: 395 -> 479 TFLOP/s, 16200 x 768 x 3072 (gx): 438 -> 656; at K = 256-512
-// (SFNO) the 128 tile still loses (264 -> 176), so it is taken from K = 768 on.
-// can_split: no epilogue, so a long K may be cut into slices (weight gradients: few output tiles, K = tokens) -- the slices
-// fill the chip where the tiles alone would not.
-static int gemm_tile_for(int M, int N, long long nbatch, int K = 0, int dt = 0, bool can_split = false) {
-    const int tile_env = dlwp_tune("GEMM_TILE"), forced = tile_env == DLWP_TUNE_UNSET ? 0 : (tile_env == 128 ? 2 : 1);
-    if (M < 128 || N < dlwp_tune_or("GEMM_TILE128_MINN", 128)) return 1;      // (knob: 96-wide outputs on the 128 tile, measurement)
-    const long long tiles = (long long)ceil_div(M, 128) * ceil_div(N, 128) * nbatch;
-    const bool fills = tiles * (can_split ? std::max(1, K / (4 * BK)) : 1) >= 224;
-    if (forced) return forced == 2 && fills ? 2 : 1;
-    return g_gemm_bf16 && (dt & 3) == 3 && K >= 768 && fills ? 2 : 1;
+// the route's plan in the kernel's arguments
+void gemm_apply(GemmDev& a, const GemmRoute& r) {
+    a.kchunk = r.kernel.kchunk;
+    a.splits = r.kernel.splits;
+    a.xcd_splitk = r.kernel.xcd_splitk;
+    a.ntn = r.ntn;
+    a.ntm = r.ntm;
+    a.vec_epi = r.vec_epi;
+    a.wide_epi = r.wide_epi;
 }
-
-static int gemm_dispatch(GemmDev& a, int transA, int transB, int T, void* stream) {
-    // 16-byte loads need every row start and every group of four along the contiguous dimension to be aligned and whole;
-    // decided per operand (a weight matrix with an odd row length must not force scalar loads on the activations)
-    bool vecA = ((uintptr_t)a.A % ((a.dt & DT_A) ? 8 : 16) == 0) && a.lda % 4 == 0 && (transA ? a.M % 4 == 0 : a.K % 4 == 0);
-    bool vecB = ((uintptr_t)a.B % ((a.dt & DT_B) ? 8 : 16) == 0) && a.ldb % 4 == 0 && (transB ? a.K % 4 == 0 : a.N % 4 == 0);
-    if (a.nbatch > 1) {
-        vecA = vecA && a.sA1 % 4 == 0 && a.sA2 % 4 == 0;
-        vecB = vecB && a.sB1 % 4 == 0 && a.sB2 % 4 == 0;
-    }
-    const int vec = (vecA ? 1 : 0) | (vecB ? 2 : 0);
-    a.vec_epi = a.splits == 1 && !a.atomic_out && a.N % 4 == 0 && a.ldc % 4 == 0 && (uintptr_t)a.C % 16 == 0 &&
-                (!a.bias || a.bias_row || (uintptr_t)a.bias % 16 == 0) && (!a.residual || (uintptr_t)a.residual % 16 == 0) &&
-                (!a.preact || (uintptr_t)a.preact % 16 == 0);
-    if (a.nbatch > 1)
-        a.vec_epi = a.vec_epi && a.sC1 % 4 == 0 && a.sC2 % 4 == 0 && a.sR1 % 4 == 0 && a.sR2 % 4 == 0 &&
-                    (a.bias_row || (a.sBi1 % 4 == 0 && a.sBi2 % 4 == 0));
-    const hipStream_t s = (hipStream_t)stream;
-    int rc;
-    const bool trace = dlwp_tune_on("GEMM_TRACE");      // shape census of an eager step: sort | uniq -c
-    if (trace)
+// one product of a plain, batched or channels-first entry: route, zero fill where the split needs it, the slab where the route wants one
+// (slab availability -- stream capture, hipMalloc -- is not the route's business: without one the call is routed again, gemm_p8_tn
+// falling back to gemm_glds_tn and that to its atomic epilogue), then the queue or the launch
+int gemm_run(GemmDev a, int transA, int transB, GemmEntry entry, const char* who, void* stream) {
+    GemmCall c = gemm_call_of(a, transA, transB, entry);
+    GemmRoute r = dlwp_gemm_route(c);
+    DLWP_REQUIRE((long long)a.nbatch * r.caller.splits <= 65535, DLWP_E_UNSUPPORTED, "%s: more than 65535 batches x splits", who);
+    if (r.zero)      // C must start from zero: every batch's [M x N] block (row pitch ldc), or the one block the batches share
+        for (int z = 0; z < (a.atomic_out ? 1 : a.nbatch); ++z)
+            if (int zrc = dlwp_zero_2d_f32(a.C + (z / a.nb2) * a.sC1 + (z % a.nb2) * a.sC2, a.ldc, a.M, a.N, stream)) return zrc;
+    if (dlwp_tune_on("GEMM_TRACE"))      // shape census of an eager step: sort | uniq -c
         fprintf(stderr, "gemm %c%c M=%d N=%d K=%d nb=%lld splits=%d dt=%d vec=%d epi=%d bias=%d res=%d act=%d rowsum=%d\n", transA ? 'T' : 'N',
-                transB ? 'T' : 'N', a.M, a.N, a.K, (long long)a.nbatch, a.splits, a.dt, vec, (int)a.vec_epi, a.bias != nullptr,
+                transB ? 'T' : 'N', a.M, a.N, a.K, (long long)a.nbatch, r.caller.splits, a.dt, r.vec_ab, (int)r.vec_epi, a.bias != nullptr,
                 a.residual != nullptr, a.act, a.rowsum != nullptr);
-    // A is k-contiguous when not transposed ([M][K]); B is k-contiguous when transposed ([N][K])
-    if (!transA && transB) rc = gemm_launch<true, true>(a, vec, T, s);
-    else if (!transA && !transB) rc = gemm_launch<true, false>(a, vec, T, s);
-    else if (transA && transB) rc = gemm_launch<false, true>(a, vec, T, s);
-    else rc = gemm_launch<false, false>(a, vec, T, s);
+    const hipStream_t s = (hipStream_t)stream;
+    while (r.slab && !(a.slab = tn_slab_for(s, r.slab_bytes))) {
+        (r.family == GEMM_P8_TN ? c.no_slab_p8tn : c.no_slab_tn) = true;
+        r = dlwp_gemm_route(c);
+    }
+    gemm_apply(a, r);
+    int rc;
+    if (r.family == GEMM_PARKED) {
+        rc = gemm_queue_park(a, r, s);
+    } else {
+        const GemmProfTag tag = gemm_prof_tag(a);
+        rc = gemm_inst(r, [&](auto k) {
+            return ki_launch(k, dim3(r.grid_x, 1, r.grid_z), dim3(r.block), r.lds, gemm_prof_flops(a), gemm_prof_bytes(a), s, KiTag{tag.s}, a);
+        });
+        // (C accumulates: the caller zeroed it for its own split-K when it does not)
+        if (!rc && r.slab) rc = gemm_slab_reduce_launch(a.slab, a.C, a.M, a.N, a.ldc, r.slices, s);
+    }
     if (rc) return rc;
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
+
+}  // namespace
+
+int g_gemm_bf16 = 0;       // dlwp_set_gemm_precision
+int g_gemm_tile256 = 0;    // dlwp_set_gemm_tile256: 0 by shape (gemm_p8_applies), 1 wherever the kernel applies, -1 never
 
 // internal entry for the channels-first (wide FNO) path: everything dlwp_gemm_batched does plus row bias, GELU on the B
 // operand, a bias-gradient row sum and batches that accumulate into one shared output (dlwpmi_internal.h)
@@ -2062,21 +1780,10 @@ int dlwp_gemm_run(const dlwp_gemm_args& g, hipStream_t stream) {
     const bool epilogue = g.bias || g.act || g.preact || g.residual;
     const bool shared_out = g.nb > 1 && g.sC == 0;
     DLWP_REQUIRE(!(shared_out && epilogue), DLWP_E_INVALID, "gemm_run: batches sharing one output take no epilogue");
-    const long long tiles = (long long)ceil_div(g.N, 64) * ceil_div(g.M, 64) * g.nb;
-    int splits = 1;
-    if (!epilogue && tiles < 256 && g.K >= 8 * BK) splits = (int)std::min<long long>(ceil_div(512, (int)tiles), g.K / (4 * BK));
-    int kchunk = ceil_div(ceil_div(g.K, splits), BK) * BK;
-    splits = ceil_div(g.K, kchunk);
-    DLWP_REQUIRE((long long)g.nb * splits <= 65535, DLWP_E_UNSUPPORTED, "gemm_run: more than 65535 batches x splits");
-    const bool atomic = shared_out || splits > 1;
-    if (atomic && !g.accumulate) {
-        for (int z = 0; z < (shared_out ? 1 : g.nb); ++z)
-            if (int zrc = dlwp_zero_2d_f32(g.C + z * g.sC, g.ldc, g.M, g.N, stream)) return zrc;
-    }
     GemmDev a{g.A, g.B, g.bias, g.residual, g.C, g.preact, g.rowsum, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.act,
-              g.accumulate, kchunk, splits, g.nb, 1, g.res_before_act, 0, 0, 0, g.sA, 0, g.sB, 0, g.sC, 0, g.sR, 0, 0, 0, 0.f,
+              g.accumulate, 0, 0, g.nb, 1, g.res_before_act, 0, 0, 0, g.sA, 0, g.sB, 0, g.sC, 0, g.sR, 0, 0, 0, 0.f,
               g.bias_row, g.act_b, shared_out ? 1 : 0};
-    return gemm_dispatch(a, g.transA, g.transB, 1, stream);
+    return gemm_run(a, g.transA, g.transB, GEMM_RUN, "gemm_run", stream);
 }
 
 extern "C" int dlwp_set_gemm_precision(int mode) {
@@ -2119,33 +1826,12 @@ static int gemm_impl(const float* A, const float* B, float* C, int M, int N, int
     DLWP_REQUIRE(act == 0 || act == 1 || (act == ACT_GELU_STORE_D && preact), DLWP_E_INVALID,
                  "gemm: act must be 0 (none), 1 (gelu) or 7 (gelu with GELU' stored to a non-NULL preact)");
     if (int drc = dtypes_ok(dt, accumulate, "gemm")) return drc;
-    const bool epilogue = bias || act || preact || residual || row_scale || (dt & DT_C);      // a bf16 output takes no split-K atomics
-    const int T = gemm_tile_for(M, N, 1, K, dt, !epilogue);
-    const int tiles = ceil_div(N, 64 * T) * ceil_div(M, 64 * T);
-    int splits = 1;
-    if (!epilogue && tiles < 256 && K >= 8 * BK) splits = std::min(ceil_div(512, tiles), K / (4 * BK));
-    int kchunk = ceil_div(ceil_div(K, splits), BK) * BK;
-    splits = ceil_div(K, kchunk);
-    // a slice count that is a multiple of 8 lets the kernel keep the tiles of a K slice on one XCD (round 5): the nearest such
-    // count at or above the heuristic's that survives the K-step rounding
-    bool xcd_splitk = false;
-    if (splits >= 8 && (dlwp_tune_or("GEMM_XCD_SPLITK", 1) & 1) != 0) {
-        for (int s8 = round_up(splits, 8); s8 >= 8 && s8 > splits / 2; s8 -= 8) {
-            const int kc = ceil_div(ceil_div(K, s8), BK) * BK, sp = ceil_div(K, kc);
-            if (sp % 8 == 0) { kchunk = kc; splits = sp; xcd_splitk = true; break; }
-        }
-    }
-    if (splits > 1 && !accumulate) {
-        const int zrc = dlwp_zero_2d_f32(C, ldc, M, N, stream);
-        if (zrc) return zrc;
-    }
-    GemmDev a{A, B, bias, residual, C, preact, rowsum, M, N, K, lda, ldb, ldc, act, accumulate, kchunk, splits,
+    GemmDev a{A, B, bias, residual, C, preact, rowsum, M, N, K, lda, ldb, ldc, act, accumulate, 0, 0,
               1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.f, 0, 0, 0};
     a.dt = dt;
-    a.xcd_splitk = xcd_splitk ? 1 : 0;
     a.row_scale = row_scale;
     a.scale_rows = scale_rows;
-    return gemm_dispatch(a, transA, transB, T, stream);
+    return gemm_run(a, transA, transB, GEMM_PLAIN, "gemm", stream);
 }
 
 // Several weight-gradient products gW_i (+)= g_i^T x_i (K = tokens) with their bias gradients in ONE launch (gemm_group_kernel):
@@ -2157,73 +1843,41 @@ extern "C" int dlwp_weight_grad_group(const dlwp_wgrad_desc* d, int n, void* str
     for (int i = 0; i < n; ++i)
         DLWP_REQUIRE(d[i].g && d[i].x && d[i].gw && d[i].T > 0 && d[i].N > 0 && d[i].K > 0, DLWP_E_INVALID,
                      "weight_grad_group: product %d has a NULL operand or an empty shape", i);
-    auto single = [&](const dlwp_wgrad_desc& q) {
-        const int dt = (q.g_bf16 ? DT_A : 0) | (q.x_bf16 ? DT_B : 0);
-        return gemm_impl((const float*)q.g, (const float*)q.x, q.gw, q.N, q.K, q.T, q.N, q.K, q.K, 1, 0, nullptr, 0, nullptr, nullptr,
-                         q.accumulate, q.gb, dt, stream);
-    };
     const bool off = dlwp_tune_on("GEMM_NOGROUP");
     // worth it while the products are latency-bound (SFNO C3, 8192 tokens: 5.68 -> 5.49 ms per step); at 32768 tokens each product fills
     // the chip by itself and the bf16 x bf16 one has a faster kernel of its own (11.5 -> 11.9 ms grouped)
     bool grouped = !off && n >= 2 && n <= 3;
     // ... and only small outputs: a FourCastNet-scale product (3072 x 768 over 16200 tokens) belongs on the LDS-DMA kernels (grouped on the
     // 64 x 64 kernel the C5 step went from 17.3 to 26.9 ms)
-    const int maxt_env = dlwp_tune("WGRAD_GROUP_MAXT");
-    const int maxt = maxt_env != DLWP_TUNE_UNSET ? maxt_env : 65536;
+    const int maxt = dlwp_tune_or("WGRAD_GROUP_MAXT", 65536);
     for (int i = 0; i < n; ++i) grouped = grouped && d[i].T <= maxt && (long long)d[i].N * d[i].K <= 512 * 512;
+    // slices: the products of the group share the chip, so the whole group gets the workgroups of one resident round
+    // (896 by default, DLWP_WGRAD_GROUP_WGS): with 512 per product as a lone launch would choose, three products ran a
+    // second partial round and twice the atomics (SFNO C3 step 5.33 -> 5.21 ms; neutral on Pangu / Swin / AFNO)
+    const int per_product = std::max(1, dlwp_tune_or("WGRAD_GROUP_WGS", 896) / n);
     GemmGroup gg{};
-    unsigned gx = 0, gz = 0;
-    for (int i = 0; grouped && i < n; ++i) {
+    for (int i = 0; i < n; ++i) {
         const dlwp_wgrad_desc& q = d[i];
-        const int M = q.N, N = q.K, K = q.T;                  // gW [N][K] = g^T [N][T] . x [T][K]
-        const int dt = (q.g_bf16 ? DT_A : 0) | (q.x_bf16 ? DT_B : 0);
-        const int tiles = ceil_div(N, 64) * ceil_div(M, 64);
-        // slices: the products of the group share the chip, so the whole group gets the workgroups of one resident round
-        // (896 by default, DLWP_WGRAD_GROUP_WGS): with 512 per product as a lone launch would choose, three products ran a
-        // second partial round and twice the atomics (SFNO C3 step 5.33 -> 5.21 ms; neutral on Pangu / Swin / AFNO)
-        const int wgs_env = dlwp_tune("WGRAD_GROUP_WGS");
-        const int per_product = std::max(1, (wgs_env != DLWP_TUNE_UNSET ? wgs_env : 896) / n);
-        int splits = 1;
-        if (tiles < 256 && K >= 8 * BK) splits = std::min(ceil_div(per_product, tiles), K / (4 * BK));
-        const int kchunk = ceil_div(ceil_div(K, splits), BK) * BK;
-        splits = ceil_div(K, kchunk);
-        GemmDev a{(const float*)q.g, (const float*)q.x, nullptr, nullptr, q.gw, nullptr, q.gb, M, N, K, M, N, N, 0, q.accumulate, kchunk, splits,
+        // gW [N][K] = g^T [N][T] . x [T][K]: M = q.N, N = q.K, K = q.T
+        GemmDev a{(const float*)q.g, (const float*)q.x, nullptr, nullptr, q.gw, nullptr, q.gb, q.N, q.K, q.T, q.N, q.K, q.K, 0, q.accumulate, 0, 0,
                   1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.f, 0, 0, 0};
-        a.dt = dt;
-        a.ntn = ceil_div(N, 64);
-        a.ntm = ceil_div(M, 64);
-        const bool vecA = ((uintptr_t)a.A % ((dt & DT_A) ? 8 : 16) == 0) && a.lda % 4 == 0 && a.M % 4 == 0;
-        const bool vecB = ((uintptr_t)a.B % ((dt & DT_B) ? 8 : 16) == 0) && a.ldb % 4 == 0 && a.N % 4 == 0;
-        if (!vecA || !vecB || splits * 1LL > 65535) { grouped = false; break; }
-        a.vec_epi = splits == 1 && a.N % 4 == 0 && a.ldc % 4 == 0 && (uintptr_t)a.C % 16 == 0;
+        a.dt = (q.g_bf16 ? DT_A : 0) | (q.x_bf16 ? DT_B : 0);
+        const GemmRoute r = grouped ? dlwp_gemm_route(gemm_call_of(a, 1, 0, GEMM_WGRAD_MEMBER, per_product)) : GemmRoute{};
+        if (!grouped || r.vec != 3) {      // not the grouped form (a member needs 16-byte loads on both operands): one launch per product
+            for (int j = 0; j < n; ++j)
+                if (int rc = gemm_impl((const float*)d[j].g, (const float*)d[j].x, d[j].gw, d[j].N, d[j].K, d[j].T, d[j].N, d[j].K, d[j].K, 1, 0,
+                                       nullptr, 0, nullptr, nullptr, d[j].accumulate, d[j].gb, (d[j].g_bf16 ? DT_A : 0) | (d[j].x_bf16 ? DT_B : 0), stream))
+                    return rc;
+            return DLWP_OK;
+        }
+        gemm_apply(a, r);
         gg.g[i] = a;
-        // bf16 arrays that allow the 16-byte path (as gemm_launch decides it for a single product); K-step 32 for every member
-        auto ok16 = [&](const float* p, int ld, int rows) { return (uintptr_t)p % 16 == 0 && ld % 8 == 0 && rows % 8 == 0; };
-        gg.s16m[i] = (((dt & DT_A) && ok16(a.A, a.lda, a.M)) ? 1 : 0) | (((dt & DT_B) && ok16(a.B, a.ldb, a.N)) ? 2 : 0);
-        gx = std::max(gx, (unsigned)(a.ntn * a.ntm));
-        gz = std::max(gz, (unsigned)splits);
-    }
-    if (!grouped) {
-        for (int i = 0; i < n; ++i)
-            if (int rc = single(d[i])) return rc;
-        return DLWP_OK;
+        gg.s16m[i] = r.s16m;
     }
     for (int i = 0; i < n; ++i)
         if (gg.g[i].splits > 1 && !gg.g[i].accumulate)
             if (int zrc = dlwp_zero_2d_f32(gg.g[i].C, gg.g[i].ldc, gg.g[i].M, gg.g[i].N, stream)) return zrc;
-    const dim3 grid(gx, n, gz);
-    const hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (g_gemm_bf16) {
-        constexpr int KS = gemm_bf_kstep(0, 1, false, false);
-        const size_t lds = sizeof(float) * 4 * ((64 * (KS + 8) > KS * (64 + 8) ? 64 * (KS + 8) : KS * (64 + 8)) / 2);
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_group_kernel<false, false, 3, 1, true, 0>), lds, "gemm_group"))) return rc;
-        hipLaunchKernelGGL((gemm_group_kernel<false, false, 3, 1, true, 0>), grid, dim3(256), lds, s, gg);
-    } else {
-        const size_t lds = sizeof(float) * 4 * Tile<1>::FLOATS;
-        if ((rc = dlwp_ensure_lds(reinterpret_cast<const void*>(gemm_group_kernel<false, false, 3, 1, false, 0>), lds, "gemm_group"))) return rc;
-        hipLaunchKernelGGL((gemm_group_kernel<false, false, 3, 1, false, 0>), grid, dim3(256), lds, s, gg);
-    }
+    if (int rc = gemm_group_launch(gg, n, (hipStream_t)stream, gemm_wgrad_group_inst)) return rc;
     DLWP_LAUNCH_CHECK();
     return DLWP_OK;
 }
@@ -2249,6 +1903,8 @@ extern "C" int dlwp_gemm_rowscale(const void* A, const void* B, void* C, int M, 
                      (const float*)residual, 0, nullptr, dtypes, stream, row_scale, rows_per_scale);
 }
 
+// (reductions over a long K with few output tiles -- weight gradients of block-diagonal layers -- are split along K inside every
+// batch and combined with float atomics, like the plain entry)
 static int gemm_batched_impl(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                              int transA, int transB, int nb1, int nb2, long long sA1, long long sA2, long long sB1,
                              long long sB2, long long sC1, long long sC2, const float* bias, long long sBi1,
@@ -2263,26 +1919,10 @@ static int gemm_batched_impl(const float* A, const float* B, float* C, int M, in
     DLWP_REQUIRE(!act_is_grad_mul(act) || (residual && !preact), DLWP_E_INVALID,
                  "gemm_batched: act 4-6 and 8 read the saved pre-activation / factor through `residual` and write no `preact`");
     DLWP_REQUIRE(act != ACT_GELU_STORE_D || preact, DLWP_E_INVALID, "gemm_batched: act 7 stores GELU' to `preact`: it must not be NULL");
-    // reductions over a long K with few output tiles (weight gradients of block-diagonal layers): split K inside every
-    // batch and combine with float atomics, like the plain entry
-    const bool epilogue = bias || act || preact || residual || (dt & DT_C);
-    const int T = gemm_tile_for(M, N, (long long)nb1 * nb2, K, dt, !epilogue);
-    const long long tiles = (long long)ceil_div(N, 64 * T) * ceil_div(M, 64 * T) * nb1 * nb2;
-    int splits = 1;
-    if (!epilogue && tiles < 256 && K >= 8 * BK) splits = (int)std::min<long long>(ceil_div(512, (int)tiles), K / (4 * BK));
-    int kchunk = ceil_div(ceil_div(K, splits), BK) * BK;
-    splits = ceil_div(K, kchunk);
-    DLWP_REQUIRE((long long)nb1 * nb2 * splits <= 65535, DLWP_E_UNSUPPORTED, "gemm_batched: more than 65535 batches (%d x %d)", nb1, nb2);
-    if (splits > 1 && !accumulate) {
-        // C must start from zero: every batch's [M x N] block (row pitch ldc)
-        for (int z1 = 0; z1 < nb1; ++z1)
-            for (int z2 = 0; z2 < nb2; ++z2)
-                if (int zrc = dlwp_zero_2d_f32(C + z1 * sC1 + z2 * sC2, ldc, M, N, stream)) return zrc;
-    }
-    GemmDev a{A, B, bias, residual, C, preact, nullptr, M, N, K, lda, ldb, ldc, act, accumulate, kchunk, splits,
+    GemmDev a{A, B, bias, residual, C, preact, nullptr, M, N, K, lda, ldb, ldc, act, accumulate, 0, 0,
               nb1 * nb2, nb2, res_before_act, 0, 0, 0, sA1, sA2, sB1, sB2, sC1, sC2, sR1, sR2, sBi1, sBi2, act_param, 0, 0, 0};
     a.dt = dt;
-    return gemm_dispatch(a, transA, transB, T, stream);
+    return gemm_run(a, transA, transB, GEMM_BATCHED, "gemm_batched", stream);
 }
 
 extern "C" int dlwp_gemm_batched(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
@@ -2303,6 +1943,37 @@ extern "C" int dlwp_gemm_batched_mixed(const void* A, const void* B, void* C, in
     return gemm_batched_impl((const float*)A, (const float*)B, (float*)C, M, N, K, lda, ldb, ldc, transA, transB, nb1, nb2, sA1,
                              sA2, sB1, sB2, sC1, sC2, bias, sBi1, sBi2, act, act_param, (float*)preact, (const float*)residual,
                              sR1, sR2, res_before_act, accumulate, dtypes, stream);
+}
+
+// debug entry: the accounting names, ';'-separated, of the launch a call would make (gemm_slab_reduce_kernel where a slab is wanted: it
+// is taken to be available; a parked product or a weight-gradient group member names its group kernel), then '|' and the plan.  Asks the
+// route and the name formatter the launches use; host state only: no device is touched, no address is dereferenced.
+extern "C" int dlwp_gemm_route_name(int entry, int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB, long long nbatch,
+                                    const long long* strides, int dtypes, const unsigned long long* addr, int flags, int per_product, int cus,
+                                    char* buf, int n) {
+    DLWP_REQUIRE(buf && n > 0 && addr && entry >= GEMM_PLAIN && entry <= GEMM_WGRAD_MEMBER && M > 0 && N > 0 && K > 0 && nbatch >= 1 && lda > 0 &&
+                 ldb > 0 && ldc > 0 && flags >= 0 && flags < 256, DLWP_E_INVALID, "gemm_route_name: bad argument");
+    DLWP_REQUIRE(addr[0] && addr[1] && addr[2], DLWP_E_INVALID, "gemm_route_name: the addresses of A, B and C must not be 0");
+    DLWP_REQUIRE(dtypes >= 0 && dtypes < 16, DLWP_E_INVALID, "gemm_route_name: dtypes is a mask of 1 (A) | 2 (B) | 4 (C, preact) | 8 (residual)");
+    DLWP_REQUIRE(entry != GEMM_WGRAD_MEMBER || per_product >= 1, DLWP_E_INVALID, "gemm_route_name: a group member needs its per_product budget");
+    static const long long none[10] = {};
+    const long long* st = strides ? strides : none;
+    const auto bit = [&](int b) { return (flags >> b & 1) != 0; };
+    const GemmCall c{M, N, K, lda, ldb, ldc, transA, transB, nbatch, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], dtypes,
+                     (uintptr_t)addr[0], (uintptr_t)addr[1], (uintptr_t)addr[2], (uintptr_t)addr[3], (uintptr_t)addr[4], (uintptr_t)addr[5],
+                     bit(0), bit(1), bit(2), bit(3), bit(4), bit(5), bit(6), (GemmEntry)entry, per_product, bit(7), cus > 0 ? cus : 256, false, false};
+    const GemmRoute r = dlwp_gemm_route(c);
+    const auto put = [&](auto k) { ki_format(k.name, buf, (size_t)n); return DLWP_OK; };
+    int rc;
+    if (r.family == GEMM_PARKED) rc = ki_consts([&](auto bf) { return put(gemm_group_any_inst(bf)); }, KiBool{r.bf});
+    else if (entry == GEMM_WGRAD_MEMBER) rc = ki_consts([&](auto bf) { return put(gemm_wgrad_group_inst(bf)); }, KiBool{r.bf});
+    else rc = gemm_inst(r, put);
+    if (rc) return rc;
+    const size_t len = strlen(buf);
+    snprintf(buf + len, (size_t)n - len, "%s|splits=%d kchunk=%d xcd=%d kernel_splits=%d kernel_kchunk=%d kernel_xcd=%d grid=%u,%u block=%u lds=%zu zero=%d",
+             r.slab ? ";gemm_slab_reduce_kernel" : "", r.caller.splits, r.caller.kchunk, r.caller.xcd_splitk, r.kernel.splits, r.kernel.kchunk,
+             r.kernel.xcd_splitk, r.grid_x, r.grid_z, r.block, r.lds, (int)r.zero);
+    return DLWP_OK;
 }
 
 #ifdef DLWP_STAMPS

@@ -578,10 +578,10 @@ int wa_setup(WaDev& a, int B_, int nW, int N, int TB, int ntypes, int heads, int
 // the tiled family's dispatcher (winattn_route.h): the three kernel templates share one parameter space <NDB, NBUF, BF>
 template <class F>
 int tiled_inst(const WaRoute& r, F&& f) {
-    return wa_consts([&](auto NDB, auto NBUF, auto BF) {
-        return f(WA_INST(winattn_fwd_kernel, WA_C(NDB), WA_C(NBUF), WA_B(BF)), WA_INST(winattn_bwd_q_kernel, WA_C(NDB), WA_C(NBUF), WA_B(BF)),
-                 WA_INST(winattn_bwd_kv_kernel, WA_C(NDB), WA_C(NBUF), WA_B(BF)));
-    }, WaOneOf<1, 2, 3, 4>{r.ndb}, WaOneOf<1, 2>{r.n2}, WaBool{r.bf});
+    return ki_consts([&](auto NDB, auto NBUF, auto BF) {
+        return f(KI_INST(winattn_fwd_kernel, KI_C(NDB), KI_C(NBUF), KI_B(BF)), KI_INST(winattn_bwd_q_kernel, KI_C(NDB), KI_C(NBUF), KI_B(BF)),
+                 KI_INST(winattn_bwd_kv_kernel, KI_C(NDB), KI_C(NBUF), KI_B(BF)));
+    }, KiOneOf<1, 2, 3, 4>{r.ndb}, KiOneOf<1, 2>{r.n2}, KiBool{r.bf});
 }
 
 }  // namespace
@@ -644,7 +644,7 @@ extern "C" int dlwp_window_attn_fwd_qrange(const float* qkv, const float* bias_t
     const size_t lds = sizeof(float) * ((size_t)(1 + nbuf) * 64 * (a.dp16 + 4) + (size_t)nbuf * a.dp16 * LDV + 256 + a.TB);
     const dim3 grid(B_ * heads * ((N + QT - 1) / QT)), block(256);
     rc = tiled_inst(r, [&](auto fwd, auto, auto) {
-        return wa_launch(fwd, grid, block, lds, 2 * 2.0 * B_ * heads * (double)N * N * d, 4.0 * B_ * N * heads * d * 4 + 4.0 * B_ * heads * N, stream, a);
+        return ki_launch(fwd, grid, block, lds, 2 * 2.0 * B_ * heads * (double)N * N * d, 4.0 * B_ * N * heads * d * 4 + 4.0 * B_ * heads * N, stream, a);
     });
     if (rc) return rc;
     DLWP_LAUNCH_CHECK();
@@ -733,14 +733,14 @@ extern "C" int dlwp_window_attn_bwd_qrange(const float* qkv, const float* bias_t
     // live accounting: the pair computes the five products of the backward once; q reads qkv, out, gout, writes gq
     const double flops = 2.5 * 2.0 * B_ * heads * (double)N * N * d, bytes = 4.0 * B_ * N * heads * d * 6;
     rc = tiled_inst(r, [&](auto, auto q, auto kv) {
-        if (int rc2 = wa_launch(q, grid, block, lds_q, flops, bytes, stream, a)) return rc2;
-        return wa_launch(kv, grid, block, lds_kv, flops, bytes, stream, a);
+        if (int rc2 = ki_launch(q, grid, block, lds_q, flops, bytes, stream, a)) return rc2;
+        return ki_launch(kv, grid, block, lds_kv, flops, bytes, stream, a);
     });
     if (rc) return rc;
     if (slab) {
         const int nqt = (N + QT - 1) / QT, n_items = (B_ / ntypes) * nqt, chunks = (n_items + FOLD_CH - 1) / FOLD_CH;
         // live accounting: one add per slab partial; the slab is read once, every chunk adds its sums into the table
-        rc = wa_launch(wa_inst(winattn_fold_kernel, wa_name("winattn_fold_kernel")), dim3((TB + 255) / 256, heads * ntypes, chunks), dim3(256), 0,
+        rc = ki_launch(ki_inst(winattn_fold_kernel, ki_name("winattn_fold_kernel")), dim3((TB + 255) / 256, heads * ntypes, chunks), dim3(256), 0,
                        (double)n_items * heads * ntypes * TB, 4.0 * n_items * heads * ntypes * TB + 8.0 * chunks * TB * ntypes * heads, stream,
                        slab, gbias_table, TB, ntypes, heads, nqt, n_items);
         if (rc) return rc;
@@ -763,10 +763,10 @@ extern "C" int dlwp_window_attn_route_name(int direction, int layout, int N, int
     if (r.family != WA_TILED) return dlwp_winattn_small_name(r, buf, n);
     return tiled_inst(r, [&](auto fwd, auto q, auto kv) {
         if (!direction) {
-            wa_format(fwd.name, buf, (size_t)n);
+            ki_format(fwd.name, buf, (size_t)n);
         } else {
-            const int len = wa_format(q.name, buf, (size_t)n);
-            if (len + 1 < n) { buf[len] = ';'; wa_format(kv.name, buf + len + 1, (size_t)(n - len - 1)); }
+            const int len = ki_format(q.name, buf, (size_t)n);
+            if (len + 1 < n) { buf[len] = ';'; ki_format(kv.name, buf + len + 1, (size_t)(n - len - 1)); }
         }
         return DLWP_OK;
     });

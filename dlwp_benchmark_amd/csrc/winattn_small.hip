@@ -24,7 +24,7 @@
 //
 // Families in this file.  Which one a call runs on, and on which instantiation, is decided by dlwp_winattn_route_fwd / _bwd below
 // (winattn_route.h: shape, layout, precision mode and the WINATTN_* knobs -> WaRoute; the tiled family of winattn.hip is one of
-// their answers); ws_launch turns a route into launch geometry and wa_launch launches it:
+// their answers); ws_launch turns a route into launch geometry and ki_launch launches it:
 //   winattn_small_fwd_kernel<NC, NDB, VEC, BF, TOK, IOBF>   forward, one wave per (window, head); TOK: operands in the token layout
 //                                                           through position maps; IOBF: bf16 token tensors
 //   winattn_small_bwd_kernel                                backward, register fragments (fp32 mode, or forced)
@@ -1624,35 +1624,35 @@ WaRoute dlwp_winattn_route_fwd(const WaCall& c) {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ instantiations
-// One dispatch per kernel template: the route's integers become compile-time constants (wa_consts) and f receives the instantiation
-// with its accounting name (WA_INST).
+// One dispatch per kernel template: the route's integers become compile-time constants (ki_consts) and f receives the instantiation
+// with its accounting name (KI_INST).
 template <class F>
 int ws_inst(const WaRoute& r, F&& f) {
-    const WaOneOf<1, 2> ndb_12{r.ndb};
-    const WaOneOf<4, 8> n2_48{r.n2};
+    const KiOneOf<1, 2> ndb_12{r.ndb};
+    const KiOneOf<4, 8> n2_48{r.n2};
     switch (r.family) {
         case WA_WAVE_FWD:
-            return wa_consts([&](auto NC, auto NDB, auto VEC, auto BF, auto TOK, auto IO) {
-                constexpr int nc = WA_C(NC), ndb = WA_C(NDB);
-                constexpr bool vec = WA_B(VEC), bf = WA_B(BF), tok = WA_B(TOK), io = WA_B(IO);
+            return ki_consts([&](auto NC, auto NDB, auto VEC, auto BF, auto TOK, auto IO) {
+                constexpr int nc = KI_C(NC), ndb = KI_C(NDB);
+                constexpr bool vec = KI_B(VEC), bf = KI_B(BF), tok = KI_B(TOK), io = KI_B(IO);
                 // what the routes can reach, and no more: head dims above 32 are <4, 3, true, true, false, .>; the token layout and bf16
                 // tensors take vector loads of bf16 operands, and bf16 tensors in the window layout have at most 64 tokens
                 constexpr bool live = ndb == 3 ? (nc == 4 && vec && bf && !tok) : (tok || io) ? (vec && bf && (tok || nc == 4)) : true;
-                if constexpr (live) return f(WA_INST(winattn_small_fwd_kernel, nc, ndb, vec, bf, tok, io));
-                else return wa_not_built();
-            }, n2_48, WaOneOf<1, 2, 3>{r.ndb}, WaBool{r.vec}, WaBool{r.bf}, WaBool{r.tok}, WaBool{r.io});
+                if constexpr (live) return f(KI_INST(winattn_small_fwd_kernel, nc, ndb, vec, bf, tok, io));
+                else return ki_not_built();
+            }, n2_48, KiOneOf<1, 2, 3>{r.ndb}, KiBool{r.vec}, KiBool{r.bf}, KiBool{r.tok}, KiBool{r.io});
         case WA_WAVE_BWD:
-            return wa_consts([&](auto NDB, auto VEC, auto BF) { return f(WA_INST(winattn_small_bwd_kernel, WA_C(NDB), WA_B(VEC), WA_B(BF))); },
-                             ndb_12, WaBool{r.vec}, WaBool{r.bf});
+            return ki_consts([&](auto NDB, auto VEC, auto BF) { return f(KI_INST(winattn_small_bwd_kernel, KI_C(NDB), KI_B(VEC), KI_B(BF))); },
+                             ndb_12, KiBool{r.vec}, KiBool{r.bf});
         case WA_LDS_BWD2:
-            return wa_consts([&](auto NDB) { return f(WA_INST(winattn_lds_bwd_kernel, WA_C(NDB))); }, WaOneOf<1, 2, 3>{r.ndb});
+            return ki_consts([&](auto NDB) { return f(KI_INST(winattn_lds_bwd_kernel, KI_C(NDB))); }, KiOneOf<1, 2, 3>{r.ndb});
         case WA_LDS_BWD1P:
-            return wa_consts([&](auto NDB, auto NW, auto IO) { return f(WA_INST(winattn_lds_bwd1p_kernel, WA_C(NDB), WA_C(NW), WA_B(IO))); },
-                             ndb_12, n2_48, WaBool{r.io});
+            return ki_consts([&](auto NDB, auto NW, auto IO) { return f(KI_INST(winattn_lds_bwd1p_kernel, KI_C(NDB), KI_C(NW), KI_B(IO))); },
+                             ndb_12, n2_48, KiBool{r.io});
         case WA_LDS_FWD_TOK:
-            return wa_consts([&](auto NC, auto NDB, auto IO) { return f(WA_INST(winattn_lds_fwd_tok_kernel, WA_C(NC), WA_C(NDB), WA_B(IO))); },
-                             n2_48, ndb_12, WaBool{r.io});
-        default: return wa_not_built();
+            return ki_consts([&](auto NC, auto NDB, auto IO) { return f(KI_INST(winattn_lds_fwd_tok_kernel, KI_C(NC), KI_C(NDB), KI_B(IO))); },
+                             n2_48, ndb_12, KiBool{r.io});
+        default: return ki_not_built();
     }
 }
 
@@ -1705,11 +1705,11 @@ int ws_launch(const WaRoute& r, WsDev& a, void* stream) {
             // (Pangu C4 layer 1, 114 pairs x 37 windows: 228 workgroups 177 us, 456: 202, 798: 252)
             a.groups = groups_of("WINATTN_WG_BWD", dlwp_cu_count() * (r.n2 == 8 ? 1 : 2) / (heads * ntypes), a.M, heads, ntypes);
             break;
-        default: return wa_not_built();
+        default: return ki_not_built();
     }
     const dim3 grid((unsigned)(heads * ntypes * a.groups));
-    const int rc = ws_inst(r, [&](const WaInst<WsDev>& k) {
-        return wa_launch(k, grid, dim3(threads), lds, ws_prof_flops(a, backward ? 5 : 2), ws_prof_bytes(a, backward), stream, a);
+    const int rc = ws_inst(r, [&](const KiInst<WsDev>& k) {
+        return ki_launch(k, grid, dim3(threads), lds, ws_prof_flops(a, backward ? 5 : 2), ws_prof_bytes(a, backward), stream, a);
     });
     if (rc) return rc;
     DLWP_LAUNCH_CHECK();
@@ -1719,7 +1719,7 @@ int ws_launch(const WaRoute& r, WsDev& a, void* stream) {
 }  // namespace
 
 int dlwp_winattn_small_name(const WaRoute& r, char* buf, int n) {
-    return ws_inst(r, [&](const WaInst<WsDev>& k) { wa_format(k.name, buf, (size_t)n); return DLWP_OK; });
+    return ws_inst(r, [&](const KiInst<WsDev>& k) { ki_format(k.name, buf, (size_t)n); return DLWP_OK; });
 }
 
 int dlwp_winattn_small_fwd(const WaRoute& r, const float* qkv, const float* table, const float* packed, const int* ia, const int* ib,

@@ -117,6 +117,7 @@ SIGNATURES = {
     "dlwp_wgrad_segments": (_I, [_V, _I, _I, _I, _V, C.c_size_t, _V]),
     "dlwp_gemm_group_begin": (_I, []),
     "dlwp_gemm_group_end": (_I, [_V]),
+    "dlwp_gemm_route_name": (_I, [_I] * 9 + [C.c_longlong, C.POINTER(C.c_longlong), _I, C.POINTER(C.c_ulonglong), _I, _I, _I, C.c_char_p, _I]),
     "dlwp_window_gather": (_I, [_V, _V, _I, _I] + [_V] * 7 + [_V]),
     "dlwp_window_gather_fill": (_I, [_V, _V, _V, _I, _I] + [_V] * 7 + [_V]),
     "dlwp_window_gather_ex": (_I, [_V, _V, _V, _V, _I, _I] + [_V] * 7 + [_I, _V]),

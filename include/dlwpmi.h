@@ -818,6 +818,19 @@ int dlwp_wgrad_segments(const dlwp_wgrad_seg_product* products, int nprod, int n
 /* product alive and unmodified until _end returns (the launches happen there).                                                      */
 int dlwp_gemm_group_begin(void);
 int dlwp_gemm_group_end(void* stream);
+/* Debug: the accounting name(s), ';'-separated, of the kernel(s) a GEMM call would launch under the precision mode, the tile256     */
+/* mode and the tuning knobs in force (gemm_slab_reduce_kernel where the K slices go to a slab, which is taken to be available; a    */
+/* product the open queue would park and a weight-gradient group member name their group kernel), then '|' and the plan:             */
+/* "splits= kchunk= xcd=" (the entry's split-K: C is zeroed first when zero=1), "kernel_splits= kernel_kchunk= kernel_xcd=" (what   */
+/* the kernel runs with), "grid=x,z block= lds=" (bytes).  entry: 0 dlwp_gemm / _mixed / _rowscale, 1 dlwp_gemm_batched*, 2 the      */
+/* channels-first internal entry, 3 a member of dlwp_weight_grad_group (per_product = its share of the group's workgroup slots, M =  */
+/* desc.N, N = desc.K, K = desc.T, transA = 1).  nbatch = nb1 * nb2; strides: NULL or {sA1, sA2, sB1, sB2, sC1, sC2, sR1, sR2,       */
+/* sBi1, sBi2}; addr: the addresses of {A, B, C, bias, preact, residual} as integers (0 = absent; only their alignment is read,      */
+/* nothing is dereferenced); flags: 1 act | 2 act on B | 4 row bias | 8 row sums | 16 row scale | 32 accumulate | 64 batches share  */
+/* the output | 128 a group queue is open; cus: compute units (<= 0: 256).  Reads host state only: works without a device.          */
+int dlwp_gemm_route_name(int entry, int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB, long long nbatch,
+                         const long long* strides, int dtypes, const unsigned long long* addr, int flags, int per_product, int cus,
+                         char* buf, int n);
 
 /* Strided-batched form: batch z = z1*nb2 + z2 (z1 < nb1, z2 < nb2) works on A + z1*sA1 +      */
 /* z2*sA2, B + z1*sB1 + z2*sB2, C (and residual) likewise; strides in floats, 0 = shared.     */

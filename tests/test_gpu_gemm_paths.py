@@ -1,5 +1,6 @@
-"""Every kernel the token GEMM entries (csrc/token_ops.hip: dlwp_gemm_mixed / dlwp_gemm_batched_mixed, gemm_launch) can launch, each case
-pinned to the instantiation it must reach through lib.kernel_accounting and held to a float64 product of the bf16-rounded operands:
+"""Every kernel the token GEMM entries (csrc/token_ops.hip: dlwp_gemm_mixed / dlwp_gemm_batched_mixed, routed by csrc/gemm_route.h) can
+launch, each case pinned to the instantiation it must reach through lib.kernel_accounting (and to what dlwp_gemm_route_name answers for the
+same call) and held to a float64 product of the bf16-rounded operands:
 per output tile of the kernel under test (edge tiles reported on their own), with sentinel rows after M and sentinel columns between N
 and ldc that must come back bit for bit, and bit-identical repeated launches wherever the kernel adds its K slices in a fixed order.
 
@@ -36,6 +37,7 @@ Case table (test_gemm_path[<case id>]; "default" = no knob, the dispatcher's own
 test_fast_path_fuzz draws twelve products per family (glds, p8, glds_tn, p8_tn) inside the family's applicability region and asserts the
 instantiation the draw must reach."""
 import contextlib
+import ctypes
 import math
 
 import numpy as np
@@ -172,17 +174,53 @@ def epi_reference(prod, e, bias, res, c0):
     return y, (pre if e["pre"] else None)
 
 
+ENTRY_PLAIN, ENTRY_BATCHED = 0, 1      # dlwp_gemm_route_name's entry (include/dlwpmi.h)
+FLAG_ACT, FLAG_ROWSUM, FLAG_ACC, FLAG_QUEUE = 1, 8, 32, 128
+ADDRS = ("A", "B", "C", "bias", "preact", "residual")
+
+
+def route_of(call, **addr):
+    """(sorted accounting names, plan text) that dlwp_gemm_route_name answers for a call (product_call / wgrad_call) whose arrays lie at
+    the given addresses (name = address; 0 or missing: absent).  Host state only."""
+    from dlwp_benchmark_amd import lib as L
+    buf = ctypes.create_string_buffer(512)
+    a = (ctypes.c_ulonglong * 6)(*[addr.get(k) or 0 for k in ADDRS])
+    L.check(L.load().dlwp_gemm_route_name(call["entry"], call["M"], call["N"], call["K"], call["lda"], call["ldb"], call["ldc"], call["tA"],
+                                          call["tB"], 1, None, call["dt"], a, call["flags"], 0, 0, buf, len(buf)))
+    names, plan = buf.value.decode().split("|")
+    return sorted(names.split(";")), plan
+
+
+def product_call(M, N, K, layout, epi, arrays=(BF, BF), cpad=8, ldpad=0, queue=False):
+    """the call arguments run_product makes for a product (layout flags, leading dimensions, storage mask, route flags) and the parsed
+    epilogue under "e"; entry: dlwp_gemm_batched_mixed with one batch"""
+    e = parse_epi(epi)
+    tA, tB = int(layout[0] == "t"), int(layout[1] == "t")
+    dt = (1 if arrays[0] == BF else 0) | (2 if arrays[1] == BF else 0) | (4 if e["out"] == BF else 0) | (8 if e["res"] == "res16" else 0)
+    flags = (FLAG_ACT if e["act"] else 0) | (FLAG_ACC if e["acc"] else 0) | (FLAG_QUEUE if queue else 0)
+    return dict(entry=ENTRY_BATCHED, M=M, N=N, K=K, tA=tA, tB=tB, lda=(M if tA else K) + ldpad, ldb=(K if tB else N) + ldpad,
+                ldc=-(-N // 8) * 8 + cpad, dt=dt, flags=flags, e=e, arrays=arrays)
+
+
+def wgrad_call(M, N, K, acc, rowsum):
+    """the call arguments run_wgrad makes: dlwp_gemm_mixed with transA, both operands bf16 arrays"""
+    return dict(entry=ENTRY_PLAIN, M=M, N=N, K=K, tA=1, tB=0, lda=M, ldb=N, ldc=N + 8, dt=3,
+                flags=(FLAG_ACC if acc else 0) | (FLAG_ROWSUM if rowsum else 0))
+
+
+def ptrs(**tensors):
+    return {k: (v.data_ptr() if v is not None else 0) for k, v in tensors.items()}
+
+
 def run_product(cuda, M, N, K, layout, epi, expect, seed, knob=None, mode="bf16", arrays=(BF, BF), cpad=8, ldpad=0, reps=1):
     """C (+)= epilogue(op(A) op(B)) through dlwp_gemm_batched_mixed with layout "nt" (y = x W^T), "nn" (gx = g W) or "tn"
-    (A given as [K][M]); asserts the launched kernels, the tile-local error of every output and the guard regions."""
+    (A given as [K][M]); asserts the launched kernels (and that the route names them), the tile-local error of every output and the
+    guard regions."""
     from dlwp_benchmark_amd import lib as L
     from dlwp_benchmark_amd.token_ops import _gemm_batched
-    e = parse_epi(epi)
+    call = product_call(M, N, K, layout, epi, arrays, cpad, ldpad)
+    e, tA, tB, lda, ldb, ldc = (call[k] for k in ("e", "tA", "tB", "lda", "ldb", "ldc"))
     g = torch.Generator().manual_seed(seed)
-    tA, tB = (1 if layout == "tn" else 0), (1 if layout == "nt" else 0)
-    lda = (M if tA else K) + ldpad
-    ldb = (K if tB else N) + ldpad
-    ldc = -(-N // 8) * 8 + cpad
     A = torch.randn(K if tA else M, lda, generator=g).to(cuda).to(arrays[0])
     B = (torch.randn(N if tB else K, ldb, generator=g) / math.sqrt(K)).to(cuda).to(arrays[1])
     opA = A[:, :M].double().T if tA else A[:, :K].double()
@@ -201,11 +239,13 @@ def run_product(cuda, M, N, K, layout, epi, expect, seed, knob=None, mode="bf16"
             C = C0.clone()
             P = P0.clone() if P0 is not None else None
 
-            def call():
+            def launch():
                 _gemm_batched(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, bias=bias, act=e["act"], act_param=LAM, preact=P, residual=res,
                               res_pre=int(e["res_pre"]), accumulate=int(e["acc"]))
-            names = gemm_names(call)
+            names = gemm_names(launch)
             assert names == expect, (names, expect)
+            routed = route_of(call, **ptrs(A=A, B=B, C=C, bias=bias, preact=P, residual=res))
+            assert routed[0] == names, (routed, names)
             outs.append((C, P))
     tile = tile_of(expect[0])
     tol = fp32_tol(K)
@@ -227,7 +267,8 @@ def run_wgrad(cuda, M, N, K, acc, rowsum, expect, seed, knob=None, reps=1):
     from dlwp_benchmark_amd import lib as L
     from dlwp_benchmark_amd.token_ops import _gemm
     gen = torch.Generator().manual_seed(seed)
-    ldc = N + 8
+    call = wgrad_call(M, N, K, acc, rowsum)
+    ldc = call["ldc"]
     gm = torch.randn(K, M, generator=gen).to(cuda).to(BF)
     x = torch.randn(K, N, generator=gen).to(cuda).to(BF)
     W0 = guarded(M, N, ldc, torch.float32, gen, cuda)
@@ -240,6 +281,8 @@ def run_wgrad(cuda, M, N, K, acc, rowsum, expect, seed, knob=None, reps=1):
             b = b0.clone() if rowsum else None
             names = gemm_names(lambda: _gemm(gm, x, W, M, N, K, M, N, ldc, 1, 0, accumulate=int(acc), rowsum=b))
             assert names == expect, (names, expect)
+            routed = route_of(call, **ptrs(A=gm, B=x, C=W))
+            assert routed[0] == names, (routed, names)
             outs.append((W, b))
     W, b = outs[0]
     check_guards("gW", W, W0, M, N)
@@ -361,10 +404,13 @@ def _draw_epi(rng, allow_acc=True):
     return "+".join(toks)
 
 
-@pytest.mark.parametrize("seed", range(12))
-@pytest.mark.parametrize("family", ["glds", "p8", "glds_tn", "p8_tn"])
-def test_fast_path_fuzz(cuda, family, seed):
-    rng = np.random.default_rng(7000 + 100 * ["glds", "p8", "glds_tn", "p8_tn"].index(family) + seed)
+FUZZ_FAMILIES = ["glds", "p8", "glds_tn", "p8_tn"]
+
+
+def fuzz_draw(family, seed):
+    """the product test_fast_path_fuzz runs for (family, seed): ("product", keyword arguments of run_product) or ("wgrad", those of
+    run_wgrad), the expected kernels among them"""
+    rng = np.random.default_rng(7000 + 100 * FUZZ_FAMILIES.index(family) + seed)
     if family in ("glds", "p8"):
         nn = bool(rng.integers(0, 2))
         if family == "glds":
@@ -387,20 +433,36 @@ def test_fast_path_fuzz(cuda, family, seed):
             expect = [P8K.format(Fa if staged else T, Fa if nn else T, T if wide else Fa)]
             knob = dict(P8, GEMM_P8_STAGED=int(staged))
         epi = _draw_epi(rng)
-        run_product(cuda, M, N, K, "nn" if nn else "nt", epi, expect, seed=seed, knob=knob, cpad=cpad, reps=2 if family == "p8" else 1)
-        return
+        return "product", dict(M=M, N=N, K=K, layout="nn" if nn else "nt", epi=epi, expect=expect, seed=seed, knob=knob, cpad=cpad,
+                               reps=2 if family == "p8" else 1)
     M, N = 8 * int(rng.integers(32 if family == "p8_tn" else 16, 120)), 8 * int(rng.integers(32 if family == "p8_tn" else 16, 120))
     K = int(rng.integers(1024, 3000))
     acc = bool(rng.integers(0, 2))
     rowsum = acc and bool(rng.integers(0, 2))
     if family == "p8_tn":
-        run_wgrad(cuda, M, N, K, acc, rowsum, ["gemm_p8_tn_kernel", REDUCE], seed=seed, knob={"tile256": 1}, reps=2)
-        return
+        return "wgrad", dict(M=M, N=N, K=K, acc=acc, rowsum=rowsum, expect=["gemm_p8_tn_kernel", REDUCE], seed=seed, knob={"tile256": 1}, reps=2)
     kd, atomic = int(rng.choice([32, 64])), int(rng.integers(0, 2))
     slab = not atomic and (-(-M // 128)) * (-(-N // 128)) >= 24
     expect = [f"gemm_glds_tn_kernel<{kd}>"] + ([REDUCE] if slab else [])
-    run_wgrad(cuda, M, N, K, acc, rowsum, sorted(expect), seed=seed, knob={"GEMM_GLDS_TN_KD": kd, "GEMM_TN_ATOMIC": atomic},
-              reps=2 if slab else 1)
+    return "wgrad", dict(M=M, N=N, K=K, acc=acc, rowsum=rowsum, expect=sorted(expect), seed=seed,
+                         knob={"GEMM_GLDS_TN_KD": kd, "GEMM_TN_ATOMIC": atomic}, reps=2 if slab else 1)
+
+
+@pytest.mark.parametrize("seed", range(12))
+@pytest.mark.parametrize("family", FUZZ_FAMILIES)
+def test_fast_path_fuzz(cuda, family, seed):
+    kind, kw = fuzz_draw(family, seed)
+    (run_product if kind == "product" else run_wgrad)(cuda, **kw)
+
+
+def queue_products(mode):
+    """test_gemm_group_queue's products: (M, N, K, tA, tB, A array type, B array type, epilogue)"""
+    lowp = BF if mode == "bf16" else torch.float32          # the fp32 mode reads fp32 arrays
+    return [(100, 72, 64, 0, 1, lowp, lowp, "bias+gelu+pre+bf16out" if mode == "bf16" else "bias+gelu+pre"),
+            (96, 132, 200, 1, 0, torch.float32, lowp, "acc"),
+            (77, 64, 48, 0, 0, lowp, torch.float32, "relu+res32"),
+            (132, 40, 36, 1, 1, torch.float32, torch.float32, "bias+res32+respre"),
+            (4096, 1024, 600, 0, 1, torch.float32, torch.float32, "bias")]       # 5 GFLOP: not parked
 
 
 @pytest.mark.parametrize("mode", ["bf16", "fp32"])
@@ -411,13 +473,7 @@ def test_gemm_group_queue(cuda, mode):
     from dlwp_benchmark_amd import lib as L
     from dlwp_benchmark_amd.token_ops import _gemm_batched
     g = torch.Generator().manual_seed(11 if mode == "bf16" else 12)
-    lowp = BF if mode == "bf16" else torch.float32          # the fp32 mode reads fp32 arrays
-    # (M, N, K, tA, tB, A array type, B array type, epilogue)
-    prods = [(100, 72, 64, 0, 1, lowp, lowp, "bias+gelu+pre+bf16out" if mode == "bf16" else "bias+gelu+pre"),
-             (96, 132, 200, 1, 0, torch.float32, lowp, "acc"),
-             (77, 64, 48, 0, 0, lowp, torch.float32, "relu+res32"),
-             (132, 40, 36, 1, 1, torch.float32, torch.float32, "bias+res32+respre"),
-             (4096, 1024, 600, 0, 1, torch.float32, torch.float32, "bias")]       # 5 GFLOP: not parked
+    prods = queue_products(mode)
     runs = []
     for M, N, K, tA, tB, da, db, epi in prods:
         e = parse_epi(epi)
